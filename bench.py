@@ -1,6 +1,12 @@
 """Benchmark: LPA on the BASELINE.json configs, GTEPS + HBM roofline.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5] [--scale S]
+                    [--dump-outputs DIR] [--full]
+
+A plain run builds the graph, warms up, times the K steps, writes its outputs when
+--dump-outputs is given and prints the result line (the headline keys only).  --full adds
+every other measurement described under "Extra keys" below, each in runs of its own
+after the timed steps.
 
 Workloads (synthetic, generated in HBM; CSR construction not timed):
   C3  R-MAT scale 24, edgefactor 16 (16.7 M V / 268 M E)          default at N = 1
@@ -26,7 +32,15 @@ decide the real call's time, not only converged ones, whatever K / W the caller
 passes.  value = m * 9 * K / t_sum / 1e9 GTEPS (m = input edges of the job).
 W warm-up calls run untimed before.
 
-Extra keys: the BASELINE.md:48 method (median superstep time over iterations
+--dump-outputs DIR: what the last timed step computed, the label vector a caller reads
+after its labelPropagation(maxIter=10) call, written by rank 0 as float64 .npy files:
+`labels.npy` (every vertex when V <= 2^21, else the labels of a fixed, seeded sample of
+2^21 vertices), `labels_index.npy` (the dense vertex id of each entry of labels.npy) and
+`labels_summary.npy` ([V, distinct labels, sum of all V labels], over the whole vector).
+The generators are seeded and the tie-break is deterministic, so equal arguments give
+equal files.
+
+Extra keys (--full): the BASELINE.md:48 method (median superstep time over iterations
 2..maxIter across >= 5 runs, HIP events, concurrent schedule), the wall time of a
 whole lpa_run(10) from reset (`run_maxiter10_ms`, supersteps 1..10 + label gather),
 the per-kernel breakdown of a serialized pass (`roofline`: the al[] rebuild, the longest
@@ -225,6 +239,30 @@ def self_launch(n):
     return subprocess.run(cmd, env=env).returncode
 
 
+DUMP_SAMPLE = 1 << 21   # two float64 files of this many entries: 32 MiB, under the 64 MB a dump may take
+DUMP_SEED = 20261019
+
+
+def dump_outputs(path, lab):
+    """--dump-outputs: the host label vector `lab` (int32, by dense vertex id) as float64
+    .npy files under `path` (every label is below 2^31: exact in float64).  Above
+    DUMP_SAMPLE vertices labels.npy holds a fixed, seeded sample of them (drawn with
+    replacement, the same for every run at this V); the summary covers the whole vector."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    V = lab.size
+    if V > DUMP_SAMPLE:
+        idx = np.random.default_rng(DUMP_SEED).integers(0, V, size=DUMP_SAMPLE)
+    else:
+        idx = np.arange(V)
+    np.save(os.path.join(path, "labels.npy"), lab[idx].astype(np.float64))
+    np.save(os.path.join(path, "labels_index.npy"), idx.astype(np.float64))
+    distinct = int(np.count_nonzero(np.bincount(lab, minlength=V))) if V else 0
+    np.save(os.path.join(path, "labels_summary.npy"),
+            np.array([V, distinct, int(lab.sum(dtype=np.int64))], dtype=np.float64))
+
+
 def quality_entry(g, lab, extra=None):
     """Community count + modularity of labels `lab` on handle g's graph (lpa_quality:
     exact integer sums on the GPU; the symmetrised multigraph LPA votes on)."""
@@ -277,11 +315,19 @@ def main():
     ap.add_argument("--weak", action="store_true",
                     help="N > 1: weak scaling from C3 (R-MAT scale 24 + log2 N; N a power of two)")
     ap.add_argument("--scale", type=int, default=None, help="R-MAT scale override (custom config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-outlier", action="store_true")
-    ap.add_argument("--no-quality", action="store_true", help="skip the community count / modularity report")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the labels of the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the extra keys: per-superstep method, lpa_run(10), "
+                         "per-kernel rooflines, outlier stage, CPU baseline, quality")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-outlier", action="store_true", help="--full: skip the outlier stage")
+    ap.add_argument("--no-quality", action="store_true",
+                    help="--full: skip the community count / modularity report")
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)  # tests: ranks + config only
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # the driver's `bench.py --gpus N`: one rank process per GPU, started here
@@ -347,7 +393,7 @@ def main():
     else:
         g = gfa.Graph(src, dst, V, device=device)
     info = g.info()
-    keep_host = world == 1 and not args.no_cpu_baseline
+    keep_host = args.full and world == 1 and not args.no_cpu_baseline
     if keep_host:
         src_np, dst_np = src.cpu().numpy(), dst.cpu().numpy()
     del src, dst
@@ -381,7 +427,49 @@ def main():
 
     cs = sorted(call_ms)
     progress(f"timed: {value:.1f} GTEPS (per call ms: min {cs[0]:.3f} median {cs[len(cs) // 2]:.3f} "
-             f"max {cs[-1]:.3f}); per-superstep method")
+             f"max {cs[-1]:.3f})")
+    if args.dump_outputs and rank == 0:
+        # the labels the last timed call left (superstep 10), before anything else runs
+        dump_outputs(args.dump_outputs, g.labels())
+        progress(f"outputs written to {args.dump_outputs}")
+    head = {
+        "metric": METRIC,
+        "value": round(value, 3),
+        "unit": "GTEPS",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(t_sum * 1e3 / args.steps, 4),
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "int32",
+        "data": "synthetic",
+        "config": {
+            "workload": workload_text(cfg, config_id) + "; labelPropagation(maxIter=10) "
+                        "(GraphFrames semantics, smallest-label ties)",
+            "config_id": config_id,
+            "vertices": V, "edges": m, "arcs_rank0": info["arcs"],
+            "parallelism": f"1D degree-ranked vertex partition x{world}, RCCL label allgather",
+            "scaling_note": ("weak: R-MAT scale 24 + log2 N, 268 M edges per GPU" if scaling == "weak" else
+                             "strong: the same graph at every N (N = 1 default C3, the north-star config; "
+                             "N > 1 default C4, BASELINE's partitioned config)"),
+        },
+        "timed_window": f"supersteps 2..{MAX_ITER} of each of {args.steps} labelPropagation(maxIter={MAX_ITER}) "
+                        f"calls ({n_timed} supersteps); step = one call",
+        "ms_per_superstep": round(t_sum * 1e3 / n_timed, 4),
+        "call_ms_min_median_max": [round(cs[0], 4), round(cs[len(cs) // 2], 4), round(cs[-1], 4)],
+    }
+    if not args.full:
+        # a plain run ends here: the headline figure needs nothing below
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        g.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    progress("per-superstep method")
     # ---- BASELINE.md:48 method: median superstep time of iterations 2..10 over >= 5
     # runs (HIP events around each superstep, concurrent schedule, graphs replayed) ----
     runs = max(5, args.steps)
@@ -543,32 +631,7 @@ def main():
     }
 
     out_json = {
-        "metric": METRIC,
-        "value": round(value, 3),
-        "unit": "GTEPS",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(t_sum * 1e3 / args.steps, 4),
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "int32",
-        "data": "synthetic",
-        "config": {
-            "workload": workload_text(cfg, config_id) + "; labelPropagation(maxIter=10) "
-                        "(GraphFrames semantics, smallest-label ties)",
-            "config_id": config_id,
-            "vertices": V, "edges": m, "arcs_rank0": info["arcs"],
-            "parallelism": f"1D degree-ranked vertex partition x{world}, RCCL label allgather",
-            "scaling_note": ("weak: R-MAT scale 24 + log2 N, 268 M edges per GPU" if scaling == "weak" else
-                             "strong: the same graph at every N (N = 1 default C3, the north-star config; "
-                             "N > 1 default C4, BASELINE's partitioned config)"),
-        },
-        "timed_window": f"supersteps 2..{MAX_ITER} of each of {args.steps} labelPropagation(maxIter={MAX_ITER}) "
-                        f"calls ({n_timed} supersteps); step = one call",
-        "ms_per_superstep": round(t_sum * 1e3 / n_timed, 4),
-        "call_ms_min_median_max": [round(cs[0], 4), round(cs[len(cs) // 2], 4), round(cs[-1], 4)],
+        **head,
         "baseline_method": {
             "what": f"BASELINE.md:48: median superstep time over iterations 2..{MAX_ITER}, {runs} runs, HIP events",
             "median_iter_ms": round(med_ms, 4),

@@ -1,10 +1,9 @@
 """Generate tests/golden/r9_golden.npz from the reference's own sample data.
 
-Run HERE only (needs /root/reference, absent on the GPU box):
     python tests/golden/make_golden.py
 
-Input: /root/reference/CommunityDetection/data/outlinks_pq/*.snappy.parquet (R9),
-restated into a graph exactly as Graphframes.py:16-73 builds it (package
+Input: tests/golden/outlinks_pq/*.snappy.parquet (R9: the reference's sample data,
+CommunityDetection/data/outlinks_pq, kept here as a fixture), restated into a graph exactly as Graphframes.py:16-73 builds it (package
 ``ingest`` module: null filter, distinct domains, sha1[:8] ids, undeduplicated
 edges).  Expected outputs come from the CPU oracle (oracle/lpa_oracle.c),
 cross-checked against the pure-Python restatement (oracle.lpa_py) before they
@@ -19,7 +18,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-PARQUET_DIR = "/root/reference/CommunityDetection/data/outlinks_pq"
+PARQUET_DIR = os.path.join(HERE, "outlinks_pq")
 
 
 def _load_ingest():

@@ -130,10 +130,9 @@ def test_ingest_restatement(golden):
     assert all(gfa.ingest.node_hash(n) == i for n, i in zip(names[:200], ids[:200]))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/CommunityDetection/data/outlinks_pq"),
-                    reason="reference data only present in the build container")
 def test_ingest_from_reference_parquet(golden):
-    v, e = gfa.ingest.load_outlinks_graph("/root/reference/CommunityDetection/data/outlinks_pq")
+    # the reference's own sample data (its outlinks parquet part), kept as a fixture
+    v, e = gfa.ingest.load_outlinks_graph(os.path.join(ROOT, "tests", "golden", "outlinks_pq"))
     ids, s, d = gfa.ingest.dense_edges(v, e)
     assert np.array_equal(ids, golden["ids"]) and np.array_equal(s, golden["src"])
     assert np.array_equal(d, golden["dst"])
