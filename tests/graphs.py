@@ -156,6 +156,183 @@ def settled_hubs(seed=0, V=20000, n_hub=30, n_mover=40):
     return V, np.concatenate(src).astype(np.int32), np.concatenate(dst).astype(np.int32)
 
 
+def _mul32(x, k):
+    return (np.asarray(x).astype(np.uint64) * np.uint64(k)) & np.uint64(0xFFFFFFFF)
+
+
+def hash_slot(labels, shift):
+    """lpa_iter.hip hash_slot: shift 26 = the 64 buckets of giant_count (wave bins, block
+    rows, units), shift 28 = the 16 buckets of the row bins' giant test."""
+    return (_mul32(labels, 0x9E3779B1) >> np.uint64(shift)).astype(np.int64)
+
+
+def giant_code2(labels):
+    """lpa_iter.hip giant_code2 of a label that is not G: 1 + a 3-way label hash."""
+    return (1 + (((_mul32(labels, 0x9E3779B1) >> np.uint64(24)) * np.uint64(3)) >> np.uint64(8))).astype(np.int64)
+
+
+TIE_DEGREES = (16, 17, 32, 33, 64, 65, 128, 129, 256, 257, 512, 513, 1024, 1025, 4096, 4097, 8192, 8193,
+               10240, 10241, 33281)
+
+
+def tie_anchor_ids(region=256):
+    """The anchor ids of tie_rows, found by restating the library's hashes: G, rivals
+    A < B < G < C < D and E with
+    - A, B in one bucket of every hash (hash_slot 26 / 28, giant_code2), C, D likewise;
+    - A, C, E in three different buckets of every hash (and of comb_bucket, 4 bits);
+    - no rival in a bucket of another pair."""
+    ids = np.arange(region)
+    h26, code, cb = hash_slot(ids, 26), giant_code2(ids), comb_bucket(ids, 4)
+    same = lambda x, y: h26[x] == h26[y] and code[x] == code[y]
+    for G in range(region // 4, region):
+        lo = [(a, b) for a in range(G) for b in range(a + 1, G) if same(a, b)]
+        hi = [(c, d) for c in range(G + 1, region) for d in range(c + 1, region) if same(c, d)]
+        for a, b in lo:
+            for c, d in hi:
+                if code[a] == code[c] or h26[a] >> 2 == h26[c] >> 2 or cb[a] == cb[c]:
+                    continue
+                for e in range(region):
+                    if e in (a, b, G, c, d) or code[e] in (code[a], code[c]):
+                        continue
+                    if len({int(h26[x]) >> 2 for x in (a, c, e)}) == 3 and len({int(cb[x]) for x in (a, c, e)}) == 3:
+                        return dict(G=G, A=a, B=b, C=c, D=d, E=e)
+    raise AssertionError("no anchor ids in the region")
+
+
+def _tie_tables(d, an):
+    """The vote tables of one row of degree d (ISSUE tables (a)-(h)): n = d - 2 engineered
+    votes (two arcs go to the row's blinker pair, whose labels share E's code bucket and
+    no rival's hash bucket).  name -> {label: count}."""
+    G, A, B, C, D, E = (an[k] for k in "GABCDE")
+    n = d - 2
+    c = (n - 1) // 2
+    t = {
+        "a_tie_lo": {G: n // 2, A: n - n // 2},           # even n: tie, A < G wins; odd: A by one
+        "b_tie_hi": {G: n - n // 2, C: n // 2},           # even n: tie, G < C wins; odd: G by one
+        "c_g_plus1_lo": {G: c + 1, A: c, E: n - 2 * c - 1},
+        "c_g_minus1_lo": {G: c, A: c + 1, E: n - 2 * c - 1},
+        "c_g_plus1_hi": {G: c + 1, C: c, E: n - 2 * c - 1},
+        "c_g_minus1_hi": {G: c, C: c + 1, E: n - 2 * c - 1},
+    }
+    # (d) G = g; two rivals of ONE bucket, each below g, together >= g
+    g = n // 2
+    t["d_pair_lo"] = {G: g, A: (n - g + 1) // 2, B: (n - g) // 2}
+    t["d_pair_hi"] = {G: g, C: (n - g + 1) // 2, D: (n - g) // 2}
+    # (e) G = g; rivals in three code buckets at g - 1 (E's bucket: g - 3 + the two blinkers)
+    g = -(-(n + 5) // 4)
+    t["e_three"] = {G: g, A: g - 1, C: g - 1, E: n - 3 * g + 2}
+    t["f_no_g"] = {A: n - 2 * (n // 3), C: n // 3, E: n // 3}
+    # (h) two non-G labels tied (A < C wins), G a minority
+    g = (n - n // 8) // 2
+    t["h_rivals_tie"] = {A: g, C: g, G: n - 2 * g}
+    if d > 8192:   # (g) a rival run of > 1023 consecutive arcs: whole 512-arc units of one bucket
+        t["g_full_unit"] = {G: n // 2 - 256, C: n - n // 2 + 256}
+    return {k: {l: v for l, v in tab.items() if v > 0} for k, tab in t.items()}
+
+
+def tie_mode(table):
+    """Mode of a vote table, the smallest label on a tie."""
+    top = max(table.values())
+    return min(l for l, v in table.items() if v == top)
+
+
+def tie_rows(degrees=TIE_DEGREES, g_mass=90_000, pad_to=0, mult_g=(200, 160, 130), mult_x=(120, 80, 40),
+             cap_g=28, cap_x=36, loops=200):
+    """Layered-anchor fixture with engineered ties and bin-edge degrees at the giant-label
+    decision sites; no random input, every row's mode known analytically.
+
+    Anchors (`loops` self-loops each) keep their ids for ever: G and the rivals of
+    tie_anchor_ids.  Below every anchor hang three layers of pool vertices, vertex i of
+    layer k joined to vertex i of layer k - 1 by mult[k - 1] parallel edges (falling with
+    depth, the fall above the cap of row attachments per pool vertex), so a layer-k vertex
+    takes its anchor's label in superstep k and keeps it.  g_mass vertices on two parallel
+    edges to G put G on more than half of the slots from superstep 1 on.  A test row is a
+    vertex that is only ever a source: its arcs go to the layer-`depth` pools with a chosen
+    count per label (consecutive pool vertices, the cursor moving round the pool), plus one
+    arc to each vertex of its blinker pair -- two vertices joined by three parallel edges,
+    which swap labels every superstep and keep the row dirty.  From superstep depth + 1 on
+    the row's neighbourhood histogram is exactly its table plus two singletons.  (One row per
+    degree and depth has no blinker pair: G on exactly half of ALL its arcs.)
+    G's pools sit in higher degree bins than the rivals' (mult_g vs mult_x), so in a row of
+    G and one rival the rival's arcs are contiguous in the column-sorted row.
+
+    The largest row (> 64 units) carries only tables a, b, g.  pad_to: isolated vertices
+    up to that many ids (the compact graph is a prefix: labels of the first V ids agree).
+
+    Returns V, src, dst, rows [(row id, depth, {label: votes})], G."""
+    an = tie_anchor_ids()
+    G = an["G"]
+    rivals = [an[k] for k in "ABCDE"]
+    region = 256
+    specs = []
+    for d in degrees:
+        for name, tab in _tie_tables(d, an).items():
+            if d > 32768 and name[0] not in "abg":
+                continue
+            for depth in (1, 2, 3):
+                specs.append((d, depth, name, tab))
+        if d <= 32768:
+            # no blinker pair: G on exactly half of the row's arcs, the smaller rival on the other
+            # half (odd d: the rival one more) -- the strict-majority settles' 2 c > deg at equality
+            for depth in (1, 2, 3):
+                specs.append((d, depth, "z_half_pure", {G: d // 2, an["A"]: d - d // 2}))
+    need = {}
+    for d, depth, name, tab in specs:
+        for l, v in tab.items():
+            need[(l, depth)] = need.get((l, depth), 0) + v
+    psize = {l: max(-(-need.get((l, k), 0) // (cap_g if l == G else cap_x)) for k in (1, 2, 3)) for l in [G] + rivals}
+    psize = {l: max(p, 1) for l, p in psize.items()}
+    nxt = region
+    mass = np.arange(nxt, nxt + g_mass)
+    nxt += g_mass
+    fill_mult = (1, 6, 12, 24, 48)     # G-mass vertices of degrees in g1, g8, g16, g32, g64
+    fill = np.arange(nxt, nxt + 8 * len(fill_mult)).reshape(len(fill_mult), 8)
+    nxt += fill.size
+    pools = {}
+    for l in [G] + rivals:
+        for k in (1, 2, 3):
+            pools[(l, k)] = np.arange(nxt, nxt + psize[l])
+            nxt += psize[l]
+    row_ids = np.arange(nxt, nxt + len(specs))
+    nxt += len(specs)
+    # blinker ids: the largest ids; code bucket of E, hash buckets of no rival
+    cand = np.arange(nxt, nxt + 40 * len(specs))
+    bad28 = {int(hash_slot(np.array([x]), 28)[0]) for x in rivals}
+    ok = (giant_code2(cand) == giant_code2(np.array([an["E"]]))[0]) & ~np.isin(hash_slot(cand, 28), list(bad28))
+    blink = cand[ok][: 2 * len(specs)].reshape(-1, 2)
+    assert blink.shape[0] == len(specs)
+    V = int(blink.max()) + 1
+    es, ed = [], []
+
+    def add(s, d, m=1):
+        es.append(np.repeat(np.asarray(s, dtype=np.int64), m))
+        ed.append(np.repeat(np.broadcast_to(np.asarray(d, dtype=np.int64), np.shape(s)), m))
+
+    for l in [G] + rivals:
+        add(np.array([l]), l, loops)
+        mult = mult_g if l == G else mult_x
+        for k in (1, 2, 3):
+            add(pools[(l, k)], pools[(l, k - 1)] if k > 1 else l, mult[k - 1])
+    add(mass, G, 2)
+    for i, m in enumerate(fill_mult):
+        add(fill[i], G, m)
+    cursor = {key: 0 for key in pools}
+    rows = []
+    for i, (d, depth, name, tab) in enumerate(specs):
+        r = int(row_ids[i])
+        for l, v in tab.items():
+            p = pools[(l, depth)]
+            add(np.full(v, r), p[(cursor[(l, depth)] + np.arange(v)) % p.size])
+            cursor[(l, depth)] = (cursor[(l, depth)] + v) % p.size
+        if name != "z_half_pure":
+            u, w = blink[i]
+            add(np.full(3, u), w)
+            add(np.array([r, r]), np.array([u, w]))
+        rows.append((r, depth, dict(tab)))
+    V = max(V, int(pad_to))
+    return V, np.concatenate(es).astype(np.int32), np.concatenate(ed).astype(np.int32), rows, G
+
+
 def code_mix(src, dst, V0):
     """R-MAT edges (V0 vertices) plus structures whose superstep-2 mode is NOT the giant
     label, so that the giant-code settle of superstep 2 (lpa_iter.hip "Giant codes")
