@@ -8,7 +8,7 @@ Two restatements of the same semantics:
 
 * ``lpa`` / ``outlier_l1`` / ``outlier_l2`` -- ctypes bindings to ``liboracle.so``
   (``oracle/lpa_oracle.c``, OpenMP C), usable at full test sizes;
-* ``lpa_py`` / ``outlier_l1_py`` -- pure-Python loops, for tiny known-answer
+* ``lpa_py`` / ``outlier_l1_py`` / ``outlier_l2_py`` -- pure-Python loops, for tiny known-answer
   cases, used to cross-check the C oracle.
 
 Reference anchors: Graphframes.py:81 (``labelPropagation(maxIter=5)``),
@@ -247,3 +247,19 @@ def outlier_l1_py(V, edges, labels):
     thr = threshold_rule_py(size)
     flags = [size[labels[v]] < thr for v in range(V)]
     return size, inc, flags, thr
+
+
+def outlier_l2_py(V, edges, labels, sub_iter):
+    """Literal App. B mode L2: E' = the distinct (s, d) with equal labels, L' = lpa_py on E',
+    per community the threshold rule over the counts of its members' sub-labels.
+    Returns (sub_labels, flags, summary) with the summary keys of ``outlier_l2``."""
+    sub_edges = list(dict.fromkeys((s, d) for s, d in (tuple(e) for e in edges) if labels[s] == labels[d]))
+    sub = lpa_py(V, sub_edges, sub_iter)
+    groups = Counter((labels[v], sub[v]) for v in range(V))
+    thr = {}
+    for l in set(labels[:V]):
+        thr[l] = threshold_rule_py({g: c for g, c in groups.items() if g[0] == l})
+    flags = [groups[(labels[v], sub[v])] < thr[labels[v]] for v in range(V)]
+    flagged_communities = {labels[v] for v in range(V) if flags[v]}
+    return sub, flags, dict(n_communities=len(thr), n_subgroups=len(groups), n_flagged=sum(flags),
+                            n_communities_flagged=len(flagged_communities))

@@ -360,3 +360,271 @@ def code_mix(src, dst, V0):
     es += [np.full(mem.size, hub), np.full(mem.size, lead)]
     ed += [mem, mem]
     return nxt, np.concatenate(es).astype(np.int32), np.concatenate(ed).astype(np.int32)
+
+
+# ---- the outlier stage's engineered fixture (tests/test_gpu_outlier_edges.py) ----
+# per-community multisets of sub-group sizes: 1 = a vertex that stays alone (edgeless, or
+# one of a label-swapping pair), n >= 3 = a clique of n vertices
+OUTLIER_CATALOGUE = (
+    ("n1", [5]),
+    ("n1_single", [1]),
+    ("n2_equal", [3, 3]),
+    ("n9_distinct", [1, 3, 4, 5, 6, 9, 10, 17, 18]),            # k = 0: thr = 18, 8 groups flagged
+    ("n9_equal", [4] * 9),
+    ("n10_unique_min", [1, 3, 3, 4, 5, 6, 7, 8, 9, 33]),        # k = 1: thr = the minimum, nothing below it
+    ("n10_min_tied", [1, 1, 3, 4, 5, 6, 7, 8, 9, 34]),
+    ("n10_equal", [5] * 10),
+    ("n11", [1, 3, 3, 3, 4, 4, 5, 5, 6, 6, 65]),
+    ("n19", [1, 1, 1] + [3] * 8 + [4] * 7 + [66]),
+    ("n20_min_lt_2nd", [1, 3] + [4] * 17 + [129]),              # k = 2: thr = 3, one group flagged
+    ("n20_min_eq_2nd", [1, 1, 3] + [4] * 16 + [130]),           # thr = 1, none
+    ("n20_2nd_eq_3rd", [1, 3, 3] + [4] * 16 + [257]),           # thr = 3, one
+    ("n20_equal", [3] * 20),
+    ("n21", [1, 3, 3] + [5] * 17 + [258]),                      # k = 2: thr = 3, one
+    ("n29", [1, 3] + [4] * 26 + [513]),                         # k = 2: thr = 3, one
+    ("n30", [1, 1, 3] + [4] * 26 + [514]),                      # k = 3: thr = 3, two
+    ("n31", [1, 3, 4] + [5] * 27 + [1100]),                     # k = 3: thr = 4, two
+    ("n100_run_straddles_k", [1] * 7 + [3] * 6 + [4] * 87),     # k = 10: positions 8..13 tied, 7 flagged
+    ("n100_run_ends_at_k", [1] * 5 + [3] * 5 + [4] * 89 + [2100]),   # positions 6..10 tied, 5 flagged
+    ("n100_run_starts_after_k", [1] * 10 + [3] * 6 + [4] * 84),      # positions 11..16 tied, thr = 1, none
+    ("n100_one_below_k", [1] * 9 + [3] * 91),                   # position 10 opens the run, 9 flagged
+)
+
+
+def threshold_of(sizes):
+    """App. B threshold of a multiset of group sizes: the k-th smallest (k = n // 10), the
+    largest when k == 0 (an independent restatement: numpy sort, ascending)."""
+    a = np.sort(np.asarray(sizes, dtype=np.int64))
+    k = a.size // 10
+    return int(a[k - 1] if k > 0 else a[-1])
+
+
+class OutlierGroups:
+    """outlier_groups' result: V, src, dst, labels (the community labelling, an input),
+    comm (community index per vertex), names, sizes (the catalogue, by community index),
+    atom_size (size of each vertex's sub-group), clique_min (the clique's smallest id, own
+    id outside cliques), partner (the pair partner, own id elsewhere), order (vertex ids in
+    construction order: communities, and inside them cliques, are consecutive stretches),
+    atom_start (positions in `order` where an atom begins)."""
+
+    def sub_labels(self, sub_iter):
+        """Closed form of the second LPA's labels after sub_iter >= 2 supersteps."""
+        assert sub_iter >= 2
+        return (self.partner if sub_iter % 2 else self.clique_min).astype(np.int32)
+
+    def closed_form(self):
+        """flags, summary of mode L2 (any sub_iter >= 2) from the catalogue alone."""
+        thr = np.array([threshold_of(sz) for sz in self.sizes])
+        flags = self.atom_size < thr[self.comm]
+        summ = dict(n_communities=len(self.sizes), n_subgroups=sum(len(sz) for sz in self.sizes),
+                    n_flagged=int(flags.sum()), n_communities_flagged=int(np.unique(self.comm[flags]).size))
+        return flags, summ
+
+
+def outlier_groups(big=True, pad_pow2=True, seed=5, n_cross=4000, n_dup=3000):
+    """Communities chosen directly as an input labelling, each a disjoint union of cliques
+    of prescribed sizes plus vertices that stay alone, so every community's multiset of
+    sub-group sizes -- and with it its threshold and its flagged groups -- is known.
+
+    A clique of n >= 3 has every pair joined one-directionally (random orientation) or every
+    pair reciprocally (two directed edges), never mixed: after superstep 1 of the second LPA
+    its smallest vertex holds the second-smallest id and every other the smallest, from
+    superstep 2 on all hold the smallest.  Two self-loops (on the second-smallest and the
+    largest member) in every third clique of n >= 8 change superstep 1 only.  A pair swaps
+    labels every superstep (two groups of size 1), an edgeless vertex keeps its id.
+    Duplicated edges (deduplicated by the stage) and n_cross edges between communities (E'
+    drops them, `incident` counts them) are added, the ids scrambled, the edges shuffled.
+    Community label values are member ids: the smallest for even communities, the largest
+    for odd ones and for the community of vertex V - 1.
+
+    big: the cliques of 1,100 (one-directional: 1,099 arcs per row) and 2,100 (reciprocal:
+    4,198) members; otherwise every clique above 300 shrinks 20-fold (CPU-sized).
+    pad_pow2: one more community of edgeless vertices brings V to a power of two."""
+    rng = np.random.default_rng(seed)
+    cat = [(name, [s if big or s <= 300 else s // 20 for s in sizes]) for name, sizes in OUTLIER_CATALOGUE]
+    n0 = sum(sum(sz) for _, sz in cat)
+    if pad_pow2:
+        V = 1 << int(n0 - 1).bit_length()
+        if V - n0 > 0:
+            cat.append(("pad_singles", [1] * (V - n0)))
+    V = sum(sum(sz) for _, sz in cat)
+    perm = rng.permutation(V).astype(np.int64)
+    comm = np.empty(V, np.int64)
+    atom_size = np.empty(V, np.int64)
+    clique_min = np.arange(V, dtype=np.int64)
+    partner = np.arange(V, dtype=np.int64)
+    atom_start = []
+    es, ed = [], []
+    nxt = 0
+    n_clique = 0
+    for c, (name, sizes) in enumerate(cat):
+        singles = []
+        for s in sizes:
+            ids = perm[nxt:nxt + s]
+            comm[ids] = c
+            atom_size[ids] = s
+            atom_start.append(nxt)
+            nxt += s
+            if s == 1:
+                singles.append(int(ids[0]))
+                continue
+            assert s >= 3
+            iu, ju = np.triu_indices(s, 1)
+            a, b = ids[iu], ids[ju]
+            reciprocal = s == 2100 or (s != 1100 and n_clique % 2 == 1)
+            if reciprocal:
+                es += [a, b]
+                ed += [b, a]
+            else:
+                flip = rng.random(a.size) < 0.5
+                es.append(np.where(flip, b, a))
+                ed.append(np.where(flip, a, b))
+            srt = np.sort(ids)
+            clique_min[ids] = srt[0]
+            partner[ids] = srt[0]
+            if s >= 8 and n_clique % 3 == 0:
+                loops = np.array([srt[1], srt[-1]])
+                es.append(loops)
+                ed.append(loops)
+            n_clique += 1
+        # half of an even community's lone vertices (a quarter of an odd one's) pair up
+        n_pairs = 0 if name == "pad_singles" else len(singles) // (4 if c % 2 else 2)
+        for i in range(n_pairs):
+            u, w = singles[2 * i], singles[2 * i + 1]
+            es.append(np.array([u]))
+            ed.append(np.array([w]))
+            partner[u], partner[w] = w, u
+    assert nxt == V
+    s = np.concatenate(es)
+    d = np.concatenate(ed)
+    dup = rng.integers(0, s.size, size=n_dup)
+    cs = rng.integers(0, V, size=4 * n_cross)
+    cd = rng.integers(0, V, size=4 * n_cross)
+    keep = np.flatnonzero(comm[cs] != comm[cd])[:n_cross]
+    assert keep.size == n_cross
+    cs, cd = cs[keep], cd[keep]
+    s = np.concatenate([s, s[dup], cs, cd[:n_cross // 8], cs[:n_cross // 8]])
+    d = np.concatenate([d, d[dup], cd, cs[:n_cross // 8], cd[:n_cross // 8]])
+    sh = rng.permutation(s.size)
+    f = OutlierGroups()
+    f.V, f.src, f.dst = V, s[sh].astype(np.int32), d[sh].astype(np.int32)
+    lo = np.full(len(cat), V, np.int64)
+    hi = np.full(len(cat), -1, np.int64)
+    np.minimum.at(lo, comm, np.arange(V))
+    np.maximum.at(hi, comm, np.arange(V))
+    use_max = (np.arange(len(cat)) % 2 == 1) | (np.arange(len(cat)) == comm[V - 1])
+    f.labels = np.where(use_max, hi, lo)[comm].astype(np.int32)
+    f.comm, f.atom_size, f.clique_min, f.partner = comm, atom_size, clique_min, partner
+    f.names = [name for name, _ in cat]
+    f.sizes = [list(sz) for _, sz in cat]
+    f.order = perm
+    f.atom_start = np.array(atom_start, dtype=np.int64)
+    return f
+
+
+def sub_edges(src, dst, labels, V):
+    """E' of mode L2, restated in numpy: the distinct directed (s, d) with equal labels."""
+    lab = np.asarray(labels)
+    key = np.unique(src.astype(np.int64) * V + dst.astype(np.int64))
+    ks, kd = key // V, key % V
+    m = lab[ks] == lab[kd]
+    return ks[m].astype(np.int32), kd[m].astype(np.int32)
+
+
+def outlier_l1_np(V, src, dst, labels, key=None):
+    """Mode L1 restated in numpy: np.bincount for the sizes, np.unique over int64 s * V + d
+    keys for the distinct edges (key: those keys, if the caller kept them).
+    Returns size, incident, flags, summary."""
+    lab = np.asarray(labels).astype(np.int64)
+    size = np.bincount(lab, minlength=V)
+    if key is None:
+        key = np.unique(np.asarray(src).astype(np.int64) * V + np.asarray(dst).astype(np.int64))
+    ls, ld = lab[key // V], lab[key % V]
+    inc = np.bincount(ls, minlength=V) + np.bincount(ld[ld != ls], minlength=V)
+    groups = size[size > 0]
+    thr = threshold_of(groups)
+    flags = size[lab] < thr
+    return size, inc, flags, dict(n_groups=int(groups.size), k=int(groups.size // 10), thr=thr,
+                                  n_flagged=int(flags.sum()))
+
+
+def coarse_labels(f, sizes):
+    """A labelling of f's V vertices with the given group sizes (they sum to V): consecutive
+    stretches of the construction order, i.e. the fixture's cliques and communities merged
+    (a stretch may end inside a clique).  Label value: the stretch's smallest member id for
+    even groups, its largest for odd ones."""
+    assert sum(sizes) == f.V
+    lab = np.empty(f.V, np.int32)
+    at = 0
+    for i, n in enumerate(sizes):
+        ids = f.order[at:at + n]
+        lab[ids] = ids.max() if i % 2 else ids.min()
+        at += n
+    return lab
+
+
+def coarse_family(V):
+    """Group-size lists for coarse_labels with the threshold rule's decision on an edge:
+    n groups on both sides of every multiple of 10 in reach, the sizes around position
+    k = n // 10 of the ascending order tied or one apart.  Every list is an engineered
+    prefix, groups of 6, and one last group with the rest of the V vertices.
+    Returns [(name, sizes, dict(n_groups, k, thr, n_flagged))], the dict written down from
+    the rule (k-th smallest, strict <), not computed by code under test."""
+    out = []
+
+    def case(name, n, prefix, thr, n_flagged):
+        mid = [6] * (n - len(prefix) - 1)
+        rest = V - sum(prefix) - sum(mid)
+        assert rest > 16 and len(prefix) + len(mid) + 1 == n
+        out.append((f"n{n}_{name}", prefix + mid + [rest],
+                    dict(n_groups=n, k=n // 10, thr=rest if thr is None else thr, n_flagged=n_flagged)))
+
+    case("all_one", 1, [], None, 0)
+    # k = 0: the largest size is the threshold, every other group is flagged
+    case("distinct", 9, [2, 3, 4, 5, 7, 8, 9, 10], None, 48)
+    case("flat", 9, [6] * 8, None, 48)
+    for n in (10, 11, 19, 20, 21, 99, 100, 101):
+        k = n // 10
+        case("kth_unique", n, [2] * (k - 1) + [3, 4], 3, 2 * (k - 1))      # position k alone at 3
+        case("tie_k_k1", n, [2] * (k - 1) + [3, 3], 3, 2 * (k - 1))        # positions k, k + 1 tied
+        case("tie_km1_k", n, [2] * k + [3], 2, 0)                          # positions k - 1 (if any), k tied
+        case("flat", n, [], 6, 0)                                          # every size but the last equal
+        if k >= 2:
+            case("run_straddles", n, [2] * (k - 2) + [3] * 4, 3, 2 * (k - 2))   # positions k - 1 .. k + 2
+    return out
+
+
+def bh_home_slot(labels):
+    """BlockHist's home slot (lpa_device.h lds_add): the top 12 bits of label * 0x9E3779B1."""
+    return (_mul32(labels, 0x9E3779B1) >> np.uint64(20)).astype(np.int64)
+
+
+BH_PROBES = 8   # lpa_device.h kBhProbes
+
+
+def bh_saturating_labels(V=65536, block=37, heavy_blocks=6, seed=3):
+    """V labels (position i is element i of the kernel's input) that overflow one block's
+    BlockHist for certain.  The home slot shared by the most label values of [0, V) is
+    found; all but one of its labels (>= 12, asserted) stand, twice each, at the start of
+    the 256-element stretch of `block` -- more distinct keys than the BH_PROBES slots a key
+    of that home slot may probe, so at least 4 of them fail every probe whatever the thread
+    order, set `sat` and go to the device histogram directly; the stretch's other elements
+    (random labels, and the heavy one) then probe their home slot only.  The last label of
+    the slot, the heavy one, fills the rest of the stretch's first half and the following
+    heavy_blocks stretches; every other position holds a random label.
+    Returns labels, the colliding labels, the heavy label."""
+    rng = np.random.default_rng(seed)
+    slot = bh_home_slot(np.arange(V))
+    best = int(np.argmax(np.bincount(slot, minlength=4096)))
+    same = np.flatnonzero(slot == best)
+    assert same.size >= 13, same.size
+    rng.shuffle(same)
+    heavy, coll = int(same[0]), same[1:]
+    assert coll.size >= 12 > BH_PROBES
+    lab = rng.integers(0, V, size=V)
+    at = 256 * block
+    assert at + 256 * (heavy_blocks + 1) <= V and 2 * coll.size <= 128
+    lab[at:at + 2 * coll.size] = np.repeat(coll, 2)
+    lab[at + 2 * coll.size:at + 128] = heavy
+    lab[at + 256:at + 256 * (heavy_blocks + 1)] = heavy
+    return lab.astype(np.int32), coll.astype(np.int32), heavy

@@ -5,7 +5,8 @@ Graphframes.py:16-73 into tests/golden/r9_golden.npz by make_golden.py)."""
 import numpy as np
 import pytest
 
-from graphs import degree_mix, random_multigraph, star, two_cliques
+from graphs import (bh_home_slot, bh_saturating_labels, coarse_family, coarse_labels, degree_mix, outlier_groups,
+                    outlier_l1_np, random_multigraph, star, threshold_of, two_cliques)
 
 
 def test_two_cliques_kat(oracle):
@@ -64,11 +65,118 @@ def test_outlier_l1_matches_python(oracle):
     assert all(inc[l] == c for l, c in pinc.items())
 
 
+@pytest.mark.parametrize("labels", ["lpa", "arbitrary"])
+@pytest.mark.parametrize("V,m,seed", [(1, 3, 0), (12, 30, 1), (40, 160, 2), (90, 500, 3), (200, 320, 4)])
+def test_outlier_l2_matches_python(oracle, V, m, seed, labels):
+    """The C oracle's mode L2 against its literal Counter restatement (outlier_l2_py): small
+    random multigraphs (duplicates, self-loops, reciprocal pairs), LPA labels and arbitrary
+    ones (a few communities, label values anywhere in [0, V))."""
+    V, s, d = random_multigraph(V, m, seed)
+    s, d = np.concatenate([s, d[: m // 4]]), np.concatenate([d, s[: m // 4]])   # reciprocal pairs
+    rng = np.random.default_rng(seed)
+    lab = oracle.lpa(V, s, d, 2) if labels == "lpa" else \
+        rng.integers(0, V, size=max(V // 8, 1))[rng.integers(0, max(V // 8, 1), size=V)].astype(np.int32)
+    edges = list(zip(s.tolist(), d.tolist()))
+    for it in (1, 2, 3, 5, 8):
+        sub, flags, summ = oracle.outlier_l2(V, s, d, lab, it)
+        psub, pflags, psumm = oracle.outlier_l2_py(V, edges, lab.tolist(), it)
+        assert sub.tolist() == psub, it
+        assert flags.tolist() == pflags, it
+        assert summ == psumm, it
+
+
 def test_threshold_rule_lst_minus_zero(oracle):
     # n < 10 groups -> k = 0 -> lst[-0] == lst[0] = the LARGEST size (Graphframes.py:136)
     assert oracle.threshold_rule_py({1: 5, 2: 3, 3: 1}) == 5
     sizes = {i: i for i in range(1, 21)}   # n = 20 -> k = 2 -> 2nd smallest
     assert oracle.threshold_rule_py(sizes) == 2
+
+
+# (sizes in ascending order, threshold, groups flagged): ties around position k = n // 10
+THRESHOLD_CASES = [
+    ([1, 2, 3, 4, 5, 6, 7, 8, 9], 9, 8),                 # n = 9: k = 0, the largest
+    ([4] * 9, 4, 0),
+    ([2] + [3] * 9, 2, 0),                               # n = 10: k = 1, the smallest; nothing is below it
+    ([2, 2] + [3] * 8, 2, 0),
+    ([5] * 10, 5, 0),
+    ([1] + [3] * 10, 1, 0),                              # n = 11
+    ([1, 1] + [3] * 17, 1, 0),                           # n = 19: still k = 1
+    ([1, 3] + [4] * 18, 3, 1),                           # n = 20: k = 2, smallest < 2nd
+    ([1, 1] + [4] * 18, 1, 0),                           # smallest = 2nd
+    ([1, 3, 3] + [4] * 17, 3, 1),                        # 2nd = 3rd
+    ([7] * 20, 7, 0),
+    ([1, 3, 3] + [4] * 18, 3, 1),                        # n = 21: k = 2
+    ([1] * 7 + [3] * 6 + [4] * 87, 3, 7),                # n = 100: k = 10, positions 8..13 tied
+    ([1] * 5 + [3] * 5 + [4] * 90, 3, 5),                # the run ends at position k
+    ([1] * 10 + [3] * 6 + [4] * 84, 1, 0),               # the run starts at position k + 1
+    ([1] * 9 + [3] * 91, 3, 9),                          # position k opens the run
+]
+
+
+@pytest.mark.parametrize("sizes,thr,n_flagged_groups", THRESHOLD_CASES,
+                         ids=[f"n{len(c[0])}_{i}" for i, c in enumerate(THRESHOLD_CASES)])
+def test_threshold_rule_ties_around_k(oracle, sizes, thr, n_flagged_groups):
+    """Hand-written thresholds at n = 9, 10, 11, 19, 20, 21, 100 with tied sizes around
+    position k: the Python rule, the numpy restatement of the tests, and the C oracle (an
+    edgeless graph whose labelling has exactly these group sizes, in shuffled order)."""
+    n = len(sizes)
+    rng = np.random.default_rng(n)
+    shuffled = rng.permutation(sizes)
+    assert oracle.threshold_rule_py({100 + i: int(c) for i, c in enumerate(shuffled)}) == thr
+    assert threshold_of(shuffled) == thr
+    V = int(sum(sizes))
+    lab = np.repeat(np.cumsum(shuffled) - 1, shuffled).astype(np.int32)   # label = the group's last vertex
+    none = np.zeros(0, np.int32)
+    size, inc, flags, summ = oracle.outlier_l1(V, none, none, lab)
+    assert (summ["n_groups"], summ["k"], summ["thr"]) == (n, n // 10, thr)
+    assert np.array_equal(flags, size[lab] < thr)
+    assert np.unique(lab[flags]).size == n_flagged_groups
+    assert summ["n_flagged"] == sum(c for c in sizes if c < thr)
+
+
+def test_outlier_groups_fixture_closed_form(oracle):
+    """tests/graphs.py outlier_groups at CPU size (the cliques above 300 shrunk): the
+    oracle's mode L2 reproduces the closed-form sub-labels, flags and summary at
+    sub_iter 2, 3, 4, 5 and 8; its mode L1 equals the numpy restatement."""
+    f = outlier_groups(big=False)
+    assert f.V == 4096 and (f.labels == f.V - 1).any()
+    assert {len(sz) for sz in f.sizes} >= {1, 2, 9, 10, 11, 19, 20, 21, 29, 30, 31, 100}
+    flags, summ = f.closed_form()
+    assert (summ["n_flagged"], summ["n_communities_flagged"]) == (86, 10)
+    for it in (2, 3, 4, 5, 8):
+        sub, fl, sm = oracle.outlier_l2(f.V, f.src, f.dst, f.labels, it)
+        assert np.array_equal(sub, f.sub_labels(it)), it
+        assert np.array_equal(fl, flags) and sm == summ, it
+    size, inc, fl1, s1 = oracle.outlier_l1(f.V, f.src, f.dst, f.labels)
+    nsize, ninc, nfl, ns1 = outlier_l1_np(f.V, f.src, f.dst, f.labels)
+    assert np.array_equal(size, nsize) and np.array_equal(inc, ninc) and np.array_equal(fl1, nfl) and s1 == ns1
+    # every member of a community shares its label, which is one of the members
+    assert np.array_equal(f.comm[f.labels], f.comm)
+
+
+def test_coarse_family_is_what_it_says(oracle):
+    """coarse_family's hand-written (n_groups, k, thr, n_flagged) against the oracle and the
+    numpy restatement on the labellings coarse_labels makes of them."""
+    f = outlier_groups(big=False)
+    seen = set()
+    for name, sizes, want in coarse_family(f.V):
+        lab = coarse_labels(f, sizes)
+        _, _, _, summ = oracle.outlier_l1(f.V, f.src, f.dst, lab)
+        assert summ == want, name
+        assert outlier_l1_np(f.V, f.src, f.dst, lab)[3] == want, name
+        seen.add(want["n_groups"])
+    assert seen == {1, 9, 10, 11, 19, 20, 21, 99, 100, 101}
+
+
+def test_bh_saturating_labels():
+    """The BlockHist overflow fixture: >= 12 labels of one home slot in one 256-element
+    stretch (more than the 8 probes reach), the heavy label of the same slot after them."""
+    lab, coll, heavy = bh_saturating_labels()
+    slots = bh_home_slot(np.append(coll, heavy))
+    assert coll.size >= 12 and np.unique(coll).size == coll.size and (slots == slots[0]).all()
+    stretch = lab[256 * 37:256 * 38]
+    assert np.isin(coll, stretch).all() and heavy not in coll.tolist()
+    assert (lab[256 * 38:256 * 44] == heavy).all()
 
 
 def test_r9_fixture_facts(golden):
