@@ -8,9 +8,9 @@ include/lpa.h); importing this package does not load it -- the first call does,
 and fails loudly if it has not been built.
 """
 from .graph import Graph, Loopback, comm_unique_id, gen_chunglu, gen_rmat, gen_sbm, run_ranks
-from .graphframe import (GraphFrame, IndexedGraph, OutlierResult, index_graph, label_propagation,
-                         outlier_scores)
+from .graphframe import (GraphFrame, IndexedGraph, OutlierResult, connected_components, index_graph,
+                         label_propagation, outlier_scores)
 from . import ingest
 
 __all__ = ["Graph", "Loopback", "run_ranks", "GraphFrame", "IndexedGraph", "OutlierResult", "comm_unique_id", "gen_chunglu", "gen_rmat",
-           "gen_sbm", "index_graph", "ingest", "label_propagation", "outlier_scores"]
+           "gen_sbm", "connected_components", "index_graph", "ingest", "label_propagation", "outlier_scores"]

@@ -87,6 +87,13 @@ class LpaQualitySummary(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LpaComponentsSummary(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int64) for k in ("n_components", "n_singletons", "largest_size", "largest_id")]
+
+    def to_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class LpaOutlierSummary(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in (
         "n_groups", "k", "threshold", "n_flagged", "n_communities", "n_communities_flagged",
@@ -127,6 +134,7 @@ SIGNATURES = {
                                           ctypes.POINTER(LpaOutlierSummary)]),
     "lpa_degrees": (ctypes.c_int, [_vp, _i32p]),
     "lpa_quality": (ctypes.c_int, [_vp, _vp, ctypes.c_int32, _vp]),
+    "lpa_components": (ctypes.c_int, [_vp, _vp, ctypes.c_int32, _vp, ctypes.POINTER(LpaComponentsSummary)]),
     "lpa_loopback_create": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(_vp)]),
     "lpa_loopback_abort": (None, [_vp]),
     "lpa_loopback_destroy": (None, [_vp]),

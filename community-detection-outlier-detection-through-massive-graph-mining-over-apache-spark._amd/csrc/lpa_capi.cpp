@@ -626,6 +626,20 @@ int lpa_quality(lpa_graph* g, const int32_t* labels, int32_t labels_on_device, l
   return quality(g, labels, labels_on_device, out);
 }
 
+int lpa_components(lpa_graph* g, int32_t* comp_out, int32_t out_is_device, int64_t* size_out,
+                   lpa_components_summary* summary) {
+  if (!g || (!comp_out && g->V > 0)) {
+    set_error("null handle or output");
+    return LPA_EINVAL;
+  }
+  if (g->m > 0 && !g->e_src) {
+    set_error("lpa_components of a distributed job runs on rank 0 (the rank that keeps the edge list)");
+    return LPA_EINVAL;
+  }
+  LPA_HIP(hipSetDevice(g->device));
+  return components(g, comp_out, out_is_device, size_out, summary);
+}
+
 int lpa_degrees(lpa_graph* g, int32_t* deg_out) {
   if (!g || (!deg_out && g->V > 0)) {
     set_error("null handle or output");

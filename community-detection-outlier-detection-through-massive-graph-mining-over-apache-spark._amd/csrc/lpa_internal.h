@@ -480,4 +480,8 @@ int outlier(lpa_graph* g, const int32_t* labels, int32_t labels_on_device, int32
             uint8_t* flags, lpa_outlier_summary* summary, int32_t out_on_device);
 int quality(lpa_graph* g, const int32_t* labels, int32_t labels_on_device, lpa_quality_summary* out);
 
+// connected components (lpa_cc.hip)
+int components(lpa_graph* g, int32_t* comp_out, int32_t out_is_device, int64_t* size_out,
+               lpa_components_summary* summary);
+
 }  // namespace lpa

@@ -304,6 +304,44 @@ class Graph:
         _lib.check(self._lib.lpa_quality(self._handle(), ptr, on_dev, ctypes.byref(q)))
         return q.to_dict()
 
+    # -- connected components ---------------------------------------------------
+    def components(self, out=None, sizes: bool = False):
+        """Connected components of the undirected view of the input multigraph
+        (lpa_components): ``comp[v]`` is the smallest dense id of v's component.  Host int32
+        array by default, or written into the int32 device tensor ``out`` (this handle's
+        device, ``num_vertices`` entries).  ``sizes=True`` returns ``(comp, sizes, summary)``:
+        ``sizes[c]`` (int64, in the memory ``comp`` is in) holds the member count at every
+        component id c and 0 elsewhere; ``summary`` is a dict of n_components, n_singletons,
+        largest_size, largest_id.  The labels and the LPA state are not touched."""
+        V = self.num_vertices
+        size = None
+        if out is not None and _is_device_tensor(out):
+            import torch
+
+            if out.dtype != torch.int32:
+                raise ValueError(f"out must be int32, got {out.dtype}")
+            if out.device.index != self.device:
+                raise ValueError(f"out must be on cuda:{self.device}, got {out.device}")
+            if out.numel() != V or not out.is_contiguous():
+                raise ValueError(f"out must hold {V} contiguous entries")
+            comp, ptr, on_dev = out, out.data_ptr(), 1
+            if sizes:
+                size = torch.empty(V, dtype=torch.int64, device=out.device)
+            torch.cuda.current_stream(out.device).synchronize()   # the library works on its own stream
+            size_ptr = size.data_ptr() if sizes else None
+        elif out is not None:
+            raise ValueError("out must be an int32 device tensor")
+        else:
+            comp = np.empty(V, dtype=np.int32)
+            ptr, on_dev = comp.ctypes.data, 0
+            if sizes:
+                size = np.empty(V, dtype=np.int64)
+            size_ptr = size.ctypes.data if sizes else None
+        summ = _lib.LpaComponentsSummary()
+        _lib.check(self._lib.lpa_components(self._handle(), ptr, on_dev, size_ptr,
+                                            ctypes.byref(summ) if sizes else None))
+        return (comp, size, summ.to_dict()) if sizes else comp
+
 
 class Loopback:
     """In-process collective group of ``nranks`` handles on one device (the

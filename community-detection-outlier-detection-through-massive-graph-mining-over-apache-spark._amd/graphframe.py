@@ -33,6 +33,8 @@ import pandas as pd
 from .graph import Graph
 
 ID, SRC, DST, LABEL = "id", "src", "dst", "label"
+COMPONENT = "component"
+CC_ALGORITHMS = ("graphframes", "graphx")
 
 
 def _check_max_iter(maxIter):
@@ -41,6 +43,12 @@ def _check_max_iter(maxIter):
     if maxIter <= 0:
         # GraphX LabelPropagation.run: require(maxSteps > 0, ...)
         raise ValueError(f"requirement failed: Maximum of steps must be greater than 0, but got {maxIter}")
+
+
+def _check_cc_algorithm(algorithm):
+    if algorithm not in CC_ALGORITHMS:
+        # graphframes.lib.ConnectedComponents.setAlgorithm: require(supportedAlgorithms.contains(value), ...)
+        raise ValueError(f"Supported algorithms are {{graphx, graphframes}}: {algorithm}")
 
 
 def _check_schema(v: pd.DataFrame, e: pd.DataFrame):
@@ -149,6 +157,20 @@ class GraphFrame:
         dense = self._gpu_graph().run(int(maxIter))
         return _attach(self._v, ig, {LABEL: _label_values(ig, dense)})
 
+    def connectedComponents(self, algorithm: str = "graphframes", checkpointInterval: int = 2,
+                            broadcastThreshold: int = 1000000) -> pd.DataFrame:
+        """``GraphFrame.connectedComponents``: vertices + ``component`` (int64), the
+        smallest member of each vertex's connected component (direction, duplicates and
+        self-loops ignored) -- its original id for integral ids (the value GraphFrames
+        returns), its dense index in ascending id order otherwise, as for ``label``.
+        ``algorithm`` must be "graphframes" or "graphx" (both name the one GPU algorithm
+        here); ``checkpointInterval`` and ``broadcastThreshold`` steer Spark's execution
+        of the GraphFrames algorithm and are accepted and ignored."""
+        _check_cc_algorithm(algorithm)
+        ig = self._indexed()
+        dense = self._gpu_graph().components()
+        return _attach(self._v, ig, {COMPONENT: _label_values(ig, dense)})
+
     def dense_labels(self, maxIter: int) -> np.ndarray:
         _check_max_iter(maxIter)
         return self._gpu_graph().run(int(maxIter))
@@ -175,6 +197,15 @@ def label_propagation(vertices: pd.DataFrame, edges: pd.DataFrame, maxIter: int,
     gf = GraphFrame(vertices, edges, device=device)
     try:
         return gf.labelPropagation(maxIter)
+    finally:
+        gf.close()
+
+
+def connected_components(vertices: pd.DataFrame, edges: pd.DataFrame, device: int = 0) -> pd.DataFrame:
+    """Function form of ``GraphFrame(vertices, edges).connectedComponents()``."""
+    gf = GraphFrame(vertices, edges, device=device)
+    try:
+        return gf.connectedComponents()
     finally:
         gf.close()
 

@@ -287,6 +287,29 @@ typedef struct lpa_quality_summary {
 } lpa_quality_summary;
 int lpa_quality(lpa_graph* g, const int32_t* labels, int32_t labels_on_device, lpa_quality_summary* out);
 
+/*
+ * Connected components of the undirected view of the input multigraph (edge direction,
+ * duplicate edges and self-loops make no difference; a vertex with no edge is its own
+ * component).  comp_out[v], by dense id, is the SMALLEST dense id of v's component:
+ * GraphX's "lowest vertex id in the component", and for integral ids the value
+ * GraphFrame.connectedComponents returns.  A pure function of (V, edge set): identical
+ * across runs, edge orders, handles and devices.  size_out (nullable, V entries):
+ * size_out[c] = members of the component whose id is c, 0 at every other index.  Both
+ * arrays are host memory unless out_is_device; summary is nullable.  V == 0: success,
+ * nothing written.  Concurrent union-find over the kept edge list (one pass); the labels
+ * and every other piece of lpa_step's state are neither read nor written, nothing is kept
+ * on the handle.  On a distributed job (nranks > 1) only rank 0 keeps the edge list this
+ * needs; the other ranks return LPA_EINVAL.  Since ABI 8.
+ */
+typedef struct lpa_components_summary {
+  int64_t n_components;  /* components, single vertices included            */
+  int64_t n_singletons;  /* components of exactly one vertex                */
+  int64_t largest_size;  /* members of the largest component (0 if V == 0)  */
+  int64_t largest_id;    /* its id; the smallest id on a tie; -1 if V == 0  */
+} lpa_components_summary;
+int lpa_components(lpa_graph* g, int32_t* comp_out, int32_t out_is_device,
+                   int64_t* size_out, lpa_components_summary* summary);
+
 /* Symmetrised degree of every vertex (dense ids), host output. */
 int lpa_degrees(lpa_graph* g, int32_t* deg_out);
 
@@ -297,8 +320,9 @@ int lpa_degrees(lpa_graph* g, int32_t* deg_out);
  * writes min(info_size, sizeof) bytes of this header's struct and zeroes the rest of a
  * larger caller struct: use it for the later fields.  lpa_abi_version() returns the
  * library's LPA_ABI_VERSION, so a binding can check the header it was built for.
- * ABI 7: lpa_graph_create_hostcoll, host_allgathers, the frozen unsized get_info. */
-#define LPA_ABI_VERSION 7
+ * ABI 7: lpa_graph_create_hostcoll, host_allgathers, the frozen unsized get_info.
+ * ABI 8: lpa_components. */
+#define LPA_ABI_VERSION 8
 int lpa_abi_version(void);
 int lpa_graph_get_info(const lpa_graph* g, lpa_graph_info* info);
 int lpa_graph_get_info_sized(const lpa_graph* g, lpa_graph_info* info, int64_t info_size);
