@@ -94,6 +94,14 @@ class LpaComponentsSummary(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LpaTriangleSummary(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int64) for k in ("n_triangles", "simple_edges", "wedges", "n_in_triangle",
+                                              "max_count", "max_count_id")]
+
+    def to_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class LpaOutlierSummary(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in (
         "n_groups", "k", "threshold", "n_flagged", "n_communities", "n_communities_flagged",
@@ -135,6 +143,7 @@ SIGNATURES = {
     "lpa_degrees": (ctypes.c_int, [_vp, _i32p]),
     "lpa_quality": (ctypes.c_int, [_vp, _vp, ctypes.c_int32, _vp]),
     "lpa_components": (ctypes.c_int, [_vp, _vp, ctypes.c_int32, _vp, ctypes.POINTER(LpaComponentsSummary)]),
+    "lpa_triangle_count": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int32, ctypes.POINTER(LpaTriangleSummary)]),
     "lpa_loopback_create": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(_vp)]),
     "lpa_loopback_abort": (None, [_vp]),
     "lpa_loopback_destroy": (None, [_vp]),

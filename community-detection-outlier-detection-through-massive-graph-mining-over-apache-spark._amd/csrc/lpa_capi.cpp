@@ -237,6 +237,9 @@ int create_common(int32_t device, hipStream_t stream, const int32_t* src, const 
   if (const char* f = getenv("LPA_FUSED_BINS")) g->fused_bins = atoi(f) < 0 ? 0 : atoi(f) > 2 ? 2 : atoi(f);
   if (const char* f = getenv("LPA_UNITS_PURE")) g->units_pure = atoi(f) ? 1 : 0;
   if (const char* f = getenv("LPA_KEEP_BITS")) g->keep_bits = atoi(f) ? 1 : 0;
+  if (const char* f = getenv("LPA_TC_SHORT")) g->tc_short = atoi(f) < 0 ? 0 : atoi(f);
+  if (const char* f = getenv("LPA_TC_WAVE")) g->tc_wave = atoi(f) < 0 ? 0 : atoi(f) > kTcWaveMax ? kTcWaveMax : atoi(f);
+  if (const char* f = getenv("LPA_TC_LDS")) g->tc_lds = atoi(f) < 0 ? 0 : atoi(f) > kTcLdsMax ? kTcLdsMax : atoi(f);
   if (const char* f = getenv("LPA_CONV_STREAMS")) g->conv_streams = atoi(f) < 1 ? 1 : atoi(f) > 3 ? 3 : atoi(f);
   // internal builds (the outlier stage's L2 sub-graph): the locality order is a
   // gather-locality heuristic worth its two atomic passes only on a graph that runs
@@ -638,6 +641,20 @@ int lpa_components(lpa_graph* g, int32_t* comp_out, int32_t out_is_device, int64
   }
   LPA_HIP(hipSetDevice(g->device));
   return components(g, comp_out, out_is_device, size_out, summary);
+}
+
+int lpa_triangle_count(lpa_graph* g, int64_t* count_out, int64_t* simple_degree_out, int32_t out_is_device,
+                       lpa_triangle_summary* summary) {
+  if (!g || (!count_out && g->V > 0)) {
+    set_error("null handle or output");
+    return LPA_EINVAL;
+  }
+  if (g->m > 0 && !g->e_src) {
+    set_error("lpa_triangle_count of a distributed job runs on rank 0 (the rank that keeps the edge list)");
+    return LPA_EINVAL;
+  }
+  LPA_HIP(hipSetDevice(g->device));
+  return triangle_count(g, count_out, simple_degree_out, out_is_device, summary);
 }
 
 int lpa_degrees(lpa_graph* g, int32_t* deg_out) {

@@ -79,6 +79,12 @@ constexpr int64_t kHotMinSlots = 4ll << 20;
 // (ncls = 8 x phases classes: block group x streams classes x, x + 8, ... one phase after
 // another, so an XCD's gathers cover 1 / ncls of the label vector at a time)
 constexpr int kMaxBlkClasses = 32;
+// triangle counting (lpa_tc.hip): default and largest out-list lengths of its kernel forms
+constexpr int kTcShort = 8;           // 8 lanes per row up to this length
+constexpr int kTcWaveMax = 1024;      // a wave per row, the list in 4 KB of the wave's LDS
+constexpr int kTcLdsMax = 15360;      // a block per row, the list in 60 KB of LDS (with the team's
+                                      //   offsets under the 64 KB a launch gets without opting in,
+                                      //   two blocks per CU; a longer list needs > 1.1e8 simple edges)
 __host__ __device__ inline uint32_t col_class(int32_t c, uint32_t ncls) { return ((uint32_t)c >> 10) & (ncls - 1u); }
 
 struct Segment {   // one unit of a seg-bin row
@@ -319,6 +325,11 @@ struct lpa_graph {
   int64_t blk_off[lpa::kMaxBlkClasses + 1] = {}; // class x: pieces [blk_off[x], blk_off[x + 1])
   int64_t blk_a0 = 0;                       // arcs [0, blk_a0) are listed (a multiple of 512)
   int64_t blk_rows = 0;                     // rows in (class, column) order
+  // triangle counting (lpa_tc.hip): out-list lengths up to which a row takes the group
+  // form, the wave form and the block form with its list in LDS (longer: in global memory)
+  int tc_short = lpa::kTcShort;             // LPA_TC_SHORT (>= 0; 0: no row takes the group form)
+  int tc_wave = lpa::kTcWaveMax;            // LPA_TC_WAVE  (0 .. kTcWaveMax)
+  int tc_lds = lpa::kTcLdsMax;              // LPA_TC_LDS   (0 .. kTcLdsMax)
   int serial = 0;                           // LPA_SERIAL=1: all tally kernels on one stream (profiling)
   int use_graphs = 1;                       // LPA_GRAPHS=0: no captured superstep graphs
   // captured supersteps: [0, 4) converged per (cur, par); [4, 12) supersteps 2 and 3 per
@@ -483,5 +494,9 @@ int quality(lpa_graph* g, const int32_t* labels, int32_t labels_on_device, lpa_q
 // connected components (lpa_cc.hip)
 int components(lpa_graph* g, int32_t* comp_out, int32_t out_is_device, int64_t* size_out,
                lpa_components_summary* summary);
+
+// triangles per vertex of the simple undirected graph (lpa_tc.hip)
+int triangle_count(lpa_graph* g, int64_t* count_out, int64_t* simple_degree_out, int32_t out_is_device,
+                   lpa_triangle_summary* summary);
 
 }  // namespace lpa

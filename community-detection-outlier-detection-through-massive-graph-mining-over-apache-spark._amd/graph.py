@@ -342,6 +342,46 @@ class Graph:
                                             ctypes.byref(summ) if sizes else None))
         return (comp, size, summ.to_dict()) if sizes else comp
 
+    # -- triangles ----------------------------------------------------------------
+    def triangle_count(self, out=None, stats: bool = False):
+        """Triangles per vertex of the canonical simple undirected graph of the input
+        multigraph (lpa_triangle_count: self-loops dropped, direction ignored, duplicates
+        collapsed): ``count[v]`` is the number of triangles that contain v.  Host int64
+        array by default, or written into the int64 device tensor ``out`` (this handle's
+        device, ``num_vertices`` entries).  ``stats=True`` returns ``(count, simple_degree,
+        summary)``: ``simple_degree[v]`` (int64, in the memory ``count`` is in) is the number
+        of distinct neighbours of v; ``summary`` is a dict of n_triangles, simple_edges,
+        wedges, n_in_triangle, max_count, max_count_id.  The labels and the LPA state are
+        not touched."""
+        V = self.num_vertices
+        deg = None
+        if out is not None and _is_device_tensor(out):
+            import torch
+
+            if out.dtype != torch.int64:
+                raise ValueError(f"out must be int64, got {out.dtype}")
+            if out.device.index != self.device:
+                raise ValueError(f"out must be on cuda:{self.device}, got {out.device}")
+            if out.numel() != V or not out.is_contiguous():
+                raise ValueError(f"out must hold {V} contiguous entries")
+            count, ptr, on_dev = out, out.data_ptr(), 1
+            if stats:
+                deg = torch.empty(V, dtype=torch.int64, device=out.device)
+            torch.cuda.current_stream(out.device).synchronize()   # the library works on its own stream
+            deg_ptr = deg.data_ptr() if stats else None
+        elif out is not None:
+            raise ValueError("out must be an int64 device tensor")
+        else:
+            count = np.empty(V, dtype=np.int64)
+            ptr, on_dev = count.ctypes.data, 0
+            if stats:
+                deg = np.empty(V, dtype=np.int64)
+            deg_ptr = deg.ctypes.data if stats else None
+        summ = _lib.LpaTriangleSummary()
+        _lib.check(self._lib.lpa_triangle_count(self._handle(), ptr, deg_ptr, on_dev,
+                                                ctypes.byref(summ) if stats else None))
+        return (count, deg, summ.to_dict()) if stats else count
+
 
 class Loopback:
     """In-process collective group of ``nranks`` handles on one device (the

@@ -34,6 +34,7 @@ from .graph import Graph
 
 ID, SRC, DST, LABEL = "id", "src", "dst", "label"
 COMPONENT = "component"
+COUNT = "count"
 CC_ALGORITHMS = ("graphframes", "graphx")
 
 
@@ -171,6 +172,32 @@ class GraphFrame:
         dense = self._gpu_graph().components()
         return _attach(self._v, ig, {COMPONENT: _label_values(ig, dense)})
 
+    def triangleCount(self) -> pd.DataFrame:
+        """``GraphFrame.triangleCount``: vertices + ``count`` (int64), the number of
+        triangles passing through each vertex.  As in GraphX ``TriangleCount`` the graph
+        is first made canonical: self-loops dropped, direction ignored, duplicate edges
+        collapsed."""
+        ig = self._indexed()
+        return _attach(self._v, ig, {COUNT: self._gpu_graph().triangle_count()})
+
+    def clusteringCoefficient(self) -> pd.DataFrame:
+        """Local clustering coefficient per vertex -- this package's own addition, not a
+        GraphFrames call (like ``degrees`` and ``outlierScores``).  Returns vertices +
+        ``count`` (triangles through the vertex, int64), ``degree`` (distinct neighbours
+        in the simple undirected graph, int64) and ``lcc`` (float64) =
+        2 count / (degree (degree - 1)), 0.0 where degree < 2, computed in numpy from the
+        exact integers.  ``.attrs["transitivity"]`` is 3 T / wedges of the whole graph
+        (0.0 without wedges)."""
+        ig = self._indexed()
+        count, deg, summ = self._gpu_graph().triangle_count(stats=True)
+        pairs = deg * (deg - 1)
+        lcc = np.zeros(count.shape, np.float64)
+        np.divide(2.0 * count, pairs, out=lcc, where=pairs > 0)
+        out = _attach(self._v, ig, {COUNT: count, "degree": deg, "lcc": lcc})
+        wedges = summ["wedges"]
+        out.attrs["transitivity"] = 3.0 * summ["n_triangles"] / wedges if wedges > 0 else 0.0
+        return out
+
     def dense_labels(self, maxIter: int) -> np.ndarray:
         _check_max_iter(maxIter)
         return self._gpu_graph().run(int(maxIter))
@@ -206,6 +233,15 @@ def connected_components(vertices: pd.DataFrame, edges: pd.DataFrame, device: in
     gf = GraphFrame(vertices, edges, device=device)
     try:
         return gf.connectedComponents()
+    finally:
+        gf.close()
+
+
+def triangle_count(vertices: pd.DataFrame, edges: pd.DataFrame, device: int = 0) -> pd.DataFrame:
+    """Function form of ``GraphFrame(vertices, edges).triangleCount()``."""
+    gf = GraphFrame(vertices, edges, device=device)
+    try:
+        return gf.triangleCount()
     finally:
         gf.close()
 

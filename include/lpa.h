@@ -310,6 +310,34 @@ typedef struct lpa_components_summary {
 int lpa_components(lpa_graph* g, int32_t* comp_out, int32_t out_is_device,
                    int64_t* size_out, lpa_components_summary* summary);
 
+/*
+ * Triangles per vertex (GraphX TriangleCount / GraphFrame.triangleCount) of the canonical
+ * simple undirected graph of the input multigraph: self-loops dropped, direction ignored,
+ * duplicates collapsed (a->b, b->a and any number of repeats of either are one edge {a,b}).
+ * count_out[v], by dense id (V entries, required), is the number of unordered vertex
+ * triples containing v that are pairwise adjacent; its sum is 3 T; a vertex in no triangle,
+ * or with no edge, gets 0.  int64: a hub can sit in more than 2^31 triangles.  A pure
+ * function of (V, edge set): identical across runs, edge orders, edge directions, handles
+ * and devices.  simple_degree_out (nullable, V entries): d(v), the distinct neighbours of v
+ * other than v.  Both arrays are host memory unless out_is_device; summary is nullable.
+ * V == 0: success, nothing written, summary {0,0,0,0,0,-1}.  The call blocks until the
+ * work is done.  Sorted-set intersection over the simple graph oriented by (degree, id)
+ * (DESIGN.md "Triangle counting"); all working memory is stream-ordered temporaries, the
+ * labels and every other piece of lpa_step's state are neither read nor written, nothing
+ * is kept on the handle.  On a distributed job (nranks > 1) only rank 0 keeps the edge
+ * list this needs; the other ranks return LPA_EINVAL.  Since ABI 9.
+ */
+typedef struct lpa_triangle_summary {
+  int64_t n_triangles;    /* T = sum(count) / 3                                        */
+  int64_t simple_edges;   /* undirected distinct non-loop edges                        */
+  int64_t wedges;         /* sum_v d(v) (d(v) - 1) / 2, d = simple degree              */
+  int64_t n_in_triangle;  /* vertices with count > 0                                   */
+  int64_t max_count;      /* largest count (0 if none)                                 */
+  int64_t max_count_id;   /* its dense id, the smallest on a tie; -1 if V == 0         */
+} lpa_triangle_summary;   /* 48 bytes */
+int lpa_triangle_count(lpa_graph* g, int64_t* count_out, int64_t* simple_degree_out,
+                       int32_t out_is_device, lpa_triangle_summary* summary);
+
 /* Symmetrised degree of every vertex (dense ids), host output. */
 int lpa_degrees(lpa_graph* g, int32_t* deg_out);
 
@@ -321,8 +349,9 @@ int lpa_degrees(lpa_graph* g, int32_t* deg_out);
  * larger caller struct: use it for the later fields.  lpa_abi_version() returns the
  * library's LPA_ABI_VERSION, so a binding can check the header it was built for.
  * ABI 7: lpa_graph_create_hostcoll, host_allgathers, the frozen unsized get_info.
- * ABI 8: lpa_components. */
-#define LPA_ABI_VERSION 8
+ * ABI 8: lpa_components.
+ * ABI 9: lpa_triangle_count. */
+#define LPA_ABI_VERSION 9
 int lpa_abi_version(void);
 int lpa_graph_get_info(const lpa_graph* g, lpa_graph_info* info);
 int lpa_graph_get_info_sized(const lpa_graph* g, lpa_graph_info* info, int64_t info_size);
