@@ -463,9 +463,9 @@ int init_labels(lpa_graph* g) {
   LPA_HIP(hipMemsetAsync(g->fcnt, 0, sizeof(int32_t) * 32, g->stream));
   LPA_HIP(hipMemsetAsync(g->counters, 0, sizeof(unsigned long long) * 8, g->stream));
   if (g->gword) {
-    LPA_HIP(hipMemsetAsync(g->gword + 2, 0, sizeof(int32_t), g->stream));  // abits stale
-    LPA_HIP(hipMemsetAsync(g->gword + 9, 0, sizeof(int32_t), g->stream));  // no abits pass ran
-    LPA_HIP(hipMemsetAsync(g->gword + 5, 0, sizeof(int32_t), g->stream));  // no giant-code refresh pending
+    LPA_HIP(hipMemsetAsync(g->gword + GW_ABITS_OK, 0, sizeof(int32_t), g->stream));  // abits stale
+    LPA_HIP(hipMemsetAsync(g->gword + GW_ABITS_PASS, 0, sizeof(int32_t), g->stream));  // no abits pass ran
+    LPA_HIP(hipMemsetAsync(g->gword + GW_CODE, 0, sizeof(int32_t), g->stream));  // no code refresh pending
   }
   g->cur = 0;
   g->since_reset = 0;
@@ -603,8 +603,8 @@ int finish_build(lpa_graph* g, int32_t* deg_own, int64_t m) {
     LPA_TRY(dev_alloc(g, (void**)&g->ugc, sizeof(uint32_t) * (g->n_segs > 0 ? g->n_segs : 1)));
     LPA_TRY(dev_alloc(g, (void**)&g->umx, sizeof(uint32_t) * (g->n_segs > 0 ? g->n_segs : 1)));
     LPA_TRY(dev_alloc(g, (void**)&g->ulist2, sizeof(int32_t) * (g->n_segs > 0 ? g->n_segs : 1)));
-    LPA_TRY(dev_alloc(g, (void**)&g->gdec, sizeof(int32_t) * 4));
-    LPA_HIP(hipMemsetAsync(g->gdec, 0, sizeof(int32_t) * 4, s));
+    LPA_TRY(dev_alloc(g, (void**)&g->gdec, sizeof(int32_t) * kGdecLen));
+    LPA_HIP(hipMemsetAsync(g->gdec, 0, sizeof(int32_t) * kGdecLen, s));
     LPA_TRY(dev_alloc(g, (void**)&g->glist, sizeof(int32_t) * (g->n_hub > 0 ? g->n_hub : 1)));
     g->hub_uoff = seg_off;  // the seg bin is exactly the hub rows (deg > kSegArcs)
     // first unit of the k_lpa_block rows
@@ -646,8 +646,8 @@ int finish_build(lpa_graph* g, int32_t* deg_own, int64_t m) {
 
   // ---- labels (replicated, ping-pong) ----
   LPA_TRY(dev_alloc(g, (void**)&g->gbits, sizeof(uint32_t) * ((g->vpad + 63) / 64 * 2)));
-  LPA_TRY(dev_alloc(g, (void**)&g->gword, sizeof(int32_t) * 16));
-  LPA_HIP(hipMemsetAsync(g->gword, 0, sizeof(int32_t) * 16, s));
+  LPA_TRY(dev_alloc(g, (void**)&g->gword, sizeof(int32_t) * kGwordLen));
+  LPA_HIP(hipMemsetAsync(g->gword, 0, sizeof(int32_t) * kGwordLen, s));
   LPA_TRY(dev_alloc(g, (void**)&g->abits, sizeof(unsigned long long) * ((g->arcs + 63) / 64 + 1)));
   LPA_TRY(dev_alloc(g, (void**)&g->lab[0], sizeof(int32_t) * g->vpad));
   LPA_TRY(dev_alloc(g, (void**)&g->lab[1], sizeof(int32_t) * g->vpad));
@@ -668,7 +668,7 @@ int finish_build(lpa_graph* g, int32_t* deg_own, int64_t m) {
 #endif
   g->gather = LPA_GATHER_OK && P == 1 && !g->pooled && !g->no_scatter && 4 * g->vpad <= (int64_t(4) << 20) && g->n_hub == 0 &&
               g->bin_begin[BIN_W2] == g->bin_begin[BIN_SEG] && g->arcs > 0;
-  // giant codes (lpa_iter.hip): the LDS hot-set rebuild's label vectors (one GPU, or the
+  // giant codes (lpa_codes.h): the LDS hot-set rebuild's label vectors (one GPU, or the
   // rank-strided form of a partitioned job: every rank codes its own arcs against the G
   // of the replicated vector), and a superstep 2 whose hub rows take the giant decision
   // (block mode, or no hub rows)
@@ -708,7 +708,7 @@ int finish_build(lpa_graph* g, int32_t* deg_own, int64_t m) {
   return LPA_OK;
 }
 
-// The class-blocked rebuild's piece lists (lpa_iter.hip rebuild_pieces) over the first
+// The class-blocked rebuild's piece lists (lpa_refresh.hip rebuild_pieces) over the first
 // H rows (in (class, column) order): per class, every row's class segment in <= 64-arc
 // pieces, row after row, then padding to a multiple of 8 pieces; class 7 also lists
 // the positions up to blk_a0, the 512-aligned start of the plain stream.

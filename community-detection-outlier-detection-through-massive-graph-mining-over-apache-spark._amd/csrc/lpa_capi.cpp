@@ -704,7 +704,7 @@ int fill_info(const lpa_graph* g, lpa_graph_info* info) {
   if (g->code_ok && g->gword) {
     LPA_HIP(hipSetDevice(g->device));
     int32_t w = 0;
-    LPA_HIP(hipMemcpyAsync(&w, g->gword + 5, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    LPA_HIP(hipMemcpyAsync(&w, g->gword + GW_CODE, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
     LPA_HIP(hipStreamSynchronize(g->stream));
     info->code_refresh = w;
   }

@@ -1,4 +1,5 @@
-// Device helpers shared by the superstep kernels (lpa_iter.hip, lpa_hub.hip).
+// Device helpers shared by the superstep kernels (lpa_iter.hip, lpa_refresh.hip, lpa_hub.hip)
+// and the other stages' kernels.
 //
 // A vote tally is packed into one 64-bit word  (count << 32) | ~label : the
 // maximum word is the highest count and, among equal counts, the smallest label,
@@ -57,6 +58,25 @@ __device__ __forceinline__ u32 wave_sum_u32(u32 v) {
          (u32)__builtin_amdgcn_readlane((int)v, 32) + (u32)__builtin_amdgcn_readlane((int)v, 48);
 }
 
+__device__ __forceinline__ u32 wave_max_u32(u32 v) {
+  v = max(v, dpp_u32<0xB1>(v));
+  v = max(v, dpp_u32<0x4E>(v));
+  v = max(v, dpp_u32<0x141>(v));
+  v = max(v, dpp_u32<0x140>(v));
+  return max(max((u32)__builtin_amdgcn_readlane((int)v, 0), (u32)__builtin_amdgcn_readlane((int)v, 16)),
+             max((u32)__builtin_amdgcn_readlane((int)v, 32), (u32)__builtin_amdgcn_readlane((int)v, 48)));
+}
+// u64 max as two 32-bit reductions (the high words, then the low words of the lanes
+// holding that high word): each DPP step is one v_max_u32 instead of two moves, a
+// 64-bit compare and two selects -- fewer VALU issues, a longer dependent chain, so it
+// serves only the issue-bound g64 row hash (C2 60.4 -> 61.6 GTEPS; as every kernel's
+// wave max, C3's latency-bound converged supersteps lost 1.5 %)
+__device__ __forceinline__ u64 wave_max_u64_split(u64 v) {
+  const u32 hi = wave_max_u32((u32)(v >> 32));
+  const u32 lo = wave_max_u32((u32)(v >> 32) == hi ? (u32)v : 0u);
+  return ((u64)hi << 32) | lo;
+}
+
 __device__ __forceinline__ u32 hash_slot(u32 label, int shift) {
   return (label * 0x9E3779B1u) >> shift;
 }
@@ -97,6 +117,22 @@ __device__ __forceinline__ int lds_insert_bounded(u64* tab, int shift, u32 mask,
   }
   atomicOr(err, 2);
   return -1;
+}
+
+// Continue an LDS insert of `word` whose probe at slot h hit another key (the tally
+// kernels' wave-owned tables, never full; lds_probe_word<false> below is the same walk
+// with the error word's plumbing, kept apart so that those kernels' code stays as it is).
+__device__ __forceinline__ int lds_probe(u64* tab, u32 mask, u64 word, u32 h) {
+  const u32 key = (u32)word;
+  while (true) {
+    h = (h + 1u) & mask;
+    const u64 old = atomicCAS(&tab[h], 0ull, word);
+    if (old == 0ull) return (int)h;
+    if ((u32)old == key) {
+      atomicAdd(&tab[h], word & 0xFFFFFFFF00000000ull);
+      return -1;
+    }
+  }
 }
 
 // Continue the insert of tally word `word` (count << 32 | ~label) whose first

@@ -41,6 +41,7 @@
 #include <climits>
 
 #include "lpa_internal.h"
+#include "lpa_schedule.h"
 
 namespace lpa {
 
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(256) void k_exch_compact(const int32_t* __restrict_
     }
     return;
   }
-  const int32_t G = gword[0];
+  const int32_t G = gword[GW_G];
   const int64_t nwords = slice >> 6;
   const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
   const int64_t nwaves = (int64_t)gridDim.x * 4;
@@ -193,7 +194,7 @@ __global__ __launch_bounds__(256) void k_exch_compact(const int32_t* __restrict_
 __global__ void k_giant_apply(const int4* __restrict__ Lc, int4* __restrict__ Ln,
                               const unsigned long long* __restrict__ bm, int64_t n4, int64_t own4_begin,
                               int64_t own4_end, const int32_t* __restrict__ gword) {
-  const int32_t G = gword[0];
+  const int32_t G = gword[GW_G];
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
     if (q >= own4_begin && q < own4_end) continue;
     const u32 b = (u32)(bm[q >> 4] >> ((q & 15) * 4)) & 0xFu;
@@ -401,7 +402,7 @@ int exchange_collective(lpa_graph* g, const int32_t* Lc, int32_t* Ln, bool first
   if (!first) {
     LPA_HIP(hipMemsetAsync(g->xpair, 0, 2 * sizeof(unsigned long long), s));   // [2]: the kernel
     // converged supersteps: the frontier lists of this superstep's tally (g->par)
-    const bool list_mode = g->since_reset >= kDenseSupersteps + 2;
+    const bool list_mode = converged_now(g);
     ListBounds lbd;
     for (int b = 0; b <= LPA_NBINS; ++b) lbd.b[b] = g->bin_begin[b];
     hipLaunchKernelGGL(k_exch_compact, dim3(grid_of(S / kCompactWords, 4096)), dim3(256), 0, s, Lc + g->own_begin,

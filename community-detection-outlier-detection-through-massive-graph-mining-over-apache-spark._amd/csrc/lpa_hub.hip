@@ -26,6 +26,7 @@
 // independent of the (non-deterministic) order in which words are staged.
 // In the converged supersteps every hub takes the k_hub_small path.
 #include "lpa_device.h"
+#include "lpa_schedule.h"
 
 namespace lpa {
 
@@ -194,15 +195,15 @@ __device__ __forceinline__ void queue_row(int64_t h, int T, int nu, int lane,
 // Superstep 2's giant-label decision for the hub rows [0, h_end) (after
 // k_lpa_units_giant): row h's G votes S_g = sum of its units' ugc, and any other
 // label's row count is at most S_m = sum of its units' umx (each unit's fullest
-// bucket).  On the 2-bit giant codes (gsel[5], k_lpa_units_code2) umx packs a unit's
+// bucket).  On the 2-bit giant codes (gsel[GW_CODE], k_lpa_units_code2) umx packs a unit's
 // three bucket counts (10 bits each) and S_m = the fullest of the three row sums -- the
 // row-level bucket test, not a sum of unit maxima.  S_g > S_m: G is the strict mode and
 // is written.  Otherwise the row is
 // tallied exactly: a unit-tallied row (h < hb2) gets wcount[h] = 0 and its units in
-// ulist2 (count ndec[0]), a block-tier row (h >= hb2, <= 16 units) goes to
-// glist (count ndec[2]); settled unit-tallied rows get wcount[h] = -1 (the combine's
-// classify / enqueue skip them).  ndec[3] = 1 when G is not worth trying: nothing is
-// decided and the exact kernels take their whole ranges (ndec[3] is their "fr_all").
+// ulist2 (count ndec[GD_UNITS]), a block-tier row (h >= hb2, <= 16 units) goes to
+// glist (count ndec[GD_ROWS]); settled unit-tallied rows get wcount[h] = -1 (the combine's
+// classify / enqueue skip them).  ndec[GD_ALL] = 1 when G is not worth trying: nothing is
+// decided and the exact kernels take their whole ranges (ndec[GD_ALL] is their "fr_all").
 // Unit-tallied rows: a wave per row; block-tier rows: a lane per row, one list atomic
 // per wave.
 __global__ __launch_bounds__(256) void k_hub_decide(int64_t h_end, const int64_t* __restrict__ uoff,
@@ -215,11 +216,11 @@ __global__ __launch_bounds__(256) void k_hub_decide(int64_t h_end, const int64_t
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t stride = (int64_t)gridDim.x * 4;
-  const int32_t G = gsel[0];
-  const bool on = gsel[1] != 0;
-  if (blockIdx.x == 0 && threadIdx.x == 0) ndec[3] = on ? 0 : 1;
+  const int32_t G = gsel[GW_G];
+  const bool on = gsel[GW_TRY] != 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) ndec[GD_ALL] = on ? 0 : 1;
   if (!on) return;  // uniform: k_lpa_units_giant counted nothing
-  const bool code = gsel[5] != 0;   // uniform
+  const bool code = gsel[GW_CODE] != 0;   // uniform
   const int64_t ha = hb2 < h_end ? hb2 : h_end;
   for (int64_t h = (int64_t)blockIdx.x * 4 + w; h < ha; h += stride) {
     const int64_t u0 = uoff[h];
@@ -261,7 +262,7 @@ __global__ __launch_bounds__(256) void k_hub_decide(int64_t h_end, const int64_t
       int base = 0;
       if (lane == 0) {
         wcount[h] = 0;
-        base = atomicAdd(&ndec[0], nu);
+        base = atomicAdd(&ndec[GD_UNITS], nu);
       }
       base = __shfl(base, 0, 64);
       for (int j = lane; j < nu; j += 64) ulist2[base + j] = (int32_t)(u0 + j);
@@ -287,7 +288,7 @@ __global__ __launch_bounds__(256) void k_hub_decide(int64_t h_end, const int64_t
       if (sg > sm) Ln[h] = G;
       else open = true;
     }
-    wave_append(open, glist, &ndec[2], (int32_t)h, lane);
+    wave_append(open, glist, &ndec[GD_ROWS], (int32_t)h, lane);
   }
 }
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include <string>
 
@@ -112,6 +113,20 @@ void set_error(const char* fmt, ...);
     if (rc_ != LPA_OK) return rc_; \
   } while (0)
 
+// LPA_TRACE (diagnostic build only): synchronise and log after every kernel (the host
+// function's stream `s`)
+#ifdef LPA_TRACE
+#define LPA_TRACE_POINT(name)                                        \
+  do {                                                               \
+    hipError_t te_ = hipStreamSynchronize(s);                        \
+    fprintf(stderr, "[lpa-trace] %s done (%s)\n", name, hipGetErrorString(te_)); \
+  } while (0)
+#else
+#define LPA_TRACE_POINT(name) \
+  do {                        \
+  } while (0)
+#endif
+
 // ---------------------------------------------------------------------------
 // Device memory held by a handle.
 // ---------------------------------------------------------------------------
@@ -137,6 +152,40 @@ struct Arena {
   int cur = 0;       // block being carved
   size_t off = 0;    // offset in it
 };
+
+// Slots of lpa_graph::gword (kGwordLen words, zeroed at build): the giant label of the
+// last refreshed vector and the device-side decisions of supersteps 2-4 that hang on it.
+// Kernels that take the word as `gsel` (the tallies' giant step) index it alike.
+enum GwordSlot {
+  GW_G = 0,           // G, the giant label of the last refreshed vector (k_giant_pick)
+  GW_TRY = 1,         // G is worth trying: it holds >= 1/5 of the hub slots (k_giant_pick)
+  GW_ABITS_OK = 2,    // abits valid: bits-mode rebuild, no scatter since (cleared by k_al_scatter
+                      //   unless it keeps the bits, by a new G, by a code refresh, by a reset)
+  GW_HOT_BITS = 3,    // hot-slot giant-bit count (k_giant_bits; the bits-mode / code-mode test)
+  GW_BINS4 = 4,       // superstep 4's bins below the hubs: 0 = lists of the unsettled rows, 1 =
+                      //   ranges (their "fr_all", k_settle_commit4)
+  GW_CODE = 5,        // giant-code refresh taken (k_code_mode): the next superstep settles from al2
+  GW_WAVE2 = 6,       // superstep 2's wave bins: 0 = lists of the rows the code settle left
+                      //   (their "fr_all", k_code_settle)
+  GW_ROWS3 = 7,       // superstep 3's labelled row bins after a code refresh: 1 = ranges
+                      //   (their "fr_all", k_code_commit)
+  GW_ABITS_PASS = 9,  // superstep 4's k_abits_pass ran: its bits are valid for the rows below
+                      //   the hubs
+  GW_PURE_ALL = 10,   // superstep 4's k_lpa_units: 0 = the impure-unit list, 1 = every unit
+                      //   (its "fr_all", k_units_pure)
+  GW_PURE_CNT = 11,   // ... and that list's length (zeroed by k_giant_pick)
+};
+constexpr int kGwordLen = 16;
+// Slots of lpa_graph::gdec (kGdecLen words): superstep 2's hub decision in block mode
+// (k_hub_decide, `ndec` there) and the lists of what it could not settle.
+enum GdecSlot {
+  GD_UNITS = 0,       // length of ulist2: the units of the unit-tallied rows left undecided
+  GD_LISTED = 1,      // a constant 0 (a list-mode "fr_all"; no launch takes it today)
+  GD_ROWS = 2,        // length of glist: the block-tier rows left undecided
+  GD_ALL = 3,         // 1 = G was not worth trying, nothing decided: the exact kernels take
+                      //   their whole ranges (their "fr_all")
+};
+constexpr int kGdecLen = 4;
 
 }  // namespace lpa
 
@@ -210,7 +259,7 @@ struct lpa_graph {
   uint32_t* ugc = nullptr;        // [n_segs] superstep 2: the unit's giant-label votes ...
   uint32_t* umx = nullptr;        // [n_segs] ... and its fullest other-label bucket (k_lpa_units_giant)
   int32_t* ulist2 = nullptr;      // [n_segs] units of the rows k_hub_decide could not settle
-  int32_t* gdec = nullptr;        // [4] their count, a constant 0 (the list-mode "fr_all"), the count of glist
+  int32_t* gdec = nullptr;        // [kGdecLen] their count, the count of glist, ... (GdecSlot)
   int32_t* glist = nullptr;       // [n_hub] block-tier rows k_hub_decide could not settle (k_lpa_block's list)
   lpa::u64* scat = nullptr;       // [hub arcs] bucket-partitioned words
   int32_t* hub_wcount = nullptr;  // [n_hub] staged words of a queued row (0 otherwise)
@@ -267,16 +316,9 @@ struct lpa_graph {
   bool al_pending = false;
   bool al_is_l0 = false;        // al holds L0[col] already (the L2 sub-graph's build writes it)
   uint32_t* gbits = nullptr;    // [vpad / 32] rebuild: bit u = (L[u] == G), the giant label
-  int32_t* gword = nullptr;     // [8] G of the last refreshed vector (k_giant_pick), worth-trying flag,
-                                //     abits valid (bits-mode rebuild, no scatter since), [3] hot-slot
-                                //     giant-bit count (k_giant_bits), [4] superstep 4 bins: 0 = lists,
-                                //     [5] giant-code refresh taken (superstep 2 settles from al2),
-                                //     [6] superstep 2's wave bins: 0 = lists of the unsettled rows,
-                                //     [7] superstep 3's row bins (code refresh), [9] superstep 4's
-                                //     k_abits_pass ran (its bits valid for the rows below the hubs),
-                                //     [10] / [11] superstep 4's impure-unit list mode / count
-                                //     (k_units_pure); 16 words
-  // giant codes (round 5, lpa_iter.hip "Giant codes"): the refresh after superstep 1 (or
+  int32_t* gword = nullptr;     // [kGwordLen] G of the last refreshed vector and the decisions of
+                                //     supersteps 2-4 that hang on it (GwordSlot)
+  // giant codes (round 5, lpa_codes.h "Giant codes"): the refresh after superstep 1 (or
   // 2), when one label G carries the hubs but not half the hot slots (R-MAT), writes a
   // 2-bit code per arc instead of al[] (code 0 = G, else 1 + a label hash mod 3; 16 arcs
   // to a word of al2) for the rows above the cut (code_lbin), and al[] only for the
@@ -312,7 +354,7 @@ struct lpa_graph {
   int64_t n_chunk_scan = 0;     // chunks below this belong to every multi-chunk column
   int32_t* chlist = nullptr;    // [vpad] changed one-chunk columns (count: counters[par][0])
   int rebuild_hot = 1;                      // LDS hot-label rebuild (LPA_REBUILD_HOT=0 disables)
-  // class-blocked labels-mode rebuild (P = 1, lpa_iter.hip rebuild_pieces): rows of
+  // class-blocked labels-mode rebuild (P = 1, lpa_refresh.hip rebuild_pieces): rows of
   // degree > block_deg keep their columns in (class, column) order (col_class); the
   // class segments cut into <= 64-arc pieces, listed per class
   // (padded to multiples of 8) so that one block group (one XCD) gathers one class
@@ -434,9 +476,17 @@ int build_hub_tables(lpa_graph* g, const int32_t* deg_own);  // lpa_hub.hip
 int launch_hub_combine(lpa_graph* g, int32_t* Lown, bool fork, bool join = true,
                        bool giant = false);  // lpa_hub.hip
 int launch_hub_decide(lpa_graph* g, int32_t* Lown, int64_t h_end, const int32_t* gsel);  // lpa_hub.hip
-bool block_mode_now(const lpa_graph* g);  // lpa_iter.hip
-bool fused_now(const lpa_graph* g);       // lpa_iter.hip
-int64_t block_rows_begin(const lpa_graph* g);  // first row of the block tiers (lpa_iter.hip)
+// (the phases of the schedule, block_mode_now / fused_now / ...: lpa_schedule.h)
+
+// refresh stage (lpa_refresh.hip)
+// changed slots in [s0, s1) -> position chunks + dirty-arc count (counters of parity `par`);
+// bins [b0, b1) given: the frontier list mode is available; mode 1 counts only, 2 is the
+// full diff after a count (label-dense supersteps)
+int launch_diff(lpa_graph* g, hipStream_t st, const int32_t* Lc, const int32_t* Ln, int64_t s0,
+                int64_t s1, bool sync, int par, int b0 = 0, int b1 = 0, int mode = 0);
+// refresh al[] for L_next of the superstep of parity `par` (scatter or rebuild)
+int launch_refresh(lpa_graph* g, const int32_t* Lc, const int32_t* Ln, bool diff_done, int par,
+                   hipEvent_t ev_scatter = nullptr, bool fold_rebuild = false);
 int rebuild_arc_labels(lpa_graph* g);  // al[i] = lab[cur][col[i]]
 // the caller-driven full exchange (lpa_exchange_put) completes the superstep just run:
 // its refresh rebuilds every arc label, and may take the giant codes as the in-library
@@ -483,6 +533,7 @@ unsigned long long* exchange_recv_counts(lpa_graph* g);
 int exchange_finish_delta(lpa_graph* g, int32_t* Lc, int32_t* Ln, int64_t cap, int par,
                           const unsigned long long* counts, int cs, bool posted = false);
 int exchange_collective(lpa_graph* g, const int32_t* Lc, int32_t* Ln, bool first, bool* changes_listed);
+// the caller-driven delta exchange's refresh of the superstep lpa_step just ran (lpa_refresh.hip)
 int launch_refresh_ext(lpa_graph* g, const int32_t* Lc, const int32_t* Ln, bool diff_done, int par);
 
 // outlier (lpa_outlier.hip)

@@ -41,174 +41,33 @@
 //   seg  deg > 1024     one wave per 512-arc unit (staged unit tally words), merged
 //                       per row by the hub combine (lpa_hub.hip)
 // Tables keep a touched-slot list: finishing a vertex costs O(distinct labels).
-#include <stdio.h>
+//
+// This file holds the lists and tally stages and the driver (run_supersteps); the
+// refresh stage is lpa_refresh.hip, and lpa_schedule.h names the phases they branch on.
 #include <string.h>
 
 #include <algorithm>
 #include <mutex>
 
-#include "lpa_internal.h"
+#include "lpa_codes.h"
+#include "lpa_device.h"
 #include "lpa_lane.h"
-
-// LPA_TRACE (diagnostic build only): synchronise and log after every kernel
-#ifdef LPA_TRACE
-#define LPA_TRACE_POINT(name)                                        \
-  do {                                                               \
-    hipError_t te_ = hipStreamSynchronize(s);                        \
-    fprintf(stderr, "[lpa-trace] %s done (%s)\n", name, hipGetErrorString(te_)); \
-  } while (0)
-#else
-#define LPA_TRACE_POINT(name) \
-  do {                        \
-  } while (0)
-#endif
+#include "lpa_schedule.h"
 
 namespace lpa {
 
-namespace {
+using namespace dev;
 
-// Diagnostic ablations (separate builds only, `make diag`; never in liblpa_hip.so):
-//   1 = stream the labels but skip the tally, 2 = skip the hub global merge,
-//   3 = peel only (no LDS hash of the residual votes)
-#ifndef LPA_DIAG
-#define LPA_DIAG 0
-#endif
+namespace {
 
 // peel rounds of the wave / unit / block tallies in the label-dense supersteps, where a
 // round rarely retires more than a few votes (measured best of 0/2/4/8 at C3)
 constexpr int kDensePeel = 2;
 
-}  // namespace
-
-// the label-dense supersteps tally the rows [hub_lane_begin, n_hub) with k_lpa_block
-// and skip their units; the superstep after them tallies every row (their units'
-// staged words are stale)
-bool block_mode_now(const lpa_graph* g) { return g->since_reset < kDenseSupersteps && g->hub_lane_begin < g->n_hub; }
-int64_t block_rows_begin(const lpa_graph* g) { return g->hub_block2_begin; }
-
-namespace {
-
-
 constexpr int kChunks = 8;    // 64-arc chunks per wave: a wave-bin row / a quarter segment
-constexpr u32 kNone = 0xFFFFFFFFu;  // empty lane
 static_assert(kSegArcs == 64 * kChunks, "a unit is one batch of chunks");
 static_assert(kWaveMaxDeg == 64 * kChunks, "a wave-bin row fits one batch of chunks");
 static_assert(kWideMaxDeg == 2 * kWaveMaxDeg, "w16 rows: 16 chunks");
-
-__device__ __forceinline__ u32 ld_stream(const int32_t* p) {
-  return (u32)__builtin_nontemporal_load(p);
-}
-
-__device__ __forceinline__ u64 tally(u32 cnt, u32 label) {
-  return ((u64)cnt << 32) | (u64)(u32)(~label);
-}
-
-__device__ __forceinline__ u64 umax64(u64 a, u64 b) { return a > b ? a : b; }
-
-// Wave reductions over a FULL wave (every call site has all 64 lanes active):
-// DPP within each 16-lane row (xor 1, xor 2, half-row mirror, row mirror: every
-// lane ends with its row's result, VALU only, no LDS round trip), then the four
-// row results via readlane (uniform result).
-template <int kCtrl>
-__device__ __forceinline__ u32 dpp_u32(u32 v) {
-  return (u32)__builtin_amdgcn_update_dpp(0, (int)v, kCtrl, 0xF, 0xF, false);
-}
-template <int kCtrl>
-__device__ __forceinline__ u64 dpp_u64(u64 v) {
-  return ((u64)dpp_u32<kCtrl>((u32)(v >> 32)) << 32) | (u64)dpp_u32<kCtrl>((u32)v);
-}
-__device__ __forceinline__ u64 readlane_u64(u64 v, int l) {
-  return ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(v >> 32), l) << 32) |
-         (u64)(u32)__builtin_amdgcn_readlane((int)(u32)v, l);
-}
-__device__ __forceinline__ u64 wave_max_u64(u64 v) {
-  v = umax64(v, dpp_u64<0xB1>(v));   // quad_perm [1,0,3,2]
-  v = umax64(v, dpp_u64<0x4E>(v));   // quad_perm [2,3,0,1]
-  v = umax64(v, dpp_u64<0x141>(v));  // row_half_mirror
-  v = umax64(v, dpp_u64<0x140>(v));  // row_mirror
-  return umax64(umax64(readlane_u64(v, 0), readlane_u64(v, 16)),
-                umax64(readlane_u64(v, 32), readlane_u64(v, 48)));
-}
-
-__device__ __forceinline__ u32 wave_sum_u32(u32 v) {
-  v += dpp_u32<0xB1>(v);
-  v += dpp_u32<0x4E>(v);
-  v += dpp_u32<0x141>(v);
-  v += dpp_u32<0x140>(v);
-  return (u32)__builtin_amdgcn_readlane((int)v, 0) + (u32)__builtin_amdgcn_readlane((int)v, 16) +
-         (u32)__builtin_amdgcn_readlane((int)v, 32) + (u32)__builtin_amdgcn_readlane((int)v, 48);
-}
-
-__device__ __forceinline__ u32 wave_max_u32(u32 v) {
-  v = max(v, dpp_u32<0xB1>(v));
-  v = max(v, dpp_u32<0x4E>(v));
-  v = max(v, dpp_u32<0x141>(v));
-  v = max(v, dpp_u32<0x140>(v));
-  return max(max((u32)__builtin_amdgcn_readlane((int)v, 0), (u32)__builtin_amdgcn_readlane((int)v, 16)),
-             max((u32)__builtin_amdgcn_readlane((int)v, 32), (u32)__builtin_amdgcn_readlane((int)v, 48)));
-}
-// u64 max as two 32-bit reductions (the high words, then the low words of the lanes
-// holding that high word): each DPP step is one v_max_u32 instead of two moves, a
-// 64-bit compare and two selects -- fewer VALU issues, a longer dependent chain, so it
-// serves only the issue-bound g64 row hash (C2 60.4 -> 61.6 GTEPS; as every kernel's
-// wave max, C3's latency-bound converged supersteps lost 1.5 %)
-__device__ __forceinline__ u64 wave_max_u64_split(u64 v) {
-  const u32 hi = wave_max_u32((u32)(v >> 32));
-  const u32 lo = wave_max_u32((u32)(v >> 32) == hi ? (u32)v : 0u);
-  return ((u64)hi << 32) | lo;
-}
-
-__device__ __forceinline__ u32 hash_slot(u32 label, int shift) {
-  return (label * 0x9E3779B1u) >> shift;
-}
-
-__device__ __forceinline__ int ceil_log2(u32 x) { return x <= 1 ? 0 : 32 - __clz(x - 1); }
-
-// Insert `cnt` votes for `label` into an LDS open-addressing table of (mask+1)
-// slots.  Returns the slot index when this call claimed an empty slot, else -1.
-__device__ __forceinline__ int lds_insert(u64* tab, int shift, u32 mask, u32 label, u32 cnt) {
-  const u32 key = ~label;
-  u32 h = hash_slot(label, shift);
-  while (true) {
-    u64 old = atomicCAS(&tab[h], 0ull, ((u64)cnt << 32) | key);
-    if (old == 0ull) return (int)h;
-    if ((u32)old == key) {
-      atomicAdd(&tab[h], (u64)cnt << 32);
-      return -1;
-    }
-    h = (h + 1u) & mask;
-  }
-}
-
-// Continue a global-table insert whose first probe at slot h returned `old`;
-// returns the claimed slot or -1 (merged into an existing key).
-__device__ __forceinline__ int global_resolve(u64* tab, u32 mask, u64 word, u32 h, u64 old) {
-  const u32 key = (u32)word;
-  const u64 add = word & 0xFFFFFFFF00000000ull;
-  while (true) {
-    if (old == 0ull) return (int)h;
-    if ((u32)old == key) {
-      atomicAdd(&tab[h], add);
-      return -1;
-    }
-    h = (h + 1u) & mask;
-    old = atomicCAS(&tab[h], 0ull, word);
-  }
-}
-
-// Continue an LDS insert of `word` whose probe at slot h hit another key.
-__device__ __forceinline__ int lds_probe(u64* tab, u32 mask, u64 word, u32 h) {
-  const u32 key = (u32)word;
-  while (true) {
-    h = (h + 1u) & mask;
-    const u64 old = atomicCAS(&tab[h], 0ull, word);
-    if (old == 0ull) return (int)h;
-    if ((u32)old == key) {
-      atomicAdd(&tab[h], word & 0xFFFFFFFF00000000ull);
-      return -1;
-    }
-  }
-}
 
 // ---------------------------------------------------------------------------
 // Tally of a batch of up to NC 64-arc chunks held in registers (kNone = empty
@@ -432,13 +291,7 @@ __device__ __forceinline__ u64 group_mode_hash(u32 v, int lane, u64* tab) {
   constexpr u32 kMask = (1u << kLg) - 1u;
   u64* gt = tab + (lane & ~(G - 1)) * 4;
   u64 w = 0ull;
-#if LPA_DIAG == 1
-  // diagnostic (timing only, wrong modes): no table, each vote counted once
-  if (v != kNone) w = (1ull << 32) | (u64)(u32)(~v);
-  if (false) {
-#else
   if (v != kNone) {
-#endif
     const u64 word = (1ull << 32) | (u64)(u32)(~v);
     u32 h = hash_slot(v, 32 - kLg);
     while (true) {
@@ -467,12 +320,6 @@ __device__ __forceinline__ u64 group_mode_hash(u32 v, int lane, u64* tab) {
   }
 }
 
-#if LPA_DIAG == 2
-#define LPA_GV(x) (x)
-#else
-#define LPA_GV(x) ((u32)Lg[(int32_t)(x)])
-#endif
-
 // peel rounds after which a chunk whose groups are still unresolved is hashed instead
 constexpr int kPeelSortAfter = 3;
 
@@ -494,12 +341,7 @@ __device__ __forceinline__ u64 decided_groups(u64 act, u64 my, u64 best, int gba
 // current vector itself, so no al[] refresh runs at all; otherwise src is al[].
 template <bool kG>
 __device__ __forceinline__ u32 arc_vote(const int32_t* __restrict__ src, const int32_t* __restrict__ L, int64_t i) {
-#if LPA_DIAG == 2
-  // diagnostic (timing only, wrong votes): the column itself, no label gather
-  if constexpr (kG) return ld_stream(src + i);
-#else
   if constexpr (kG) return (u32)L[(int32_t)ld_stream(src + i)];
-#endif
   else return ld_stream(src + i);
 }
 
@@ -750,8 +592,8 @@ __device__ __forceinline__ void wave_bin(int64_t bid, int64_t nblk, u64* tab_all
   for (int k = lane; k < kCap; k += 64) tab[k] = 0ull;  // only waves with rows clear
   // gsel (label-dense supersteps): the giant-label word of the labels this superstep
   // reads (k_giant_pick: label, worth trying)
-  const bool giant = gsel != nullptr && gsel[1] != 0;
-  const u32 G = giant ? (u32)gsel[0] : 0u;
+  const bool giant = gsel != nullptr && gsel[GW_TRY] != 0;
+  const u32 G = giant ? (u32)gsel[GW_G] : 0u;
   SpanBatch cur = span_batch(rp, br, ib, stride, lane);
   SpanBatch nxt;  // the next batch: loaded at p == 32, half a batch before its first use
   nxt.b = nxt.e = 0;
@@ -834,8 +676,8 @@ __global__ __launch_bounds__(64 * kBlockWaves) void k_lpa_block(const int64_t* _
   if (threadIdx.x < kGB) ghist[threadIdx.x] = 0u;
   if (threadIdx.x < 2) gcnt[threadIdx.x] = gmax[threadIdx.x] = 0u;
   // gsel (label-dense supersteps): the giant-label word (k_giant_pick; giant_count)
-  const bool giant = gsel != nullptr && gsel[1] != 0;
-  const u32 G = giant ? (u32)gsel[0] : 0u;
+  const bool giant = gsel != nullptr && gsel[GW_TRY] != 0;
+  const u32 G = giant ? (u32)gsel[GW_G] : 0u;
   __syncthreads();
   int rpar = 0;  // parity of the rows this block has tallied
   for (int64_t q = blockIdx.x; q < n; q += gridDim.x) {
@@ -1034,8 +876,8 @@ __device__ __forceinline__ void rows_bin(int64_t bid, int64_t nblk, u64* htab_al
   // gsel (superstep 2, rows of > 8 arcs): a chunk whose every row is decided for the
   // giant label (its exact count above each of the row's kGB label-hash buckets of
   // other votes, as giant_decide) skips the peel / hash
-  const bool giant = G >= 16 && gsel != nullptr && gsel[1] != 0;
-  const u32 Gl = giant ? (u32)gsel[0] : 0u;
+  const bool giant = G >= 16 && gsel != nullptr && gsel[GW_TRY] != 0;
+  const u32 Gl = giant ? (u32)gsel[GW_G] : 0u;
   u32* hg = ghist_all + w * (64 / G * kGB) + (lane / G) * kGB;
   const int gj = lane & (G - 1);   // G >= kGB when giant: lane gj < kGB owns bucket gj
   if (gj < kGB) hg[gj] = 0u;
@@ -1170,7 +1012,7 @@ __device__ __forceinline__ void rows_bin(int64_t bid, int64_t nblk, u64* htab_al
     for (int k = 0; k < D; ++k) rows_rp_nb<G>(rp, vbeg + (bi + k * stride) * RB, vend, lane, rpl[k], rpe[k]);
     rows_labels_nb<G, false>(cc[0], vb[0], al, vbeg + bi * RB, vend, rpl[0], rpe[0], lane);
 #pragma unroll
-    for (int c = 0; c < kChunks; ++c) labg[0][c] = LPA_GV(cc[0][c]);
+    for (int c = 0; c < kChunks; ++c) labg[0][c] = (u32)Lg[(int32_t)(cc[0][c])];
     rows_labels_nb<G, false>(cc[1], vb[1], al, vbeg + (bi + stride) * RB, vend, rpl[1], rpe[1], lane);
     while (true) {
 #pragma unroll
@@ -1179,7 +1021,7 @@ __device__ __forceinline__ void rows_bin(int64_t bid, int64_t nblk, u64* htab_al
         __builtin_amdgcn_sched_barrier(0);
         rows_rp_nb<G>(rp, vbeg + (bi + D * stride) * RB, vend, lane, rpl[k], rpe[k]);
 #pragma unroll
-        for (int c = 0; c < kChunks; ++c) labg[k1][c] = LPA_GV(cc[k1][c]);
+        for (int c = 0; c < kChunks; ++c) labg[k1][c] = (u32)Lg[(int32_t)(cc[k1][c])];
         rows_labels_nb<G, false>(cc[k2], vb[k2], al, vbeg + (bi + 2 * stride) * RB, vend, rpl[k2], rpe[k2], lane);
         __builtin_amdgcn_sched_barrier(0);
         tally_batch(labg[k], vb[k], vbeg + bi * RB);
@@ -1487,7 +1329,7 @@ __global__ __launch_bounds__(256) void k_lpa_units(const int32_t* __restrict__ a
 // units of the rows it cannot settle are then tallied exactly (k_lpa_units, list mode).
 // Block 0 also zeroes the undecided-unit list count (*ndec) for k_hub_decide.
 // (k_lpa_units_code2 below: the same from the 2-bit giant codes, when the refresh took
-// them -- gsel[5]; this form returns at once then.)
+// them -- gsel[GW_CODE]; this form returns at once then.)
 template <typename T>
 __device__ __forceinline__ void unit_load_nb_t(u32 (&raw)[kChunks], const T* __restrict__ al, const Segment& d,
                                                int lane) {
@@ -1509,12 +1351,12 @@ __global__ __launch_bounds__(256) void k_lpa_units_giant(const T* __restrict__ a
   __shared__ u32 hist_all[4][64];
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (blockIdx.x == 0 && threadIdx.x == 0) ndec[0] = ndec[2] = 0;  // unit list, block-row list
-  if (gsel[5] != 0) return;  // k_lpa_units_code2's turn (uniform)
-  if (gsel[1] == 0) return;  // no giant label worth trying: k_hub_decide lists every row
+  if (blockIdx.x == 0 && threadIdx.x == 0) ndec[GD_UNITS] = ndec[GD_ROWS] = 0;  // unit list, block-row list
+  if (gsel[GW_CODE] != 0) return;  // k_lpa_units_code2's turn (uniform)
+  if (gsel[GW_TRY] == 0) return;  // no giant label worth trying: k_hub_decide lists every row
   u32* hist = hist_all[w];
   hist[lane] = 0u;
-  const u32 G = (u32)gsel[0];
+  const u32 G = (u32)gsel[GW_G];
   const int64_t stride = (int64_t)gridDim.x * 4;
   int64_t u = (int64_t)blockIdx.x * 4 + w;
   if (u >= nunits) return;  // no block-level barriers in this kernel
@@ -1572,9 +1414,10 @@ __global__ __launch_bounds__(256) void k_lpa_units_giant(const T* __restrict__ a
 // bound, its joiners' bits clear -- when its al[] entry is G.  A lane per 64-arc chunk, eight
 // units per wave; a lane reads its chunk's bit words and only the al[] entries of the clear
 // bits, stopping at the first non-G vote.  The other units are listed (ulist, count
-// gword[11], zeroed by k_giant_pick; a block's ids gathered in LDS first) for k_lpa_units in list mode (gword[10] = 0, its
-// "fr_all").  Only with the kept bits (gword[2]: nothing writes them during superstep 4);
-// otherwise gword[10] = 1 and k_lpa_units takes every unit.
+// gword[GW_PURE_CNT], zeroed by k_giant_pick; a block's ids gathered in LDS first) for
+// k_lpa_units in list mode (gword[GW_PURE_ALL] = 0, its "fr_all").  Only with the kept
+// bits (gword[GW_ABITS_OK]: nothing writes them during superstep 4); otherwise
+// gword[GW_PURE_ALL] = 1 and k_lpa_units takes every unit.
 constexpr int kPureIds = 8192;  // units per k_units_pure block (its LDS list)
 __global__ __launch_bounds__(256) void k_units_pure(const int32_t* __restrict__ al,
                                                     const unsigned long long* __restrict__ abits, int64_t arcs,
@@ -1583,10 +1426,10 @@ __global__ __launch_bounds__(256) void k_units_pure(const int32_t* __restrict__ 
                                                     int32_t* __restrict__ ucnt, int32_t* __restrict__ ulist) {
   __shared__ int32_t lids[kPureIds];
   __shared__ int ln, lbase;
-  const bool on = gword[2] != 0 && gword[1] != 0;
-  if (blockIdx.x == 0 && threadIdx.x == 0) gword[10] = on ? 0 : 1;
+  const bool on = gword[GW_ABITS_OK] != 0 && gword[GW_TRY] != 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) gword[GW_PURE_ALL] = on ? 0 : 1;
   if (!on) return;  // uniform
-  const int32_t G = gword[0];
+  const int32_t G = gword[GW_G];
   const int lane = threadIdx.x & 63;
   const int c = lane & 7;
   const int64_t nwords = (arcs + 63) >> 6;
@@ -1644,160 +1487,9 @@ __global__ __launch_bounds__(256) void k_units_pure(const int32_t* __restrict__ 
   __syncthreads();
   const int n = ln;
   if (n == 0) return;  // uniform
-  if (threadIdx.x == 0) lbase = atomicAdd(&gword[11], n);
+  if (threadIdx.x == 0) lbase = atomicAdd(&gword[GW_PURE_CNT], n);
   __syncthreads();
   for (int i = threadIdx.x; i < n; i += 256) ulist[lbase + i] = lids[i];
-}
-
-// ---------------------------------------------------------------------------
-// refresh of the replicated neighbour labels al[]
-// ---------------------------------------------------------------------------
-// Scatter chunks: column u's al[] positions cpos[cptr[u] ..) are cut into chunks of
-// kChunkPos, numbered statically at build time (chunks cch[u] .. cch[u+1] - 1,
-// cowner[chunk] = u).  A changed column flags its chunks in the bytemap chflag[]
-// (plain byte stores, no list to build); the scatter walks the bytemap.
-__device__ __forceinline__ void flag_chunks(uint8_t* __restrict__ chflag, const int64_t* __restrict__ cch,
-                                            int64_t u) {
-  int64_t c = cch[u];
-  const int64_t e = cch[u + 1];
-  for (; c < e && (c & 15); ++c) chflag[c] = 1;  // hub columns: thousands of chunks,
-  for (; c + 16 <= e; c += 16)                    // 16 flags per store
-    *reinterpret_cast<uint4*>(chflag + c) = make_uint4(0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u);
-  for (; c < e; ++c) chflag[c] = 1;
-}
-
-// changed vertices of the slot range [s0, s1): a column with one scatter chunk (the
-// vast majority) is appended to chlist[] (LDS queue, one atomic per block), a longer
-// one flags its chunks in chflag[]; the dirty arcs are counted (one atomic per wave);
-// with Lsync != nullptr the new label is also copied into Lc (the next superstep's
-// output vector: frontier, a row the next superstep skips already holds its label
-// there; inside the concurrent tally the scatter does it).  int4 quads (vpad is a
-// multiple of 64), kDiffQuads per block; lanes outside the range masked (the
-// neighbouring slots may belong to a bin another stream is still computing).
-//
-// Frontier superstep (lists != nullptr and *fr_all == 0): only the rows listed for
-// bins [b0, b1) were re-tallied (every other row provably kept its label, and its
-// output slot already holds it), so the diff walks those lists -- grid-stride over
-// their concatenation -- instead of the slot range.
-struct BinBounds {
-  int64_t b[LPA_NBINS + 1];
-};
-constexpr int kDiffQuads = 2048;
-// counters[1] value that makes the refresh rebuild al[] (k_dense_decide)
-constexpr unsigned long long kForcedRebuild = 1ull << 62;
-
-// Label-dense supersteps (P = 1): the per-stream diffs only counted the changed slots.
-// More than 1/10 of the slots changed: the refresh rebuilds al[] (counters[1] forced),
-// so no position chunk is ever emitted; otherwise the full diff (mode 2) runs next.
-// A superstep after a giant-code refresh (gword[5]) always rebuilds: its al[] entries were
-// never written for the rows that superstep settled from codes.
-__global__ void k_dense_decide(unsigned long long* __restrict__ counters, int64_t n_slots,
-                               const int32_t* __restrict__ gword) {
-  if (threadIdx.x == 0 && ((int64_t)counters[2] * 10 > n_slots || gword[5] != 0)) counters[1] = kForcedRebuild;
-}
-// fcnt[] slot set by the row settle of a giant superstep (k_settle_*): the bin kernels
-// walk lists of the unsettled rows, but the diff scans every slot (settled rows may
-// have changed label)
-__global__ __launch_bounds__(256) void k_diff(const int4* __restrict__ Lc4,
-                                              const int4* __restrict__ Ln4, int32_t* __restrict__ Lsync,
-                                              int64_t s0, int64_t s1,
-                                              const int64_t* __restrict__ cptr,
-                                              const int64_t* __restrict__ cch,
-                                              uint8_t* __restrict__ chflag,
-                                              int32_t* __restrict__ chlist,
-                                              unsigned long long* __restrict__ counters,
-                                              BinBounds bb, int b0, int b1,
-                                              const int32_t* __restrict__ flist,
-                                              const int32_t* __restrict__ fcnt,
-                                              const int32_t* __restrict__ fr_all, int mode) {
-  // mode 1 (label-dense supersteps): only count the changed slots (counters[2]); mode 2:
-  // the full diff unless k_dense_decide already chose the rebuild (counters[1] forced)
-  if (mode == 2 && counters[1] >= kForcedRebuild) return;
-  if (mode == 1) {
-    unsigned long long c = 0;
-    const int64_t q0 = s0 / 4 + (int64_t)blockIdx.x * kDiffQuads;
-    const int64_t q1 = min((s1 + 3) / 4, q0 + kDiffQuads);
-    for (int64_t q = q0 + threadIdx.x; q < q1; q += 256) {
-      const int4 a = Lc4[q], b = Ln4[q];
-      int chg = (a.x != b.x) | ((a.y != b.y) << 1) | ((a.z != b.z) << 2) | ((a.w != b.w) << 3);
-      if (q * 4 < s0 || q * 4 + 4 > s1) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (q * 4 + k < s0 || q * 4 + k >= s1) chg &= ~(1 << k);
-      }
-      c += (unsigned long long)__popc(chg);
-    }
-    // (the counts summed per block first: one atomic per block on the counter, not one
-    // per wave -- the same-address atomics of ~8 K waves queue at the counter's channel)
-    __shared__ unsigned long long csum;
-    if (threadIdx.x == 0) csum = 0ull;
-    __syncthreads();
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&csum, c);
-    __syncthreads();
-    if (threadIdx.x == 0 && csum) atomicAdd(&counters[2], csum);
-    return;
-  }
-  __shared__ int32_t q_col[kDiffQuads * 4];
-  __shared__ int qn;
-  __shared__ unsigned long long base_s, dsum;
-  const int lane = threadIdx.x & 63;
-  if (threadIdx.x == 0) {
-    qn = 0;
-    dsum = 0ull;
-  }
-  __syncthreads();
-  unsigned long long dirty = 0;
-  auto emit = [&](int64_t u, int32_t nb) {
-    if (Lsync) Lsync[u] = nb;
-    dirty += (unsigned long long)(cptr[u + 1] - cptr[u]);
-    const int64_t nch = cch[u + 1] - cch[u];
-    if (nch == 1) q_col[atomicAdd(&qn, 1)] = (int32_t)u;
-    else if (nch > 1) flag_chunks(chflag, cch, u);
-  };
-  if (flist != nullptr && *fr_all == 0 && fcnt[kFcntSettled] == 0) {
-    // a list holds at most its bin's rows, so the grid (sized for the slot range)
-    // gives each thread <= 32 entries, inside the block's queue
-    int64_t total = 0;
-    for (int b = b0; b < b1; ++b) total += fcnt[b];
-    const int32_t* Lc = reinterpret_cast<const int32_t*>(Lc4);
-    const int32_t* Ln = reinterpret_cast<const int32_t*>(Ln4);
-    for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < total; v += (int64_t)gridDim.x * 256) {
-      int64_t acc = 0;
-      int b = b0;
-      while (v >= acc + fcnt[b]) acc += fcnt[b++];
-      const int64_t u = flist[bb.b[b] + (v - acc)];
-      const int32_t nb = Ln[u];
-      if (Lc[u] != nb) emit(u, nb);
-    }
-  } else {
-    const int64_t q0 = s0 / 4 + (int64_t)blockIdx.x * kDiffQuads;
-    const int64_t q1 = min((s1 + 3) / 4, q0 + kDiffQuads);
-    for (int64_t q = q0 + threadIdx.x; q < q1; q += 256) {
-      const int4 a = Lc4[q], b = Ln4[q];
-      int chg = (a.x != b.x) | ((a.y != b.y) << 1) | ((a.z != b.z) << 2) | ((a.w != b.w) << 3);
-      if (q * 4 < s0 || q * 4 + 4 > s1) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (q * 4 + k < s0 || q * 4 + k >= s1) chg &= ~(1 << k);
-      }
-      if (chg) {
-        const int32_t nb[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if ((chg >> k) & 1) emit(q * 4 + k, nb[k]);
-      }
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) dirty += __shfl_xor(dirty, off, 64);
-  if (lane == 0 && dirty) atomicAdd(&dsum, dirty);
-  __syncthreads();
-  if (threadIdx.x == 0 && dsum) atomicAdd(&counters[1], dsum);
-  const int n = qn;
-  if (n == 0) return;  // uniform
-  if (threadIdx.x == 0) base_s = atomicAdd(&counters[0], (unsigned long long)n);
-  __syncthreads();
-  for (int i = threadIdx.x; i < n; i += 256) chlist[base_s + i] = q_col[i];
 }
 
 // Frontier lists: consume the dirty flags the previous superstep's al[] scatter left
@@ -1979,11 +1671,11 @@ __global__ __launch_bounds__(256) void k_frontier_lists(uint8_t* __restrict__ rd
 // row's units alike, so no stale flag survives), k_settle_commit switches the
 // superstep to list mode, and k_frontier_lists turns the flags into the bin lists
 // (block scans, no per-row atomics).  It applies only while *fr_all (every row due),
-// gword[1] (G worth trying) and gword[2] (abits match al), checked alike by every
+// gword[GW_TRY] (G worth trying) and gword[GW_ABITS_OK] (abits match al), checked alike by every
 // block before k_settle_commit changes fr_all.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ bool settle_on(const int32_t* fr_all, const int32_t* gword) {
-  return *fr_all != 0 && gword[1] != 0 && (gword[2] != 0 || gword[9] != 0);
+  return *fr_all != 0 && gword[GW_TRY] != 0 && (gword[GW_ABITS_OK] != 0 || gword[GW_ABITS_PASS] != 0);
 }
 
 __device__ __forceinline__ unsigned long long range_mask(int64_t x, int64_t w0, int64_t w1, int64_t a, int64_t b) {
@@ -2003,7 +1695,7 @@ __global__ __launch_bounds__(256) void k_settle_big(const int64_t* __restrict__ 
   if (!settle_on(fr_all, gword)) return;  // uniform
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int32_t G = gword[0];
+  const int32_t G = gword[GW_G];
   for (int64_t v = (int64_t)blockIdx.x * 4 + w; v < n_hub; v += (int64_t)gridDim.x * 4) {
     const int64_t a = rp[v], b = rp[v + 1];
     const int64_t w0 = a >> 6, w1 = (b - 1) >> 6;
@@ -2027,7 +1719,7 @@ __global__ __launch_bounds__(256) void k_settle_rows(const int64_t* __restrict__
                                                      const int32_t* __restrict__ gword, int32_t* __restrict__ Ln,
                                                      uint8_t* __restrict__ rdirty) {
   if (!settle_on(fr_all, gword)) return;  // uniform
-  const int32_t G = gword[0];
+  const int32_t G = gword[GW_G];
   for (int64_t v = r0 + (int64_t)blockIdx.x * 256 + threadIdx.x; v < r1; v += (int64_t)gridDim.x * 256) {
     const int64_t a = rp[v], b = rp[v + 1];
     const int64_t w0 = a >> 6, w1 = (b - 1) >> 6;
@@ -2046,16 +1738,16 @@ __global__ __launch_bounds__(256) void k_settle_rows(const int64_t* __restrict__
 // One streaming pass over 4 B/arc (the bins' giant decision cost ~2.5x that: LDS
 // histogram atomics, scalar-issue bound row batches); the next batch's loads are in
 // flight while a batch is packed.  Round 6: only when superstep 3's scatter did not keep
-// the bits (gword[2] != 0: the bits of the bits-mode rebuild, the arcs whose column left
+// the bits (gword[GW_ABITS_OK] != 0: the bits of the bits-mode rebuild, the arcs whose column left
 // G cleared by that scatter -- a lower bound of each row's G votes, which the settle's
-// strict-majority test only needs).  gword[9] = 1: the bits are valid (G worth trying).
+// strict-majority test only needs).  gword[GW_ABITS_PASS] = 1: the bits are valid (G worth trying).
 __global__ __launch_bounds__(256) void k_abits_pass(const int32_t* __restrict__ al, int64_t p0, int64_t arcs,
                                                     int32_t* __restrict__ gword,
                                                     unsigned long long* __restrict__ abits) {
-  if (gword[1] == 0) return;  // uniform: no settle this superstep
-  if (gword[2] != 0) return;  // uniform: the kept bits serve (no block writes gword[2] here)
-  if (blockIdx.x == 0 && threadIdx.x == 0) gword[9] = 1;
-  const u32 G = (u32)gword[0];
+  if (gword[GW_TRY] == 0) return;  // uniform: no settle this superstep
+  if (gword[GW_ABITS_OK] != 0) return;  // uniform: the kept bits serve (no block writes that word here)
+  if (blockIdx.x == 0 && threadIdx.x == 0) gword[GW_ABITS_PASS] = 1;
+  const u32 G = (u32)gword[GW_G];
   const int lane = threadIdx.x & 63;
   const int64_t nw = (int64_t)gridDim.x * 4;
   const int64_t w1 = (arcs + 63) >> 6;
@@ -2093,1046 +1785,14 @@ __global__ void k_settle_commit(int32_t* __restrict__ fr_all, const int32_t* __r
   fcnt[kFcntSettled] = 1;
 }
 
-// superstep 4: the bins below the hubs walk the lists of their unsettled rows (gword[4]
+// superstep 4: the bins below the hubs walk the lists of their unsettled rows (gword[GW_BINS4]
 // = 0, their "fr_all") when the settle ran, their ranges otherwise; the hub units and the
 // combine keep fr_all = 1 (every hub row re-tallied, concurrently with the settle)
 __global__ void k_settle_commit4(const int32_t* __restrict__ fr_all, int32_t* __restrict__ gword) {
-  gword[4] = settle_on(fr_all, gword) ? 0 : 1;
+  gword[GW_BINS4] = settle_on(fr_all, gword) ? 0 : 1;
 }
 
-// rebuild al[] when the changed vertices touch more than `thr` arcs (host-set)
-__device__ __forceinline__ bool rebuild_wanted(const unsigned long long* counters, int64_t thr) {
-  return (int64_t)counters[1] > thr;
-}
-
-// few changes: al[cpos[p]] = L_next[u] for the positions of each changed u.
-// A chunk is (u << 32 | k): positions [cptr[u] + 256 k, ...).  A wave takes 64
-// chunks, one per lane (independent loads of cptr and the label): chunks of <= 16
-// positions are written by their own lane (4 stores in flight per step), longer
-// ones by the whole wave (coalesced cpos).
-// Frontier marks for the next superstep: the row holding arc position p (and, for a
-// hub row, the 512-arc unit holding it) must be re-tallied.
-struct FrontierMarks {
-  const int32_t* crow;       // [arcs] row of each position
-  const int64_t* rp;         // row offsets
-  const int64_t* uoff;       // hub rows: first unit
-  int64_t n_hub;
-  uint8_t* rdirty;           // next parity
-  uint8_t* udirty;           // next parity
-  __device__ __forceinline__ void mark(int64_t p) const {
-    const int32_t r = crow[p];
-    rdirty[r] = 1;
-    if (r < n_hub) udirty[uoff[r] + ((p - rp[r]) >> 9)] = 1;
-  }
-};
-static_assert(kSegArcs == 512, "unit of a position: (p - rp[row]) >> 9");
-
-// Wave-cooperative scatter of every lane's run: al[cpos[b + i]] = lab, i < n
-// (n <= kChunkPos).  The runs are cut into 16-position pieces dealt over the wave's
-// lanes (lane -> piece by a binary search over the inclusive piece prefix), so a
-// wave whose lanes hold runs of 17..256 positions writes them in parallel instead of
-// run after run with the whole wave.  Every lane of the wave must call it.
-// clr (this lane's run): also clear the arc giant bits of its positions (a column that
-// left G, superstep 3's scatter keeping the bits of the bits-mode rebuild: k_al_scatter)
-__device__ __forceinline__ void scatter_runs(int64_t b, int n, int32_t lab, bool clr, const uint32_t* __restrict__ cpos,
-                                             int32_t* __restrict__ al, bool all, const FrontierMarks& fm,
-                                             unsigned long long* __restrict__ abits, int lane) {
-  if (al == nullptr && all) return;  // gather mode without marks: nothing to write (uniform)
-  const int k = (n + 15) >> 4;
-  int incl = k;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += o;
-  }
-  const int S = __shfl(incl, 63, 64);
-  for (int r0 = 0; r0 < S; r0 += 64) {
-    const int t = r0 + lane;
-    int o = 0;  // the owner: first lane whose inclusive piece count exceeds t
-#pragma unroll
-    for (int st = 32; st >= 1; st >>= 1) {
-      const int ic = __shfl(incl, o + st - 1, 64);
-      if (ic <= t) o += st;
-    }
-    o = o < 64 ? o : 63;
-    const int excl = __shfl(incl, o, 64) - __shfl(k, o, 64);
-    const int64_t bo = __shfl(b, o, 64);
-    const int no = __shfl(n, o, 64);
-    const int32_t lv = __shfl(lab, o, 64);
-    const bool cl = __shfl((int)clr, o, 64) != 0;
-    if (t < S) {
-      const int p0 = (t - excl) * 16;
-      const int cnt = min(16, no - p0);
-      const uint32_t* src = cpos + bo + p0;
-      for (int q = 0; q < cnt; q += 4) {
-        uint32_t p[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) p[u] = q + u < cnt ? src[q + u] : 0u;
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          if (q + u < cnt) {
-            if (al) al[p[u]] = lv;   // gather mode: marks only
-            if (cl) atomicAnd(&abits[p[u] >> 6], ~(1ull << (p[u] & 63u)));
-            if (!all) fm.mark(p[u]);
-          }
-      }
-    }
-  }
-}
-
-// al[i] = L[col[i]] over the whole arc array by the calling grid (grid-stride): each
-// thread keeps 8 gathers in flight (two int4 column quads), col / al streamed
-// non-temporally
-__device__ __forceinline__ void rebuild_all(const int32_t* __restrict__ col, int64_t arcs,
-                                            const int32_t* __restrict__ Ln, int32_t* __restrict__ al) {
-  const int64_t n4 = arcs >> 2;
-  const v4i* __restrict__ c4 = reinterpret_cast<const v4i*>(col);
-  v4i* __restrict__ a4 = reinterpret_cast<v4i*>(al);
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (; q + stride < n4; q += 2 * stride) {
-    const v4i c0 = __builtin_nontemporal_load(c4 + q);
-    const v4i c1 = __builtin_nontemporal_load(c4 + q + stride);
-    v4i r0, r1;
-    r0.x = Ln[c0.x]; r0.y = Ln[c0.y]; r0.z = Ln[c0.z]; r0.w = Ln[c0.w];
-    r1.x = Ln[c1.x]; r1.y = Ln[c1.y]; r1.z = Ln[c1.z]; r1.w = Ln[c1.w];
-    __builtin_nontemporal_store(r0, a4 + q);
-    __builtin_nontemporal_store(r1, a4 + q + stride);
-  }
-  if (q < n4) {
-    const v4i c0 = __builtin_nontemporal_load(c4 + q);
-    v4i r0;
-    r0.x = Ln[c0.x]; r0.y = Ln[c0.y]; r0.z = Ln[c0.z]; r0.w = Ln[c0.w];
-    __builtin_nontemporal_store(r0, a4 + q);
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (arcs & 3)) {
-    const int64_t i = (n4 << 2) + threadIdx.x;
-    al[i] = Ln[col[i]];
-  }
-}
-
-__global__ __launch_bounds__(256) void k_al_scatter(const int32_t* __restrict__ chlist,
-                                                    const uint4* __restrict__ chflag16, int64_t ngroups,
-                                                    const int32_t* __restrict__ cowner,
-                                                    const int64_t* __restrict__ cch,
-                                                    const unsigned long long* __restrict__ counters,
-                                                    unsigned long long* __restrict__ counters_next,
-                                                    const int64_t* __restrict__ cptr,
-                                                    const uint32_t* __restrict__ cpos,
-                                                    const int32_t* __restrict__ Ln,
-                                                    int32_t* __restrict__ al, int64_t thr,
-                                                    FrontierMarks fm, int32_t* __restrict__ fr_all_next,
-                                                    int frontier, int64_t fr_thr,
-                                                    int32_t* __restrict__ Lold,
-                                                    const int32_t* __restrict__ col_fold, int64_t arcs,
-                                                    int32_t* __restrict__ gword, int keep_bits,
-                                                    const uint32_t* __restrict__ gbits,
-                                                    unsigned long long* __restrict__ abits) {
-  // the next superstep's counters (the other parity; no memset launch)
-  if (blockIdx.x == 0 && threadIdx.x < 3) counters_next[threadIdx.x] = 0ull;
-  const bool rebuild = rebuild_wanted(counters, thr);
-  // al changes here (scatter, or the plain folded rebuild), so the arc giant bits go
-  // stale: gword[2] = 0 -- except in superstep 3's scatter (keep_bits, host-set), right
-  // after the bits-mode rebuild whose bits they are: a column that LEFT G (its gbits
-  // bit, the rebuild's bitmap of the same vector and G) clears its positions' bits, one
-  // atomic each (rare: R-MAT superstep 3 moves labels onto G); a column that joined G
-  // leaves its bits clear.  The bits then hold a lower bound of every row's G votes, all
-  // superstep 4's settle needs, and its k_abits_pass is skipped (round 6; exact upkeep
-  // with an atomic per written position cost superstep 3 0.25 ms, round 3).  A wanted,
-  // non-folded rebuild follows this kernel and sets gword[2] itself.
-  const bool keep = keep_bits != 0 && !rebuild;
-  if (blockIdx.x == 0 && threadIdx.x == 0 && (!rebuild || col_fold) && !keep) gword[2] = 0;
-  const int32_t Gk = gword[0];
-  auto left_g = [&](int64_t u, int32_t lab) -> bool {
-    return keep && lab != Gk && ((gbits[u >> 5] >> (u & 31)) & 1u);
-  };
-  // The next superstep tallies every row after a rebuild, with the frontier off, or
-  // when more than fr_thr arcs changed: then nearly every row has a changed neighbour
-  // anyway (R-MAT superstep 3 -> 4: 1.5 % of arcs dirty, 88 % of the arcs in dirty
-  // rows) and the per-position marks would cost more than they save.
-  const bool all = rebuild || !frontier || (int64_t)counters[1] > fr_thr;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *fr_all_next = all ? 1 : 0;
-  const int lane = threadIdx.x & 63;
-  const int64_t wid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  // col_fold (captured converged supersteps): a wanted rebuild is done here, the plain
-  // form, instead of by a k_al_rebuild_hot launch that nearly always returns at once
-  // (one dependent launch fewer per converged superstep)
-  if (rebuild && col_fold) rebuild_all(col_fold, arcs, Ln, al);
-  // one-chunk columns from the list: a lane each, longer rows of positions by the wave
-  if (!rebuild) {
-    const int64_t nl = (int64_t)counters[0];
-    for (int64_t c0 = wid * 64; c0 < nl; c0 += nw * 64) {
-      const int64_t c = c0 + lane;
-      int64_t b = 0;
-      int n = 0;
-      int32_t lab = 0;
-      bool clr = false;
-      if (c < nl) {
-        const int64_t u = chlist[c];
-        b = cptr[u];
-        n = (int)(cptr[u + 1] - b);  // <= kChunkPos
-        lab = Ln[u];
-        Lold[u] = lab;  // frontier sync (after the join)
-        clr = left_g(u, lab);
-      }
-      scatter_runs(b, n, lab, clr, cpos, al, all, fm, abits, lane);
-    }
-  }
-  uint4* __restrict__ flw = const_cast<uint4*>(chflag16);
-  // multi-chunk columns: a wave takes 64 groups of 16 chunk flags, one group per lane,
-  // and clears them.  Lane l of wave w takes group g0 + l * nw + w: the consecutive
-  // chunks of one changed hub column land in different waves (wave-consecutive
-  // groups would hand a column's hundreds of chunks to one wave, one after another)
-  for (int64_t g0 = 0; g0 < ngroups; g0 += nw * 64) {
-    const int64_t gi = g0 + (int64_t)lane * nw + wid;
-    uint4 f = make_uint4(0u, 0u, 0u, 0u);
-    if (gi < ngroups) f = chflag16[gi];
-    const bool any = (f.x | f.y | f.z | f.w) != 0u;
-    if (any) flw[gi] = make_uint4(0u, 0u, 0u, 0u);
-    if (rebuild || __ballot(any) == 0ull) continue;  // the rebuild re-gathers every arc
-    u32 bits = 0u;
-    const u32 fw[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if ((fw[k >> 2] >> (8 * (k & 3))) & 0xFFu) bits |= 1u << k;
-    // every lane pops its next flagged chunk per round: chunks of <= 16 positions are
-    // written by their own lane, longer ones by the whole wave (coalesced cpos)
-    while (__ballot(bits != 0u)) {
-      int64_t b = 0;
-      int n = 0;
-      int32_t lab = 0;
-      bool clr = false;
-      if (bits) {
-        const int t = __ffs(bits) - 1;
-        bits &= bits - 1u;
-        const int64_t cid = gi * 16 + t;
-        const int64_t u = cowner[cid];
-        const int64_t kk = cid - cch[u];
-        b = cptr[u] + kk * kChunkPos;
-        n = (int)min((int64_t)kChunkPos, cptr[u + 1] - b);
-        lab = Ln[u];
-        // frontier sync of a changed label into the next superstep's output vector
-        // (after the join; every changed vertex with local arcs has a chunk 0)
-        if (kk == 0) Lold[u] = lab;
-        clr = left_g(u, lab);
-      }
-      scatter_runs(b, n, lab, clr, cpos, al, all, fm, abits, lane);
-    }
-  }
-}
-
-// After a lazy reset (al0) the first refresh that only scatters needs the L0 arc
-// labels in al first: copied here unless the rebuild that follows rewrites every arc.
-__global__ __launch_bounds__(256) void k_al_fill_unless_rebuild(const unsigned long long* __restrict__ counters,
-                                                                int64_t thr, const v4i* __restrict__ src,
-                                                                v4i* __restrict__ dst, int64_t arcs) {
-  if (rebuild_wanted(counters, thr)) return;
-  const int64_t n4 = arcs >> 2;
-  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x)
-    __builtin_nontemporal_store(__builtin_nontemporal_load(src + q), dst + q);
-  if (blockIdx.x == 0 && threadIdx.x < (arcs & 3)) {
-    const int64_t i = (n4 << 2) + threadIdx.x;
-    reinterpret_cast<int32_t*>(dst)[i] = reinterpret_cast<const int32_t*>(src)[i];
-  }
-}
-
-// many changes: al[i] = L_next[col[i]].  Random label gathers: each thread
-// keeps 8 gathers in flight (two int4 column quads), streams col/al non-temporally.
-template <bool kIfWanted>
-__global__ __launch_bounds__(256) void k_al_rebuild(const unsigned long long* __restrict__ counters,
-                                                    int64_t thr, const int32_t* __restrict__ col,
-                                                    int64_t arcs,
-                                                    const int32_t* __restrict__ Ln,
-                                                    int32_t* __restrict__ al, int32_t* __restrict__ gword) {
-  if (kIfWanted && !rebuild_wanted(counters, thr)) return;
-  if (blockIdx.x == 0 && threadIdx.x == 0) gword[2] = 0;  // no arc giant bits from this form
-  rebuild_all(col, arcs, Ln, al);
-}
-
-// Giant-label bitmap of L (before a rebuild): bit u = (L[u] == G), G = L[0], the label
-// of the highest-degree vertex.  Once the labels concentrate (R-MAT, after superstep
-// 2: ~98.5 % of the arcs point at a column labelled G) the rebuild gathers one BIT per
-// arc -- the hot slots' bits from LDS, the rest from this 1-bit-per-slot array, which
-// stays in L2 (2 MB at C3 against the 64 MB label vector) -- and reads the label
-// vector only for the columns whose bit is clear.  One ballot per 64 slots; lanes
-// 0..7 store the wave's eight 64-bit words (64 contiguous bytes).
-// The giant-label candidate of a label vector: the most frequent label among the
-// kPickK highest-degree vertices (degree ranks k < kPickK; at P > 1 rank k lives at slot
-// (k mod P) S + k / P), and whether it holds >= 1/5 of them (gword[1]: the tallies'
-// giant step is worth trying).  On R-MAT and Chung-Lu (oracle, scale 21-22) that label
-// is the degree-weighted mode of the whole vector in every superstep -- the top hub's
-// own label is not (Chung-Lu superstep 2: the mode holds 43 % of the arcs' columns, the
-// top hub's label 0.3 %).  One block, a 2K-slot LDS table.  The choice of G only
-// affects speed: every use of it is exact for any G.
-constexpr int kHotLabels = kHotRankedLabels;  // rank-strided label set (P > 1: power-of-two shares)
-constexpr int kHotLabelsSingle = 40960;    // P = 1: the whole 160 KB of LDS
-// bits mode: 1,310,688 slots' bits (the last LDS word counts the set bits first)
-constexpr int64_t kHotBits = 32ll * (kHotLabelsSingle - 1);
-constexpr int kPickK = 1024;
-__global__ __launch_bounds__(1024) void k_giant_pick(const int32_t* __restrict__ L, int64_t n_real, int64_t S,
-                                                     int P, int32_t* __restrict__ gword) {
-  __shared__ u64 tab[2 * kPickK];
-  __shared__ u64 wbest[kPickK / 64];
-  const int t = threadIdx.x;
-  tab[t] = 0ull;
-  tab[t + kPickK] = 0ull;
-  __syncthreads();
-  const int64_t n = n_real < kPickK ? n_real : kPickK;
-  if (t < n) lds_insert(tab, 32 - 11, 2 * kPickK - 1, (u32)L[(int64_t)(t % P) * S + t / P], 1u);
-  __syncthreads();
-  const u64 b = wave_max_u64(umax64(tab[t], tab[t + kPickK]));
-  if ((t & 63) == 0) wbest[t >> 6] = b;
-  __syncthreads();
-  if (t == 0) {
-    u64 m = 0ull;
-#pragma unroll
-    for (int k = 0; k < kPickK / 64; ++k) m = umax64(m, wbest[k]);
-    const int32_t G = (int32_t)(~(u32)m);
-    if (G != gword[0]) gword[2] = 0;  // the arc giant bits are relative to the old G
-    gword[0] = G;
-    gword[3] = 0;  // k_giant_bits counts the set bits of the hot slots here
-    gword[5] = 0;  // no giant-code refresh unless k_code_mode takes it below
-    gword[9] = 0;  // no k_abits_pass since this refresh
-    gword[11] = 0;  // superstep 4's impure-unit list (k_units_pure)
-    gword[1] = n > 0 && 5 * (int64_t)(m >> 32) >= n ? 1 : 0;
-  }
-}
-
-// (abits / nzero: the class-blocked rebuild that follows ORs the arc giant bits of its
-// pieces into abits[0, nzero): zeroed here, one launch ahead)
-// gword[3] counts the set bits of the hot slots, slot i with (i & hmask) < hlim: the first
-// kHotBits slots at P = 1 (hmask all ones), the first hlim slots of every slice of a
-// rank-strided vector (hmask = slice - 1) -- the degree-ranked top set either way
-template <bool kIfWanted>
-__global__ __launch_bounds__(256) void k_giant_bits(const unsigned long long* __restrict__ counters, int64_t thr,
-                                                    const int32_t* __restrict__ L, int64_t n,
-                                                    int32_t* __restrict__ gword,
-                                                    unsigned long long* __restrict__ bits,
-                                                    unsigned long long* __restrict__ abits, int64_t nzero,
-                                                    uint64_t hmask, int64_t hlim) {
-  if (kIfWanted && !rebuild_wanted(counters, thr)) return;
-  // the hot-bit count: summed per block in LDS, one global atomic per block (a returning
-  // atomic per wave on the one word serialised: ~2,500 of them, ~30 us at C3)
-  __shared__ u32 bcnt;
-  if (threadIdx.x == 0) bcnt = 0u;
-  __syncthreads();
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nzero; i += (int64_t)gridDim.x * blockDim.x)
-    abits[i] = 0ull;
-  const int32_t G = gword[0];
-  const int lane = threadIdx.x & 63;
-  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t g0 = (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 512; g0 < n; g0 += nw * 512) {
-    int32_t v[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int64_t i = g0 + k * 64 + lane;
-      v[k] = i < n ? (int32_t)ld_stream(L + i) : ~G;
-    }
-    unsigned long long mine = 0ull;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const unsigned long long m = __ballot(v[k] == G);
-      if (lane == k) mine = m;
-    }
-    if (lane < 8 && g0 + lane * 64 < n) bits[(g0 >> 6) + lane] = mine;
-    // the hot slots' set bits (the rebuild's bits-mode test without an LDS fill); hlim
-    // and the slice are multiples of 64, so a bit word is hot or cold as a whole
-    const int64_t wi = g0 + lane * 64;
-    const bool hot = lane < 8 && wi < n && (int64_t)((uint64_t)wi & hmask) < hlim;
-    if (__ballot(hot)) {
-      const u32 c = wave_sum_u32(hot ? (u32)__popcll(mine) : 0u);
-      if (lane == 0 && c) atomicAdd(&bcnt, c);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0 && bcnt) atomicAdd(&gword[3], (int32_t)bcnt);
-}
-
-// al[i] = lab(col[i]) over every arc by the calling grid (one wave per 512-arc batch,
-// grid-stride); bits: also the arc giant bits (abits: bit i = al[i] == G, one ballot
-// per 64 arcs), which the next superstep's full tally settles rows from (k_settle_*).
-template <typename Lab>
-__device__ __forceinline__ void rebuild_stream(Lab lab, int32_t G, bool bits, const int32_t* __restrict__ col,
-                                               int64_t arcs, int32_t* __restrict__ al,
-                                               unsigned long long* __restrict__ abits) {
-  // lane-consecutive arcs: one gather instruction covers 64 consecutive arcs of
-  // a row, whose sorted columns often share lines (hub rows) -> fewer L2 requests.
-  // Full 512-arc batches are software-pipelined: the next batch's column loads are in
-  // flight while this batch's labels are looked up and stored.
-  const int lane = threadIdx.x & 63;
-  const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
-  const int64_t step = nw * 512;
-  const int64_t nfull = arcs & ~(int64_t)511;  // arcs of the full batches
-  int64_t base = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 512;
-  int32_t c[8];
-  if (base < nfull) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) c[k] = __builtin_nontemporal_load(col + base + k * 64 + lane);
-  }
-  for (; base < nfull; base += step) {
-    int32_t cn[8], r[8];
-    const int64_t nb = base + step;
-    if (nb < nfull) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) cn[k] = __builtin_nontemporal_load(col + nb + k * 64 + lane);
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) r[k] = lab(c[k]);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) __builtin_nontemporal_store(r[k], al + base + k * 64 + lane);
-    if (bits) {
-      unsigned long long mine = 0ull;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const unsigned long long m = __ballot(r[k] == G);
-        if (lane == k) mine = m;
-      }
-      if (lane < 8) abits[(base >> 6) + lane] = mine;
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) c[k] = cn[k];
-  }
-  // the partial last batch (one wave)
-  if (nfull < arcs && base == nfull) {
-    for (int k = 0; k < 8; ++k) {
-      const int64_t i = base + k * 64 + lane;
-      const bool v = i < arcs;
-      const int32_t x = v ? lab(col[i]) : 0;
-      if (v) al[i] = x;
-      const unsigned long long m = __ballot(v && x == G);
-      if (bits && lane == 0 && base + k * 64 < arcs) abits[(base >> 6) + k] = m;
-    }
-  }
-}
-
-// The same stream in a three-stage software pipeline over 512-arc batches (P = 1 hot
-// kernel): at step t the column loads of batch t + 3 are issued, batch t + 2's probe
-// words fetched (p1: an LDS word, or an L2 word of gbits for a cold column), batch
-// t + 1's labels resolved (p2: from the word, else a gather of L[c]) and batch t stored,
-// so each wave keeps three batches' dependent loads in flight instead of one batch's
-// chain (col -> bit word -> label).  Rings of 3 column sets and 2 word / label sets,
-// six steps unrolled so no set is copied while its loads are in flight.
-// The main loop is branch-free (every stage's batch exists, and p1 / p2 issue their
-// loads unconditionally, at a clamped address where the value is not needed): the
-// vector-memory counter is then tracked exactly, and waiting for batch t's labels does
-// not wait for the loads of batches t + 1 .. t + 3 -- with a conditional load in the
-// loop the compiler waited for every outstanding load (vmcnt(0)) at each step, which
-// serialised the pipeline.  The last few batches run guarded.
-//   fetch(t, c)  batch t's columns        probe(c, w)   p1 words
-//   resolve(c, w, r)  p2 labels          store(t, r)    stores (+ arc giant bits)
-template <typename Pre, typename F, typename Q, typename R, typename St>
-__device__ __forceinline__ void pipe3(int64_t nb, Pre pre, F fetch, Q probe, R resolve, St store) {
-  int32_t c0[8], c1[8], c2[8], r0[8], r1[8];
-  u32 w0[8], w1[8];
-  int64_t t = 0;
-  if (nb <= 0) return;
-  // pre(t, slot): batch t's descriptors (six slots, batch t in slot t mod 6), four
-  // steps ahead of its fetch
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (k < nb) pre(k, k);
-  fetch(0, c0, 0);
-  if (nb > 1) fetch(1, c1, 1);
-  if (nb > 2) fetch(2, c2, 2);
-  probe(c0, w0);
-  if (nb > 1) probe(c1, w1);
-  resolve(c0, w0, r0);
-#define LPA_PIPE_STEP(GUARD, I, CA, CB, CC, WA, WB, RA, RB) \
-  if (!GUARD || t + 4 < nb) pre(t + 4, (I + 4) % 6);      \
-  if (!GUARD || t + 3 < nb) fetch(t + 3, CA, (I + 3) % 6); \
-  if (!GUARD || t + 2 < nb) probe(CC, WA);                 \
-  if (!GUARD || t + 1 < nb) resolve(CB, WB, RB);           \
-  store(t, RA, I);                                         \
-  ++t;                                                     \
-  if (GUARD && t >= nb) break;
-#define LPA_PIPE_CYCLE(GUARD)                                 \
-  LPA_PIPE_STEP(GUARD, 0, c0, c1, c2, w0, w1, r0, r1)        \
-  LPA_PIPE_STEP(GUARD, 1, c1, c2, c0, w1, w0, r1, r0)        \
-  LPA_PIPE_STEP(GUARD, 2, c2, c0, c1, w0, w1, r0, r1)        \
-  LPA_PIPE_STEP(GUARD, 3, c0, c1, c2, w1, w0, r1, r0)        \
-  LPA_PIPE_STEP(GUARD, 4, c1, c2, c0, w0, w1, r0, r1)        \
-  LPA_PIPE_STEP(GUARD, 5, c2, c0, c1, w1, w0, r1, r0)
-  // unguarded cycles: their last step (t + 5) issues pre(t + 9), so t + 9 < nb keeps
-  // every descriptor read inside the list (a piece list has no padding past its end)
-  while (t + 10 <= nb) {
-    LPA_PIPE_CYCLE(false)
-  }
-  while (true) {
-    LPA_PIPE_CYCLE(true)
-  }
-#undef LPA_PIPE_CYCLE
-#undef LPA_PIPE_STEP
-}
-
-// arc giant bits of one 64-lane chunk at arc position st (len lanes live, lanes
-// consecutive): one word, or two when st is not word-aligned (ORed: other chunks share
-// the words; nzero-ed by k_giant_bits beforehand)
-__device__ __forceinline__ void or_arc_bits(unsigned long long* __restrict__ abits, u32 st, unsigned long long m,
-                                            int lane) {
-  const u32 wd = st >> 6, off = st & 63u;
-  if (m && lane == 0) atomicOr(&abits[wd], m << off);
-  if (m && lane == 1 && off && (m >> (64u - off))) atomicOr(&abits[wd + 1], m >> (64u - off));
-}
-
-// the plain stream: this wave's whole 512-arc batches of [0, arcs), then the partial
-// last batch (one wave)
-template <typename P1, typename P2>
-__device__ __forceinline__ void rebuild_pipe(P1 p1, P2 p2, int32_t G, bool bits, const int32_t* __restrict__ col,
-                                             int64_t arcs, int32_t* __restrict__ al,
-                                             unsigned long long* __restrict__ abits) {
-  const int lane = threadIdx.x & 63;
-  const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
-  const int64_t wv = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t nbatch = arcs >> 9;
-  const int64_t nb = wv < nbatch ? (nbatch - wv + nw - 1) / nw : 0;
-  auto base = [&](int64_t t) { return (wv + t * nw) * 512; };
-  auto pre = [](int64_t, int) {};
-  auto fetch = [&](int64_t t, int32_t (&c)[8], int) {
-    const int64_t b = base(t);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) c[k] = __builtin_nontemporal_load(col + b + k * 64 + lane);
-  };
-  auto probe = [&](const int32_t (&c)[8], u32 (&w)[8]) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) w[k] = p1(c[k]);
-  };
-  auto resolve = [&](const int32_t (&c)[8], const u32 (&w)[8], int32_t (&r)[8]) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) r[k] = p2(c[k], w[k]);
-  };
-  auto store = [&](int64_t t, const int32_t (&r)[8], int) {
-    const int64_t b = base(t);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) __builtin_nontemporal_store(r[k], al + b + k * 64 + lane);
-    if (bits) {
-      unsigned long long mine = 0ull;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const unsigned long long m = __ballot(r[k] == G);
-        if (lane == k) mine = m;
-      }
-      if (lane < 8) abits[(b >> 6) + lane] = mine;
-    }
-  };
-  pipe3(nb, pre, fetch, probe, resolve, store);
-  // the partial last batch (one wave)
-  const int64_t nfull = nbatch << 9;
-  if (nfull < arcs && wv == nbatch % nw) {
-    for (int k = 0; k < 8; ++k) {
-      const int64_t i = nfull + k * 64 + lane;
-      const bool v = i < arcs;
-      const int32_t c = v ? col[i] : 0;
-      const int32_t x = p2(c, p1(c));
-      if (v) al[i] = x;
-      const unsigned long long m = __ballot(v && x == G);
-      if (bits && lane == 0 && nfull + k * 64 < arcs) abits[(nfull >> 6) + k] = m;
-    }
-  }
-}
-
-// The class-blocked part of a labels-mode rebuild (P = 1).  A labels-mode rebuild is
-// bound by its L2-missing gathers (C3 superstep 1: 3.6x the algorithmic bytes); a block
-// group (blocks b = x mod 8, one XCD under the observed round-robin placement, speed
-// only) streams the pieces of column class x -- the class segments of the rows of degree
-// > block_deg, which keep their columns in (class, column) order -- so an XCD's gathers
-// touch 1/8 of the label lines and its L2 holds far more of them (C3, simulated: 0.18
-// -> 0.02 missing gathers per arc).  8 pieces (<= 64 arcs, lane-consecutive) per batch
-// and wave, in pipe3's pipeline; a lane past its piece carries column 0 (a hot-set LDS
-// read) and stores nothing; the descriptors ride a register ring four batches ahead
-// (scalar loads in the stage that used them cost a round trip per step: the pieces
-// phase ran at ~7 us per batch and wave).  bits: the arc giant bits, ORed.
-#ifdef LPA_BLKTIME
-// diagnostic build only (csrc/Makefile blktime): per block of the last blocked rebuild,
-// the wall clock at its start, after its pieces and at its end
-__device__ unsigned long long g_blk_time[3 * 512];
-extern "C" int lpa_diag_blk_times(unsigned long long* out) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_blk_time), sizeof(g_blk_time)) != hipSuccess) return -1;
-  static unsigned long long zero[3 * 512];
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_blk_time), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
-}
-#endif
-struct BlkInfo {
-  int64_t off[kMaxBlkClasses + 1];  // class x: pieces [off[x], off[x + 1]), multiples of 8
-  int64_t a0;                       // listed arcs [0, a0) (0: no blocked part)
-  int phases;                       // classes / 8: group x streams x, x + 8, ...
-};
-template <typename P1, typename P2>
-__device__ __forceinline__ void rebuild_pieces(P1 p1, P2 p2, int32_t G, bool bits, const u64* __restrict__ pieces,
-                                               int64_t q0, int64_t q1, int64_t wi, int64_t nwv,
-                                               const int32_t* __restrict__ col, int32_t* __restrict__ al,
-                                               unsigned long long* __restrict__ abits) {
-  const int lane = threadIdx.x & 63;
-  auto uni = [](int64_t v) -> int64_t {
-    return (int64_t)(((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)((u64)v >> 32)) << 32) |
-                     (u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)v));
-  };
-  const int64_t step = uni(nwv * 8), first = uni(q0 + wi * 8), last = uni(q1);
-  const int64_t nb = first < last ? (last - first + step - 1) / step : 0;
-  // descriptor ring: lane k < 8 of slot j holds piece k of the batch in slot j, loaded
-  // four steps ahead (a vector load, so waiting for it never waits on newer loads);
-  // the stages read it with readlane
-  u64 dr[6];
-  auto pre = [&](int64_t t, int j) {
-    const int64_t qq = first + t * step;
-    dr[j] = lane < 8 ? pieces[qq + lane] : 0ull;
-  };
-  auto desc = [&](int j, int k) -> u64 {
-    return ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(dr[j] >> 32), k) << 32) |
-           (u64)(u32)__builtin_amdgcn_readlane((int)(u32)dr[j], k);
-  };
-  auto fetch = [&](int64_t, int32_t (&c)[8], int j) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const u64 d = desc(j, k);
-      const bool live = lane < (int)(d >> 32);
-#if defined(LPA_BLK_ABL) && LPA_BLK_ABL == 3
-      const int32_t x = (int32_t)(((u32)d + lane) * 2654435761u >> 8);  // ablation: no column loads
-#else
-      const int32_t x = __builtin_nontemporal_load(col + (u32)d + (live ? lane : 0));
-#endif
-      c[k] = live ? x : 0;
-    }
-  };
-  // the probe word is read where it is used (an LDS read in the labels / hybrid modes
-  // this path serves): no word ring, 16 VGPRs fewer
-  auto probe = [&](const int32_t (&)[8], u32 (&)[8]) {};
-  auto resolve = [&](const int32_t (&c)[8], const u32 (&)[8], int32_t (&r)[8]) {
-#pragma unroll
-#if defined(LPA_BLK_ABL) && LPA_BLK_ABL == 1
-    for (int k = 0; k < 8; ++k) r[k] = c[k];  // ablation: no label gathers
-#else
-    for (int k = 0; k < 8; ++k) r[k] = p2(c[k], p1(c[k]));
-#endif
-  };
-  auto store = [&](int64_t, const int32_t (&r)[8], int j) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const u64 d = desc(j, k);
-      const int ln = (int)(d >> 32);
-#if defined(LPA_BLK_ABL) && LPA_BLK_ABL == 2
-      if (lane < ln && r[k] == -7) al[(u32)d + lane] = 0;  // ablation: no stores
-#else
-      if (lane < ln) __builtin_nontemporal_store(r[k], al + (u32)d + lane);
-      if (bits) or_arc_bits(abits, (u32)d, __ballot(lane < ln && r[k] == G), lane);
-#endif
-    }
-  };
-  pipe3(nb, pre, fetch, probe, resolve, store);
-}
-
-// al[] rebuild with an LDS hot set (the slots of the highest-degree vertices: at P = 1
-// the first slots, 30-40 % of all arc targets on R-MAT).  The rebuild is bound by the
-// line traffic of its L2-missing 4-B gathers, and every gather served from LDS is one
-// L2 request fewer.  One 1024-thread block per CU, 160 KB of LDS, in one of two modes
-// that every block picks alike from the same data:
-//   bits    (most hot slots carry the giant label G): LDS holds the giant-label bits of
-//           the first 1.31 M slots, the other columns' bits come from gbits (L2); a
-//           set bit is G, a clear one reads L[c].
-//   labels  LDS holds the labels of the first 40,960 slots; the rest read L[c].
-// kRanked (P > 1, power-of-two slices and rank count): the hottest vertices of rank
-// r's slice are its first slots (degree rank k lives at slot (k mod P) S + k / P),
-// so the global top set is the first H slots of every slice: slot c is hot iff
-// (c mod S) < H, at LDS index (c / S) H + c mod S (H = 2^hot_lg labels or 2^hb_lg bits).
-// kPieces (P = 1, a class-blocked handle: its labels-mode rebuild goes through the pieces):
-// its own instantiation, so that the plain one's registers are allocated without the
-// pieces' descriptor ring (one form for both spilled 16 VGPRs to scratch at the 128 of
-// four waves per SIMD)
-template <bool kIfWanted, bool kRanked, bool kPieces = false>
-__global__ __launch_bounds__(1024) void k_al_rebuild_hot(const unsigned long long* __restrict__ counters,
-                                                         int64_t thr, const int32_t* __restrict__ col,
-                                                         int64_t arcs, const int32_t* __restrict__ Ln,
-                                                         int32_t nhot, int32_t* __restrict__ al,
-                                                         int slice_lg, int hot_lg, int hb_lg,
-                                                         const uint32_t* __restrict__ gbits, int64_t nbits,
-                                                         int32_t* __restrict__ gword,
-                                                         unsigned long long* __restrict__ abits,
-                                                         const u64* __restrict__ pieces, BlkInfo blk,
-                                                         const int32_t* __restrict__ skip) {
-  if (kIfWanted && !rebuild_wanted(counters, thr)) return;
-  if (skip && *skip) return;  // the giant-code refresh replaces this rebuild (k_code_mode)
-  __shared__ u32 hot[kHotLabelsSingle];
-  u32* s_cnt = &hot[kHotLabelsSingle - 1];   // beyond the bit words; labels mode refills it
-  // ---- the giant-label bits of the hot slots, and how many are set ----
-  const int64_t nhb = kRanked ? ((int64_t)(nbits >> slice_lg) << hb_lg) : (nbits < kHotBits ? nbits : kHotBits);
-  const int nhw = (int)((nhb + 31) >> 5);
-  if (threadIdx.x == 0) *s_cnt = 0u;
-  __syncthreads();
-  int cnt = 0;
-  for (int q = threadIdx.x; q < nhw; q += 1024) {
-    int64_t gw = q;
-    if constexpr (kRanked) gw = ((int64_t)(q >> (hb_lg - 5)) << (slice_lg - 5)) + (q & ((1 << (hb_lg - 5)) - 1));
-    const u32 w = gbits[gw];
-    hot[q] = w;
-    cnt += __popc(w);
-  }
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-  if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(s_cnt, (u32)cnt);
-  __syncthreads();
-  const bool bits = 2 * (int64_t)*s_cnt >= nhb && nhb > 0;  // uniform: the same data in every block
-  // hybrid (P = 1): G on >= 1/8 of the bit-range slots but not on half -- labels-mode
-  // gathers that also write the arc giant bits (the next superstep's settle).  (Taking a
-  // cold column's G from its gbits bit instead of its label measured slower: C5 186.7 ->
-  // 176.4 GTEPS.)
-  const bool hyb = !kRanked && !bits && 8 * (int64_t)*s_cnt >= nhb && nhb > 0;
-  const int32_t G = gword[0];
-  // bits / hybrid modes also write the arc giant bits (abits: bit i = al[i] == G, one
-  // ballot per 64 arcs), which the next superstep's full tally settles rows from
-  // (k_settle_*)
-  if (blockIdx.x == 0 && threadIdx.x == 0) gword[2] = (bits || hyb) ? 1 : 0;
-  if (!bits) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < nhot; i += 1024)
-      hot[i] = (u32)(kRanked ? Ln[((int64_t)(i >> hot_lg) << slice_lg) + (i & ((1 << hot_lg) - 1))] : Ln[i]);
-    __syncthreads();
-  }
-  const u32 nh = (u32)nhot;
-  const u32 smask = kRanked ? (1u << slice_lg) - 1u : 0u, hcap = 1u << hot_lg, bcap = 1u << hb_lg;
-  auto lab = [&](int c) -> int32_t {
-    if (bits) {
-      u32 w;
-      if constexpr (kRanked) {
-        const u32 j = (u32)c & smask;
-        w = j < bcap ? hot[((((u32)c >> slice_lg) << hb_lg) + j) >> 5] : gbits[(u32)c >> 5];
-      } else {
-        w = (u32)c < (u32)nhb ? hot[(u32)c >> 5] : gbits[(u32)c >> 5];
-      }
-      return ((w >> ((u32)c & 31u)) & 1u) ? G : Ln[c];
-    }
-    if constexpr (kRanked) {
-      const u32 j = (u32)c & smask;
-      return j < hcap ? (int32_t)hot[(((u32)c >> slice_lg) << hot_lg) + j] : Ln[c];
-    } else {
-      return (u32)c < nh ? (int32_t)hot[c] : Ln[c];
-    }
-  };
-  if constexpr (kRanked) {
-    rebuild_stream(lab, G, bits, col, arcs, al, abits);
-  } else {
-    // branch-free probes (pipe3): both sources are read -- the LDS word at a clamped
-    // index, the gbits word / the label at a fixed address where it is not needed (the
-    // wave's lanes then share one line)
-    const u32 nhbu = (u32)nhb;
-    // (the slots' labels through a buffer descriptor: launch_rebuild takes this kernel at
-    // P = 1 only up to kHotMaxSlots = 2^29 slots, so every byte offset fits the voffset)
-    const auto ln_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Ln, 0, (int)(nbits * 4), 0x00020000);
-    constexpr int kPast = (int)0x80000000u;  // past every record count: no request
-    auto run = [&](auto p1, auto p2, bool wbits) {
-      // uniform: labels / hybrid mode of a blocked handle (the bits mode through the
-      // pieces measured slower, round 6: C5 superstep 3 13.4 -> 17.4 ms, C4 superstep 2
-      // 8.9 -> 12.8 ms -- its lookups hit LDS / L2 anyway, the split arc ranges cost)
-      if (kPieces && !bits) {
-        const int grp = blockIdx.x & 7;
-        const int64_t nwv = (int64_t)(gridDim.x >> 3) * (blockDim.x >> 6);
-        const int64_t wi = (int64_t)(blockIdx.x >> 3) * (blockDim.x >> 6) + (threadIdx.x >> 6);
-#ifdef LPA_BLKTIME
-        if (threadIdx.x == 0 && blockIdx.x < 512) g_blk_time[3 * blockIdx.x] = wall_clock64();
-#endif
-        for (int ph = 0; ph < blk.phases; ++ph)
-          rebuild_pieces(p1, p2, G, wbits, pieces, blk.off[grp + 8 * ph], blk.off[grp + 8 * ph + 1], wi, nwv,
-                         col, al, abits);
-#ifdef LPA_BLKTIME
-        if ((threadIdx.x & 63) == 0 && blockIdx.x < 512) atomicMax(&g_blk_time[3 * blockIdx.x + 1], wall_clock64());
-#endif
-        // then every block: the plain stream over the rows below block_deg
-        rebuild_pipe(p1, p2, G, wbits, col + blk.a0, arcs - blk.a0, al + blk.a0, abits + blk.a0 / 64);
-#ifdef LPA_BLKTIME
-        if ((threadIdx.x & 63) == 0 && blockIdx.x < 512) atomicMax(&g_blk_time[3 * blockIdx.x + 2], wall_clock64());
-#endif
-      } else {
-        rebuild_pipe(p1, p2, G, wbits, col, arcs, al, abits);
-      }
-    };
-    if (bits) {
-      // the gbits words and the labels through buffer descriptors (base + 32-bit offset:
-      // two VGPRs fewer per address under the 128 of four waves per SIMD, where the 64-bit
-      // form spilled 14), and a lane that needs no word or label takes an offset past the
-      // records: the range check drops its request instead of re-reading a fixed line
-      const auto gb_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)gbits, 0, (int)(((nbits + 31) >> 5) * 4), 0x00020000);
-      run(
-          [&](int c) -> u32 {
-            const bool h = (u32)c < nhbu;
-            const u32 hw = hot[(h ? (u32)c : nhbu - 1u) >> 5];
-            const u32 gw = __builtin_amdgcn_raw_buffer_load_b32(gb_rsrc, h ? kPast : (int)(((u32)c >> 5) << 2), 0, 0);
-            return h ? hw : gw;
-          },
-          [&](int c, u32 w) -> int32_t {
-            const bool g = (w >> ((u32)c & 31u)) & 1u;
-            const int32_t x = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(ln_rsrc, g ? kPast : (int)((u32)c << 2), 0, 0);
-            return g ? G : x;
-          },
-          true);
-    } else {
-      run([&](int c) -> u32 { return hot[(u32)c < nh ? (u32)c : nh - 1u]; },
-          [&](int c, u32 w) -> int32_t {
-            const bool h = (u32)c < nh;
-            const int32_t x = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(ln_rsrc, h ? kPast : (int)((u32)c << 2), 0, 0);
-            return h ? (int32_t)w : x;
-          },
-          hyb);
-    }
-  }
-}
-
-// al[] rebuild of a small label vector (P = 1, < kHotMinSlots slots: it stays in L2 /
-// the Infinity Cache, so an LDS hot set saves no misses while every block's 160 KB fill
-// costs as much as the arcs' stream at C2 scale): the same bits / labels modes, the
-// bits-mode test from k_giant_bits' count of the hot slots' set bits (gword[3]).
-template <bool kIfWanted>
-__global__ __launch_bounds__(256) void k_al_rebuild_small(const unsigned long long* __restrict__ counters,
-                                                          int64_t thr, const int32_t* __restrict__ col, int64_t arcs,
-                                                          const int32_t* __restrict__ Ln, int32_t* __restrict__ al,
-                                                          const uint32_t* __restrict__ gbits, int64_t nbits,
-                                                          int32_t* __restrict__ gword,
-                                                          unsigned long long* __restrict__ abits) {
-  if (kIfWanted && !rebuild_wanted(counters, thr)) return;
-  const int64_t nhb = nbits < kHotBits ? nbits : kHotBits;
-  const bool bits = nhb > 0 && 2 * (int64_t)gword[3] >= nhb;  // uniform
-  const int32_t G = gword[0];
-  if (blockIdx.x == 0 && threadIdx.x == 0) gword[2] = bits ? 1 : 0;
-  if (!bits) {  // labels mode: the plain 16 B/lane gather stream (C2: 0.21 -> ~0.17 ms)
-    rebuild_all(col, arcs, Ln, al);
-    return;
-  }
-  auto lab = [&](int c) -> int32_t {
-    if ((gbits[(u32)c >> 5] >> ((u32)c & 31u)) & 1u) return G;
-    return Ln[c];
-  };
-  rebuild_stream(lab, G, true, col, arcs, al, abits);
-}
-
-// ---------------------------------------------------------------------------
-// Giant codes (round 5): the refresh after superstep 1 without the labels-mode al[]
-// rebuild.  On R-MAT the labels L1 of superstep 1 already have a giant label G (the
-// label of ~97 % of the 1,024 top hubs, ~37 % of the arcs' columns) but not on half the
-// hot slots, so that refresh gathered a full 4-B label per arc (C3: 2.35 ms, 3.6x its
-// algorithmic bytes in L2-missing lines), and superstep 2 read them back only to
-// decide nearly every row for G: a row's G votes above every bucket of a label hash of
-// its other votes make G its strict mode (giant_count; oracle, R-MAT-22: 98 % of the
-// arcs sit in rows so decided with 16 buckets, 100 % of the rows above 64 arcs).
-// A bucket only needs a FUNCTION of the label -- and three buckets suffice (oracle,
-// R-MAT-21 superstep 2: rows of 65-1024 arcs holding 99.9 % of their arcs, every hub row,
-// 90 % of the 9-64-arc rows' arcs decided; 63 buckets: 100 / 100 / 99.4 %) -- so the
-// refresh writes 2-bit codes, 0 = (label == G), else 1 + a hash of the label mod 3:
-//   code2     per slot, 16 to a word (k_code_build): 4 MB at C3, one XCD's L2
-//   al2[i]    per arc of the rows above the cut, code2[col[i]], 16 arcs to a word
-//             (k_code_rebuild; the 655,360 hottest slots' codes in LDS)
-//   al[i]     per arc of the rows below the cut (code_lbin: <= 64 arcs on a label vector
-//             of <= 64 MB, else <= 8), their labels
-// and superstep 2 decides the hub rows (k_lpa_units_code2 + k_hub_decide) and the rows of
-// the other coded rows (k_code_settle) by popcounts of the code words -- no
-// table, no atomics; only the rows left undecided get their al[] entries gathered
-// (k_code_partial_*) and are tallied exactly, in list mode.  Exact for any G and any hash
-// (a label's count is at most its bucket's); gword[5] marks the refresh taken, so the
-// labels-mode rebuild is skipped and superstep 2's refresh rebuilds al[] whatever the
-// change count.
-// (Round 5 first shipped 8-bit codes with 64-bucket LDS histograms: C3 code rebuild 1.41
-// ms, code settle 0.63 ms -- the histogram atomics and the 16 MB code array's L2 misses.)
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ u32 giant_code2(u32 x, u32 G) {
-  return x == G ? 0u : 1u + ((((x * 0x9E3779B1u) >> 24) * 3u) >> 8);
-}
-
-// the four codes' counts among the fields of w whose low bits fm selects:
-// c0 | c1 << 16 (x) and c2 | c3 << 16 (y)
-__device__ __forceinline__ void code2_counts(u32 w, u32 fm, u32& x, u32& y) {
-  const u32 lo = w & fm, hi = (w >> 1) & fm;
-  x += (u32)__popc(fm & ~(lo | hi)) | ((u32)__popc(lo & ~hi) << 16);
-  y += (u32)__popc(hi & ~lo) | ((u32)__popc(lo & hi) << 16);
-}
-// low bits of the fields of word wi that hold arcs [b, e)
-__device__ __forceinline__ u32 code2_fmask(int64_t wi, int64_t b, int64_t e) {
-  const int64_t base = wi * 16;
-  const int64_t l0 = b - base, h0 = e - base;
-  const int lo = (int)(l0 < 0 ? 0 : l0 > 16 ? 16 : l0), hi = (int)(h0 < 0 ? 0 : h0 > 16 ? 16 : h0);
-  const u32 mh = hi >= 16 ? 0xFFFFFFFFu : ((1u << (2 * hi)) - 1u);
-  const u32 ml = lo >= 16 ? 0xFFFFFFFFu : ((1u << (2 * lo)) - 1u);
-  return mh & ~ml & 0x55555555u;
-}
-// G decided from summed counts: its votes above every bucket
-__device__ __forceinline__ bool code2_decided(u32 x, u32 y) {
-  const u32 c0 = x & 0xFFFFu, c1 = x >> 16, c2 = y & 0xFFFFu, c3 = y >> 16;
-  return c0 > max(c1, max(c2, c3));
-}
-__device__ __forceinline__ u32 spread16(u32 v) {
-  v = (v | (v << 8)) & 0x00FF00FFu;
-  v = (v | (v << 4)) & 0x0F0F0F0Fu;
-  v = (v | (v << 2)) & 0x33333333u;
-  return (v | (v << 1)) & 0x55555555u;
-}
-// the 2-bit codes r[k] of arcs b + 64 k + lane (b a multiple of 512) -> 32 words at
-// al2[b / 16 ..): two ballots per chunk, lane l < 32 assembles word l (chunk l / 4)
-__device__ __forceinline__ void store_code2(uint32_t* __restrict__ al2, int64_t b, const int32_t (&r)[8], int lane) {
-  u64 m0 = 0, m1 = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const u64 b0 = __ballot(r[k] & 1), b1 = __ballot((r[k] >> 1) & 1);
-    if ((lane >> 2) == k) {
-      m0 = b0;
-      m1 = b1;
-    }
-  }
-  const int sh = (lane & 3) * 16;
-  const u32 w = spread16((u32)(m0 >> sh) & 0xFFFFu) | (spread16((u32)(m1 >> sh) & 0xFFFFu) << 1);
-  if (lane < 32) al2[(b >> 4) + lane] = w;
-}
-
-// gword[5] = take the giant-code refresh: a rebuild is wanted, G is worth trying, and the
-// bits-mode rebuild (G on >= half the hot slots) does not apply; no arc giant bits then
-__global__ void k_code_mode(const unsigned long long* __restrict__ counters, int64_t thr, int64_t nhb,
-                            int32_t* __restrict__ gword) {
-  if (threadIdx.x != 0) return;
-  const bool on = rebuild_wanted(counters, thr) && gword[1] != 0 && 2 * (int64_t)gword[3] < nhb;
-  gword[5] = on ? 1 : 0;
-  if (on) gword[2] = 0;
-}
-
-// code2 for every slot: 16 labels (four int4 loads) -> one word (vpad is a multiple of 64)
-__global__ __launch_bounds__(256) void k_code_build(const int4* __restrict__ L4, int64_t nw,
-                                                   const int32_t* __restrict__ gword, uint32_t* __restrict__ code2) {
-  if (gword[5] == 0) return;
-  const u32 G = (u32)gword[0];
-  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nw; q += (int64_t)gridDim.x * blockDim.x) {
-    u32 w = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int4 v = L4[4 * q + k];
-      w |= (giant_code2((u32)v.x, G) | (giant_code2((u32)v.y, G) << 2) | (giant_code2((u32)v.z, G) << 4) |
-            (giant_code2((u32)v.w, G) << 6))
-           << (8 * k);
-    }
-    code2[q] = w;
-  }
-}
-
-// pipe3 over this wave's whole 512-arc batches in [bat0, bat1) (grid-stride by waves)
-template <typename P1, typename P2, typename St>
-__device__ __forceinline__ void range_pipe(P1 p1, P2 p2, St st, const int32_t* __restrict__ col, int64_t bat0,
-                                           int64_t bat1) {
-  const int lane = threadIdx.x & 63;
-  const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
-  const int64_t wv = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t nb = bat0 + wv < bat1 ? (bat1 - bat0 - wv + nw - 1) / nw : 0;
-  auto base = [&](int64_t t) { return (bat0 + wv + t * nw) * 512; };
-  auto pre = [](int64_t, int) {};
-  auto fetch = [&](int64_t t, int32_t (&c)[8], int) {
-    const int64_t b = base(t);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) c[k] = __builtin_nontemporal_load(col + b + k * 64 + lane);
-  };
-  auto probe = [&](const int32_t (&c)[8], u32 (&w)[8]) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) w[k] = p1(c[k]);
-  };
-  auto resolve = [&](const int32_t (&c)[8], const u32 (&w)[8], int32_t (&r)[8]) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) r[k] = p2(c[k], w[k]);
-  };
-  auto store = [&](int64_t t, const int32_t (&r)[8], int) { st(base(t), r); };
-  pipe3(nb, pre, fetch, probe, resolve, store);
-}
-
-// al for [pB, arcs) (pB = code_pcut rounded down to a 512-arc batch) and al2 for [0, pA)
-// (pA = code_pcut rounded up, at most the full batches): the batch across code_pcut gets
-// both; the partial last batch (one wave) writes whichever applies.  One 1024-thread
-// block per CU, 160 KB of LDS: the labelled rows (code_lbin) first, with the 40,960
-// hottest labels in LDS, then the codes, with the 655,360 hottest slots' codes in LDS --
-// the gathers are bound by their lane count, not their bytes, so the LDS share is the
-// lever -- and the others from the 2-bit code array (vpad / 4 bytes: L2-resident at C3).
-// kRanked (a partitioned job's rank, round 6): the hot sets are the first 2^hot_lg labels
-// and the first 2^hc_lg codes of EVERY slice (degree rank k lives at slot (k mod P) S +
-// k / P, so these are the global top degree ranks), at LDS index (c / S) H + c mod S as in
-// k_al_rebuild_hot's ranked form; at P = 1 they are the first slots.
-template <bool kRanked>
-__global__ __launch_bounds__(1024) void k_code_rebuild(const int32_t* __restrict__ gword,
-                                                       const int32_t* __restrict__ col, int64_t arcs,
-                                                       const int32_t* __restrict__ Ln, int64_t nslots,
-                                                       const uint32_t* __restrict__ code2, int64_t p64,
-                                                       uint32_t* __restrict__ al2, int32_t* __restrict__ al,
-                                                       int slice_lg, int hot_lg, int hc_lg) {
-  if (gword[5] == 0) return;
-  __shared__ u32 hot[kHotLabelsSingle];
-  const u32 G = (u32)gword[0];
-  const int lane = threadIdx.x & 63;
-  const int64_t nfull = arcs >> 9;
-  const int64_t bA = min((p64 + 511) >> 9, nfull), bB = p64 >> 9;
-  const u32 smask = kRanked ? (1u << slice_lg) - 1u : 0u;
-  // slot c -> its hot-set index (h: whether it has one) for a set of 2^lg per slice
-  auto hot_at = [&](int c, int lg, u32 nflat, bool& h) -> u32 {
-    if constexpr (kRanked) {
-      const u32 j = (u32)c & smask;
-      h = j < (1u << lg);
-      return (((u32)c >> slice_lg) << lg) + j;
-    } else {
-      h = (u32)c < nflat;
-      return (u32)c;
-    }
-  };
-  // ---- the labels of the rows below the cut ----
-  const u32 nh = kRanked ? (u32)((nslots >> slice_lg) << hot_lg)
-                         : (u32)(nslots < kHotLabelsSingle ? nslots : kHotLabelsSingle);
-  for (u32 i = threadIdx.x; i < nh; i += 1024)
-    hot[i] = (u32)Ln[kRanked ? ((int64_t)(i >> hot_lg) << slice_lg) + (i & ((1u << hot_lg) - 1u)) : (int64_t)i];
-  __syncthreads();
-  range_pipe([&](int c) -> u32 {
-               bool h;
-               const u32 k = hot_at(c, hot_lg, nh, h);
-               return hot[h ? k : nh - 1u];
-             },
-             [&](int c, u32 w) -> int32_t {
-               bool h;
-               (void)hot_at(c, hot_lg, nh, h);
-               const int32_t x = Ln[h ? 0 : c];
-               return h ? (int32_t)w : x;
-             },
-             [&](int64_t b, const int32_t (&r)[8]) {
-#pragma unroll
-               for (int k = 0; k < 8; ++k) __builtin_nontemporal_store(r[k], al + b + k * 64 + lane);
-             },
-             col, bB, nfull);
-  // ---- the codes of the rows above ----
-  __syncthreads();
-  // (a multiple of 16 either way: ranked, 2^hc_lg >= 16 codes per slice)
-  const u32 nc = kRanked ? (u32)((nslots >> slice_lg) << hc_lg)
-                         : (u32)(nslots < 16 * kHotLabelsSingle ? nslots : 16 * kHotLabelsSingle);
-  for (u32 q = threadIdx.x; q < nc / 16; q += 1024)
-    hot[q] = code2[kRanked ? ((int64_t)(q >> (hc_lg - 4)) << (slice_lg - 4)) + (q & ((1u << (hc_lg - 4)) - 1u))
-                           : (int64_t)q];
-  __syncthreads();
-  auto cp1 = [&](int c) -> u32 {
-    bool h;
-    const u32 k = hot_at(c, hc_lg, nc, h);
-    const u32 cc = h ? k : nc - 1u;
-    return (hot[cc >> 4] >> (((u32)c & 15u) * 2u)) & 3u;   // (k = c mod 16 where hot)
-  };
-  auto cp2 = [&](int c, u32 w) -> int32_t {
-    bool h;
-    (void)hot_at(c, hc_lg, nc, h);
-    const u32 x = code2[h ? 0u : ((u32)c >> 4)];
-    return (int32_t)(h ? w : ((x >> (((u32)c & 15u) * 2u)) & 3u));
-  };
-  range_pipe(cp1, cp2, [&](int64_t b, const int32_t (&r)[8]) { store_code2(al2, b, r, lane); }, col, 0, bA);
-  // the partial last batch
-  const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
-  const int64_t wv = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const int64_t t0 = nfull << 9;
-  if (t0 < arcs && wv == nfull % nw) {
-    int32_t r[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int64_t i = t0 + k * 64 + lane;
-      r[k] = 0;
-      if (i < arcs) {
-        const u32 x = (u32)Ln[col[i]];
-        if (i < p64) r[k] = (int32_t)giant_code2(x, G);
-        else al[i] = (int32_t)x;
-      }
-    }
-    if (t0 < p64) store_code2(al2, t0, r, lane);   // uniform; al2 covers this batch then
-  }
-}
-
-// k_lpa_units_giant on the 2-bit giant codes (the refresh took them: gsel[5]): ugc[u] = the
+// k_lpa_units_giant on the 2-bit giant codes (the refresh took them: gsel[GW_CODE]): ugc[u] = the
 // unit's code-0 (G) votes, umx[u] = its three other buckets' counts (k_hub_decide sums
 // each over the row and takes the fullest: the row-level bucket test), by popcounts of
 // its <= 33 code words (lane l: word l).  Units in batches of 64 per wave (one descriptor
@@ -3145,9 +1805,9 @@ __global__ __launch_bounds__(256) void k_lpa_units_code2(const uint32_t* __restr
   constexpr int D = 4;
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (blockIdx.x == 0 && threadIdx.x == 0) ndec[0] = ndec[2] = 0;  // unit list, block-row list
-  if (gsel[5] == 0) return;  // k_lpa_units_giant's turn (uniform)
-  if (gsel[1] == 0) return;  // no giant label worth trying: k_hub_decide lists every row
+  if (blockIdx.x == 0 && threadIdx.x == 0) ndec[GD_UNITS] = ndec[GD_ROWS] = 0;  // unit list, block-row list
+  if (gsel[GW_CODE] == 0) return;  // k_lpa_units_giant's turn (uniform)
+  if (gsel[GW_TRY] == 0) return;  // no giant label worth trying: k_hub_decide lists every row
   const int64_t stride = (int64_t)gridDim.x * 4;
   for (int64_t base = (int64_t)blockIdx.x * 4 + w; base < nunits; base += 64 * stride) {
     const int64_t uk = base + (int64_t)lane * stride;
@@ -3287,7 +1947,7 @@ __device__ __forceinline__ void code_settle_rows(const int64_t* __restrict__ rp,
 }
 
 // one launch for the seven settled bins (w16 .. w2, g64 .. g16): block b belongs to the
-// task t with first[t] <= b < first[t + 1]; gword[6] = 0 (the bins' "fr_all" of
+// task t with first[t] <= b < first[t + 1]; gword[GW_WAVE2] = 0 (the bins' "fr_all" of
 // superstep 2: lists) when a giant-code refresh was taken, 1 otherwise (and nothing else
 // happens then)
 struct CodeTasks {
@@ -3297,10 +1957,10 @@ struct CodeTasks {
 __global__ __launch_bounds__(256) void k_code_settle(const int64_t* __restrict__ rp, const uint32_t* __restrict__ al2,
                                                      CodeTasks ct, int32_t* __restrict__ gword,
                                                      int32_t* __restrict__ Ln, uint8_t* __restrict__ rdirty) {
-  const bool on = gword[5] != 0;
-  if (blockIdx.x == 0 && threadIdx.x == 0) gword[6] = on ? 0 : 1;
+  const bool on = gword[GW_CODE] != 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) gword[GW_WAVE2] = on ? 0 : 1;
   if (!on) return;  // uniform
-  const int32_t G = gword[0];
+  const int32_t G = gword[GW_G];
   int t = 0;
   while (t < 6 && (int32_t)blockIdx.x >= ct.first[t + 1]) ++t;
   const int64_t bx = (int64_t)blockIdx.x - ct.first[t], nbx = ct.first[t + 1] - ct.first[t];
@@ -3326,7 +1986,7 @@ __global__ __launch_bounds__(256) void k_code_partial_rows(const int32_t* __rest
                                                            const int32_t* __restrict__ flist,
                                                            const int32_t* __restrict__ fcnt, BinBounds bb, int b0,
                                                            int b1) {
-  if (gword[5] == 0) return;
+  if (gword[GW_CODE] == 0) return;
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int bm = b1 < BIN_G64 ? b1 : BIN_G64;   // [b0, bm): wave bins; [bm, b1): row bins
@@ -3395,7 +2055,7 @@ __global__ __launch_bounds__(256) void k_code_partial_hub(const int32_t* __restr
                                                           const int32_t* __restrict__ ulst,
                                                           const int32_t* __restrict__ nup,
                                                           const Segment* __restrict__ segs) {
-  if (gword[5] == 0) return;
+  if (gword[GW_CODE] == 0) return;
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t nr = nrp ? *nrp : 0, total = nr + *nup;
@@ -3424,10 +2084,10 @@ __global__ __launch_bounds__(256) void k_code_settle_hubs(const int64_t* __restr
                                                           const uint32_t* __restrict__ umx, int64_t n_hub,
                                                           const int32_t* __restrict__ gword, int32_t* __restrict__ Ln,
                                                           uint8_t* __restrict__ rdirty, uint8_t* __restrict__ udirty) {
-  if (gword[5] == 0) return;  // uniform
+  if (gword[GW_CODE] == 0) return;  // uniform
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int32_t G = gword[0];
+  const int32_t G = gword[GW_G];
   for (int64_t h = (int64_t)blockIdx.x * 4 + w; h < n_hub; h += (int64_t)gridDim.x * 4) {
     const int64_t u0 = uoff[h], u1 = uoff[h + 1];
     u64 sg = 0, s1 = 0, s2 = 0, s3 = 0;   // umx: three bucket counts (k_lpa_units_code2)
@@ -3455,12 +2115,12 @@ __global__ __launch_bounds__(256) void k_code_settle_hubs(const int64_t* __restr
 }
 
 // superstep 3: a code settle ran -> list mode for the hub and wave bins (fr_all = 0), the
-// diff scans every slot (settled rows changed), the row bins keep their ranges (gword[7]
+// diff scans every slot (settled rows changed), the row bins keep their ranges (gword[GW_ROWS3]
 // = 1, their al[] entries were written); otherwise the row bins follow fr_all
 __global__ void k_code_commit(int32_t* __restrict__ fr_all, int32_t* __restrict__ gword, int32_t* __restrict__ fcnt) {
   if (threadIdx.x != 0) return;
-  gword[7] = gword[5] ? 1 : *fr_all;
-  if (gword[5]) {
+  gword[GW_ROWS3] = gword[GW_CODE] ? 1 : *fr_all;
+  if (gword[GW_CODE]) {
     *fr_all = 0;
     fcnt[kFcntSettled] = 1;
   }
@@ -3670,11 +2330,6 @@ __global__ void k_first_final(const int64_t* __restrict__ rp, int64_t S, u64* __
   }
 }
 
-inline unsigned cap_grid(int64_t want, int64_t cap) {
-  if (want < 1) want = 1;
-  return (unsigned)(want < cap ? want : cap);
-}
-
 // tally kernels of one superstep; bev marks: 0 start, k+1 after kernel k
 // (0 seg, 1 hub_final + hub_write, 2 wave, 3..7 g16..g1)
 // Tally kernels of one superstep on three streams (the bins write disjoint
@@ -3683,25 +2338,10 @@ inline unsigned cap_grid(int64_t want, int64_t cap) {
 // them concurrently hides the ~2-5 us launch gap of each dependent kernel and the
 // tails of the small bins.  bev (nullable): events 2k / 2k+1 bracket tally kernel
 // k on its own stream (0 units, 1 hub combine, 2..11 bins w8 .. g1).
-int launch_diff(lpa_graph* g, hipStream_t st, const int32_t* Lc, const int32_t* Ln, int64_t s0,
-                int64_t s1, bool sync, int par, int b0 = 0, int b1 = 0, int mode = 0);
-
 // diff (P = 1, concurrent schedule): each stream diffs the slots its own bins
 // produced right after them (aux0 w16..w4, aux1 w2..g1 + isolated, main the seg
 // rows after the hub combine), overlapping most of the diff with the tally tail
 // the per-bin dirty-row lists of this superstep (zeroes the other parity's counts)
-// Gather mode (lpa_build: small label vector, no row above 128 arcs -- C2) for the first
-// kGatherSteps supersteps: their tallies read L[col[i]] (arc_vote), no al[] is written
-// (the scatter only marks the frontier), and the last of them rebuilds al once, for the
-// later supersteps, whose cheaper tallies beat the gathers (C2, same box: label-dense
-// supersteps 0.42-0.49 -> 0.34-0.37 ms gathering, converged ones 0.16-0.22 ms from al[]
-// against 0.25-0.30 gathering; LPA_GATHER_STEPS=99, every superstep gathering, re-measured:
-// supersteps 2-10 2.84 against 2.65 ms)
-#ifndef LPA_GATHER_STEPS
-#define LPA_GATHER_STEPS 6
-#endif
-constexpr int kGatherSteps = LPA_GATHER_STEPS;
-bool gather_now(const lpa_graph* g) { return g->gather && g->since_reset < kGatherSteps; }
 int launch_frontier_lists(lpa_graph* g, hipStream_t st = nullptr, const int32_t* fr = nullptr) {
   if (!st) st = g->stream;
   if (!fr) fr = g->fr_all + g->par;
@@ -3714,18 +2354,6 @@ int launch_frontier_lists(lpa_graph* g, hipStream_t st = nullptr, const int32_t*
                      g->fcnt + 16 * g->par, g->fcnt + 16 * (g->par ^ 1), nbr);
   LPA_HIP(hipGetLastError());
   return LPA_OK;
-}
-
-// label-dense superstep: its diff only counts the changed slots, and its refresh
-// rebuilds al[] unless few changed (k_dense_decide).  P > 1: the count runs after the
-// exchange over the whole replicated vector (launch_refresh), P = 1 per stream inside
-// the tally
-bool dense_refresh(const lpa_graph* g) { return g->since_reset < kDenseSupersteps; }
-
-// superstep 1 from L0 by column runs (k_first_runs); the caller's refresh diffs
-bool first_runs_now(const lpa_graph* g) {
-  return g->first_runs && g->cols_sorted && g->first_best && g->rstart && g->since_reset == 0 && g->arcs > 0 &&
-         !g->serial;
 }
 
 int launch_first(lpa_graph* g, int32_t* Lown) {
@@ -3741,16 +2369,6 @@ int launch_first(lpa_graph* g, int32_t* Lown) {
   LPA_HIP(hipGetLastError());
   return LPA_OK;
 }
-
-// the refresh after superstep 1 or 2 may take the giant codes (after superstep 1 on
-// R-MAT, after superstep 2 on Chung-Lu: the first label vector whose giant carries the
-// hubs without holding half the hot slots).  Round 6: on every rank of a partitioned job
-// too -- the refresh follows the exchange, so it codes the replicated vector, and G (picked
-// from it) is the same on every rank; each rank codes and settles its own rows
-bool code_refresh_now(const lpa_graph* g) { return g->code_ok && g->since_reset <= 1; }
-// ... and superstep 2 (block mode) or 3 then settles from them
-bool code_tally_now(const lpa_graph* g) { return g->code_ok && g->since_reset == 1; }
-bool code_tally3_now(const lpa_graph* g) { return g->code_ok && g->since_reset == 2 && g->code3; }
 
 // the code settle of the seven settled bins in one launch (k_code_settle; it returns at
 // once unless a giant-code refresh was taken): blocks split over the bins by work (a
@@ -3798,7 +2416,7 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
   // their captured graphs pay a cross-queue dependency per node, ~3.5 us, where a
   // one-queue chain pays ~1.9: tools/microbench/mb_launch.hip.  With the frontier off
   // every superstep tallies every row, and the bins' overlap on three streams pays)
-  const bool conv = g->since_reset >= kDenseSupersteps + 2 && g->frontier;
+  const bool conv = converged_now(g) && g->frontier;
   const int nstr = g->serial ? 1 : conv ? g->conv_streams : 3;
   hipStream_t sb = nstr >= 2 ? g->aux_stream[0] : s;
   hipStream_t sc = nstr >= 3 ? g->aux_stream[1] : sb;
@@ -3808,7 +2426,7 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
   // supersteps 2-4 (the label-dense ones after the column-run superstep 1): the tallies
   // try the giant label first (giant_decide); gsel = its word, picked by the previous
   // superstep's refresh from the labels this one reads
-  const int32_t* gsel = (g->since_reset >= 1 && g->since_reset <= 3) ? g->gword : nullptr;
+  const int32_t* gsel = giant_offered_now(g) ? g->gword : nullptr;
   if (bev) LPA_HIP(hipEventRecord(bev[kTallyEv + 4], s));
   // superstep 3: rows settled from the arc giant bits of superstep 2's rebuild (each
   // kernel returns at once unless they are valid): the others' dirty flags, then the
@@ -3816,11 +2434,11 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
   // superstep 4 (one GPU): the same settle for the rows below the hubs, from a fresh
   // abits pass, on aux0 while the main stream re-tallies every hub unit and row (range
   // mode: their staged words are current again for the frontier supersteps); the bins
-  // below the hubs then walk their unsettled rows' lists (fr_bins = gword[4])
+  // below the hubs then walk their unsettled rows' lists (fr_bins = gword[GW_BINS4])
   // (P > 1: each rank settles its owned rows from its own arc giant bits; G is the same
   // on every rank, k_giant_pick reads the replicated vector)
-  const bool settle4 = g->since_reset == 3 && g->abits != nullptr && !gather_now(g);  // its abits come from al
-  const int32_t* fr_bins = settle4 ? g->gword + 4 : fr_all;
+  const bool settle4 = settle4_now(g);
+  const int32_t* fr_bins = settle4 ? g->gword + GW_BINS4 : fr_all;
   if (settle4) {
     if (!g->serial) {
       LPA_HIP(hipEventRecord(g->ev_fork, s));
@@ -3848,7 +2466,7 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
     // superstep 3: rows settled from the arc giant bits of superstep 2's rebuild (each
     // kernel returns at once unless they are valid): the others' dirty flags, then the
     // lists of this superstep are built from them in list mode
-    if (g->since_reset == 2 && g->abits && !block_mode_now(g) && !code_tally3_now(g)) {
+    if (settle3_now(g) && !block_mode_now(g) && !code_tally3_now(g)) {
       const int64_t r0 = g->n_hub, r1 = g->bin_begin[BIN_ISO];
       // the hub rows (main) and the rows below them (aux0) settle side by side: disjoint
       // rows, both read only abits; joined before the commit
@@ -3907,11 +2525,11 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
     }
   }
   // the wave bins' "fr_all": superstep 2 after a giant-code refresh walks the lists above;
-  // the row bins': superstep 3's code commit keeps them in range mode (gword[7])
-  const int32_t* fr_wave = code_tally_now(g) ? g->gword + 6 : fr_bins;
+  // the row bins': superstep 3's code commit keeps them in range mode (gword[GW_ROWS3])
+  const int32_t* fr_wave = code_tally_now(g) ? g->gword + GW_WAVE2 : fr_bins;
   // the labelled row bins of a code refresh (from code_lbin on) take their ranges (superstep
-  // 3 after one: gword[7], k_code_commit); coded row bins below it follow the wave bins
-  const int32_t* fr_rows = code_tally3_now(g) ? g->gword + 7 : fr_bins;
+  // 3 after one: gword[GW_ROWS3], k_code_commit); coded row bins below it follow the wave bins
+  const int32_t* fr_rows = code_tally3_now(g) ? g->gword + GW_ROWS3 : fr_bins;
   auto fr_row = [&](int bin) { return bin < g->code_lbin ? fr_wave : fr_rows; };
   if (bev) LPA_HIP(hipEventRecord(bev[kTallyEv + 5], s));
   if (sb != s) {
@@ -3926,7 +2544,7 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
     // then tallies them (w2 included), beside the hub path on main and the row bins on
     // the third stream (they read neither the flags nor those al[] entries)
     LPA_TRY(launch_code_settle(g, sb, Lown));
-    LPA_TRY(launch_frontier_lists(g, sb, g->gword + 6));
+    LPA_TRY(launch_frontier_lists(g, sb, g->gword + GW_WAVE2));
     BinBounds bnd;
     for (int b = 0; b <= LPA_NBINS; ++b) bnd.b[b] = bb[b];
     hipLaunchKernelGGL(k_code_partial_rows, dim3(2048), dim3(256), 0, sb, g->gword, g->rp, g->col, Lc, g->al,
@@ -3945,23 +2563,23 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
   const bool blk = block_mode_now(g);
   // peel rounds of the wave / unit / block tallies (LPA_DENSE_PEEL in the label-dense
   // supersteps, where a round rarely retires more than a few votes)
-  const int pmax = g->since_reset < kDenseSupersteps ? kDensePeel : kPeelMax;
+  const int pmax = label_dense_now(g) ? kDensePeel : kPeelMax;
   // peel rounds of the row bins (range mode) before a chunk is hashed: none in the
   // label-dense supersteps (measured best of 0/1/2/3 at C3), one in supersteps 3 and 4
   // (C2's rows are still label-dense there: 0.59 -> 0.52 ms each; both are launched
   // eagerly, so no captured graph bakes the value), kPeelSortAfter after that (1 there:
   // C3's converged supersteps +10 %)
-  const int sort_after = g->since_reset < kDenseSupersteps ? 0 : g->since_reset <= 3 ? 1 : kPeelSortAfter;
+  const int sort_after = label_dense_now(g) ? 0 : rows_peel_once_now(g) ? 1 : kPeelSortAfter;
   // superstep 2 in block mode: every hub row by giant counts first (k_lpa_units_giant
   // over all units, k_hub_decide); only the rows it cannot settle are tallied exactly --
   // block-tier rows by k_lpa_block from glist, the longer ones by their units
   const bool giant_units = gsel != nullptr && block_mode_now(g);
-  // the block tiers' rows: in giant mode the undecided ones (glist, count gdec[2]; all
-  // of them when G was not worth trying: gdec[3] as "fr_all"), else the superstep's
+  // the block tiers' rows: in giant mode the undecided ones (glist, count gdec[GD_ROWS]; all
+  // of them when G was not worth trying: gdec[GD_ALL] as "fr_all"), else the superstep's
   // rows or frontier list
   const int32_t* blist = giant_units ? g->glist : g->flist;
-  const int32_t* bcnt = giant_units ? g->gdec + 2 : fcnt;
-  const int32_t* ball = giant_units ? g->gdec + 3 : fr_all;
+  const int32_t* bcnt = giant_units ? g->gdec + GD_ROWS : fcnt;
+  const int32_t* ball = giant_units ? g->gdec + GD_ALL : fr_all;
   // (the block tiers' giant step is then done: no gsel for them)
   const int32_t* bsel = giant_units ? nullptr : gsel;
   // wide tier (rows 4096 < deg <= 8192: 16 waves, a 16K-slot table, one block per CU)
@@ -4011,7 +2629,7 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
   // supersteps (same box: C3 superstep 2 1.87 -> 1.71 ms, C4 9.28 -> 8.89, C5 28.75 ->
   // 28.14), while the converged supersteps, whose critical path is the hub path, lost
   // 8-15 us each that way
-  const bool units_last = !g->serial && g->since_reset >= 1 && g->since_reset <= 3;
+  const bool units_last = units_last_now(g);
   auto launch_units = [&]() -> int {
     if (giant_units && g->n_segs > 0) {
       hipLaunchKernelGGL(k_lpa_units_giant<int32_t>, dim3(cap_grid((g->n_segs + 3) / 4, 2048)), dim3(256), 0, s,
@@ -4025,7 +2643,7 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
       LPA_TRY(launch_hub_decide(g, Lown, g->n_hub, gsel));
       if (code_tally_now(g)) {  // the undecided hub rows' al[] entries (code refresh only)
         hipLaunchKernelGGL(k_code_partial_hub, dim3(2048), dim3(256), 0, s, g->gword, g->rp, g->col, Lc, g->al,
-                           g->glist, g->gdec + 2, g->ulist2, g->gdec, g->segs);
+                           g->glist, g->gdec + GD_ROWS, g->ulist2, g->gdec + GD_UNITS, g->segs);
         LPA_HIP(hipGetLastError());
       }
       // the wide tier's few undecided rows right here on the main stream (the fourth
@@ -4038,7 +2656,8 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
     LPA_TRY(mark(0, s));
     if (n_units > 0 && giant_units) {
       hipLaunchKernelGGL(k_lpa_units, dim3(cap_grid((n_units + 3) / 4, 2048)), dim3(256), 0, s,
-                         g->al, g->segs, n_units, g->stage, g->ucnt, g->ulist2, g->gdec, g->gdec + 3, pmax);
+                         g->al, g->segs, n_units, g->stage, g->ucnt, g->ulist2, g->gdec + GD_UNITS,
+                         g->gdec + GD_ALL, pmax);
       LPA_HIP(hipGetLastError());
     } else if (n_units > 0 && settle4 && g->units_pure) {
       // superstep 4: the pure-G units staged without a tally, the others listed
@@ -4048,7 +2667,8 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
                          g->abits, g->arcs, g->segs, n_units, g->gword, g->stage, g->ucnt, g->ulist2);
       LPA_HIP(hipGetLastError());
       hipLaunchKernelGGL(k_lpa_units, dim3(cap_grid((n_units + 3) / 4, 2048)), dim3(256), 0, s,
-                         g->al, g->segs, n_units, g->stage, g->ucnt, g->ulist2, g->gword + 11, g->gword + 10, pmax);
+                         g->al, g->segs, n_units, g->stage, g->ucnt, g->ulist2, g->gword + GW_PURE_CNT,
+                         g->gword + GW_PURE_ALL, pmax);
       LPA_HIP(hipGetLastError());
     } else if (n_units > 0) {
       hipLaunchKernelGGL(k_lpa_units, dim3(cap_grid((n_units + 3) / 4, 2048)), dim3(256), 0, s,
@@ -4202,7 +2822,7 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
   // hub combine after the bins are queued: its tail kernels on the aux streams
   // run after those streams' bins
   LPA_TRY(mark(2, s));
-  const bool hub_fork = !g->serial && g->since_reset < kDenseSupersteps;
+  const bool hub_fork = !g->serial && label_dense_now(g);
   LPA_TRY(launch_hub_combine(g, Lown, hub_fork, !split, giant_units));
   if (split) {
     LPA_TRY(launch_block_narrow(s));
@@ -4241,243 +2861,7 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
   return LPA_OK;
 }
 
-// al[] rebuild: the LDS hot-label kernel on a single-GPU handle (hub slots are
-// [0, kHotLabels) there), the plain one otherwise
-constexpr int64_t kHotMaxSlots = int64_t(1) << 29;  // k_al_rebuild_hot's 32-bit label offsets (P = 1)
-int launch_rebuild(lpa_graph* g, bool if_wanted, int64_t thr, const int32_t* L,
-                   const unsigned long long* ctr) {
-  hipStream_t s = g->stream;
-  const bool code = if_wanted && code_refresh_now(g);
-  // the giant label of the refreshed vector: the rebuild's bits below and the next
-  // superstep's tallies (launch_tally's gsel) read it
-  if (g->V > 0) {
-    hipLaunchKernelGGL(k_giant_pick, dim3(1), dim3(kPickK), 0, s, L, g->V, g->slice, g->nranks, g->gword);
-    LPA_HIP(hipGetLastError());
-  }
-  const bool ranked = rebuild_ranked(g);
-  // hot slots of the bits-mode / code-mode test (k_giant_bits' count in gword[3]): the
-  // first kHotBits slots at P = 1, the first kHotBits / P (whole bit words) of every slice
-  // of a rank-strided vector -- the same degree-ranked top set
-  const uint64_t hmask = ranked ? (uint64_t)(g->slice - 1) : ~0ull;
-  const int64_t hlim = ranked ? std::min<int64_t>(g->slice, kHotBits / g->nranks / 64 * 64) : kHotBits;
-  const int64_t nhot_bits = ranked ? g->nranks * hlim : std::min<int64_t>(g->vpad, kHotBits);
-  if (g->rebuild_hot && g->nranks == 1 && g->vpad < kHotMinSlots) {
-    const int64_t ngrp = (g->vpad + 511) / 512;
-    const unsigned gb = cap_grid((ngrp + 3) / 4, 4096), gr = cap_grid((g->arcs + 2047) / 2048, 8192);
-    if (if_wanted) {
-      hipLaunchKernelGGL(k_giant_bits<true>, dim3(gb), dim3(256), 0, s, ctr, thr, L, g->vpad, g->gword,
-                         (unsigned long long*)g->gbits, g->abits, (int64_t)0, hmask, hlim);
-      hipLaunchKernelGGL(k_al_rebuild_small<true>, dim3(gr), dim3(256), 0, s, ctr, thr, g->col, g->arcs, L, g->al,
-                         g->gbits, g->vpad, g->gword, g->abits);
-    } else {
-      hipLaunchKernelGGL(k_giant_bits<false>, dim3(gb), dim3(256), 0, s, ctr, thr, L, g->vpad, g->gword,
-                         (unsigned long long*)g->gbits, g->abits, (int64_t)0, hmask, hlim);
-      hipLaunchKernelGGL(k_al_rebuild_small<false>, dim3(gr), dim3(256), 0, s, ctr, thr, g->col, g->arcs, L, g->al,
-                         g->gbits, g->vpad, g->gword, g->abits);
-    }
-  } else if (g->rebuild_hot && ((g->nranks == 1 && g->vpad <= kHotMaxSlots) || ranked)) {
-    int dev_cus = 256;
-    (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, g->device);
-    int slice_lg = 0, hot_lg = 0, hb_lg = 0;
-    int32_t nhot = (int32_t)(g->vpad < kHotLabelsSingle ? g->vpad : kHotLabelsSingle);
-    if (ranked) {
-      while ((int64_t(1) << slice_lg) < g->slice) ++slice_lg;
-      while ((int64_t(1) << hot_lg) < kHotLabels / g->nranks) ++hot_lg;
-      nhot = (int32_t)(g->nranks << hot_lg);
-      // bits per slice: the largest power of two with P of them in the LDS bit budget,
-      // at least one word and at most the slice
-      while ((int64_t(2) << hb_lg) * g->nranks <= kHotBits && (int64_t(2) << hb_lg) <= g->slice) ++hb_lg;
-      if (hb_lg < 5 || slice_lg < 5) hb_lg = 0;
-    }
-    // the giant-label bitmap of L first (same wanted-check: both return at once when
-    // the scatter refreshes instead)
-    const int64_t ngrp = (g->vpad + 511) / 512;
-    // class-blocked labels-mode rebuild (P = 1): a grid of whole 8-block groups
-    const bool blk = !ranked && g->blk_pieces && g->blk_a0 > 0 && dev_cus >= 8;
-    if (blk) dev_cus &= ~7;
-    const int64_t nzero = blk ? g->blk_a0 / 64 : 0;
-    if (if_wanted)
-      hipLaunchKernelGGL(k_giant_bits<true>, dim3(cap_grid((ngrp + 3) / 4, 4096)), dim3(256), 0, s, ctr, thr, L,
-                         g->vpad, g->gword, (unsigned long long*)g->gbits, g->abits, nzero, hmask, hlim);
-    else
-      hipLaunchKernelGGL(k_giant_bits<false>, dim3(cap_grid((ngrp + 3) / 4, 4096)), dim3(256), 0, s, ctr, thr, L,
-                         g->vpad, g->gword, (unsigned long long*)g->gbits, g->abits, nzero, hmask, hlim);
-    LPA_HIP(hipGetLastError());
-    // ranked without a usable bit share: nbits 0 keeps every block in labels mode
-    const int64_t nbits = (ranked && hb_lg == 0) ? 0 : g->vpad;
-    BlkInfo binfo;
-    for (int x = 0; x <= kMaxBlkClasses; ++x) binfo.off[x] = g->blk_off[x];
-    binfo.a0 = blk ? g->blk_a0 : 0;
-    binfo.phases = g->blk_classes / 8;
-#define LPA_HOT_LAUNCH(W, R, B)                                                                  \
-  hipLaunchKernelGGL((k_al_rebuild_hot<W, R, B>), dim3(dev_cus), dim3(1024), 0, s, ctr, thr, g->col, \
-                     g->arcs, L, nhot, g->al, slice_lg, hot_lg, hb_lg, g->gbits, nbits, g->gword, g->abits, \
-                     blk ? g->blk_pieces : nullptr, binfo, code ? g->gword + 5 : nullptr)
-    if (code) {
-      hipLaunchKernelGGL(k_code_mode, dim3(1), dim3(64), 0, s, ctr, thr, nhot_bits, g->gword);
-      LPA_HIP(hipGetLastError());
-    }
-    if (if_wanted) {
-      if (ranked) LPA_HOT_LAUNCH(true, true, false);
-      else if (blk) LPA_HOT_LAUNCH(true, false, true);
-      else LPA_HOT_LAUNCH(true, false, false);
-    } else {
-      if (ranked) LPA_HOT_LAUNCH(false, true, false);
-      else if (blk) LPA_HOT_LAUNCH(false, false, true);
-      else LPA_HOT_LAUNCH(false, false, false);
-    }
-#undef LPA_HOT_LAUNCH
-    if (code) {
-      LPA_HIP(hipGetLastError());
-      hipLaunchKernelGGL(k_code_build, dim3(cap_grid((g->vpad / 16 + 255) / 256, 4096)), dim3(256), 0, s,
-                         (const int4*)L, g->vpad / 16, g->gword, g->code2);
-      LPA_HIP(hipGetLastError());
-      // ranked: 2^hc_lg codes of every slice in LDS (P << hc_lg <= 16 kHotLabelsSingle)
-      int hc_lg = 4;
-      while (ranked && (int64_t(g->nranks) << (hc_lg + 1)) <= 16ll * kHotLabelsSingle &&
-             (int64_t(1) << (hc_lg + 1)) <= g->slice)
-        ++hc_lg;
-      if (ranked)
-        hipLaunchKernelGGL(k_code_rebuild<true>, dim3(dev_cus), dim3(1024), 0, s, g->gword, g->col, g->arcs, L,
-                           g->vpad, g->code2, g->code_pcut, g->al2, g->al, slice_lg, hot_lg, hc_lg);
-      else
-        hipLaunchKernelGGL(k_code_rebuild<false>, dim3(dev_cus), dim3(1024), 0, s, g->gword, g->col, g->arcs, L,
-                           g->vpad, g->code2, g->code_pcut, g->al2, g->al, 0, 0, 0);
-    }
-  } else {
-    const unsigned grid = cap_grid((g->arcs / 4 + 511) / 512, 8192);
-    if (if_wanted)
-      hipLaunchKernelGGL(k_al_rebuild<true>, dim3(grid), dim3(256), 0, s, ctr, thr, g->col,
-                         g->arcs, L, g->al, g->gword);
-    else
-      hipLaunchKernelGGL(k_al_rebuild<false>, dim3(grid), dim3(256), 0, s, ctr, thr, g->col,
-                         g->arcs, L, g->al, g->gword);
-  }
-  LPA_HIP(hipGetLastError());
-  return LPA_OK;
-}
-
-// changed slots in [s0, s1) -> position chunks + dirty-arc count (counters of this
-// superstep's parity)
-int launch_diff(lpa_graph* g, hipStream_t st, const int32_t* Lc, const int32_t* Ln, int64_t s0,
-                int64_t s1, bool sync, int par, int b0, int b1, int mode) {
-  if (s1 <= s0) return LPA_OK;
-  const int64_t nq = (s1 + 3) / 4 - s0 / 4;
-  BinBounds bnd;
-  for (int b = 0; b <= LPA_NBINS; ++b) bnd.b[b] = g->bin_begin[b];
-  // bins [b0, b1) given: the frontier list mode is available (the concurrent tally
-  // of this superstep; its lists are those of g->par)
-  const bool lists = b1 > b0;
-  hipLaunchKernelGGL(k_diff, dim3((unsigned)((nq + kDiffQuads - 1) / kDiffQuads)), dim3(256), 0, st,
-                     (const int4*)Lc, (const int4*)Ln, sync ? const_cast<int32_t*>(Lc) : nullptr, s0, s1,
-                     g->cptr, g->cch, g->chflag, g->chlist, g->counters + 4 * par, bnd, b0, b1,
-                     lists ? g->flist : nullptr, g->fcnt + 16 * g->par, g->fr_all + g->par, mode);
-  LPA_HIP(hipGetLastError());
-  return LPA_OK;
-}
-
-// refresh al[] for L_next (after the exchange, so every rank sees all changes) of the
-// superstep of parity `par`; diff_done: the tally schedule already ran the diff per
-// stream (launch_tally) or the exchange listed the changes
-// fold_rebuild: k_al_scatter does a wanted rebuild itself (captured converged
-// supersteps: saves the rebuild launch, which is almost never wanted there)
-int launch_refresh(lpa_graph* g, const int32_t* Lc, const int32_t* Ln, bool diff_done, int par,
-                   hipEvent_t ev_scatter = nullptr, bool fold_rebuild = false) {
-  if (g->arcs == 0) return LPA_OK;
-  hipStream_t s = g->stream;
-  // this superstep's counters (zeroed by the previous k_al_scatter or at build)
-  unsigned long long* ctr = g->counters + 4 * par;
-  // one rank: its isolated slots (and the padding) never change; P > 1: the whole
-  // replicated vector (other ranks' slots change through the exchange)
-  const int64_t nd = !exchanges(g) ? g->bin_begin[BIN_ISO] : g->vpad;
-  // diff_done means, at P = 1, that the tally's per-stream diffs ran (count-only ones in
-  // a label-dense superstep); at P > 1, that the delta exchange queued every change
-  // already (nothing left to count or diff)
-  if (dense_refresh(g) && !(diff_done && exchanges(g))) {
-    // counted changed slots (in the tally, or here) -> rebuild, or the full diff
-    if (!diff_done) LPA_TRY(launch_diff(g, s, Lc, Ln, 0, nd, false, par, 0, 0, 1));
-    hipLaunchKernelGGL(k_dense_decide, dim3(1), dim3(64), 0, s, ctr, nd, g->gword);
-    LPA_HIP(hipGetLastError());
-    LPA_TRY(launch_diff(g, s, Lc, Ln, 0, nd, true, par, 0, 0, 2));
-  } else {
-    if (!diff_done) LPA_TRY(launch_diff(g, s, Lc, Ln, 0, nd, true, par));
-    // P > 1, superstep 2 after a giant-code refresh, its changes exchanged as a delta
-    // (the change chunks are queued): the rows it settled from codes have no al[] entries,
-    // so this refresh rebuilds whatever the change count (k_dense_decide's code clause)
-    if (code_tally_now(g)) {
-      hipLaunchKernelGGL(k_dense_decide, dim3(1), dim3(64), 0, s, ctr, INT64_MAX, g->gword);
-      LPA_HIP(hipGetLastError());
-    }
-  }
-  LPA_TRACE_POINT("diff");
-  // (a handle without the CSC position index rebuilds every time: counters[1] >= 0 > -1)
-  const int64_t thr = g->no_scatter ? -1 : (int64_t)(kRebuildFrac * (double)g->arcs);
-  FrontierMarks fm;
-  fm.crow = g->crow;
-  fm.rp = g->rp;
-  fm.uoff = g->hub_uoff;
-  fm.n_hub = g->n_hub;
-  fm.rdirty = g->rdirty[par ^ 1];
-  fm.udirty = g->udirty[par ^ 1];
-  if (code_tally3_now(g)) {
-    // superstep 3 after a giant-code refresh: its settled rows' al[] entries were never
-    // written, so this refresh rebuilds (k_dense_decide's code clause; n_slots: no count)
-    hipLaunchKernelGGL(k_dense_decide, dim3(1), dim3(64), 0, s, ctr, INT64_MAX, g->gword);
-    LPA_HIP(hipGetLastError());
-  }
-  // gather mode (lpa_build): no al[] to keep -- the scatter only marks the rows the next
-  // superstep re-tallies (and syncs the changed labels into Lc), no rebuild
-  const bool gnow = gather_now(g);
-  // superstep 3's refresh keeps the arc giant bits of superstep 2's bits-mode rebuild
-  // (k_al_scatter; superstep 4's row settle reads them)
-  const bool keep_bits = g->since_reset == 2 && g->abits != nullptr && g->gbits != nullptr && !gnow &&
-                         g->keep_bits;
-  if (g->al_pending && !gnow) {  // the column-run superstep after a lazy reset (al holds nothing)
-    hipLaunchKernelGGL(k_al_fill_unless_rebuild, dim3(cap_grid((g->arcs / 4 + 255) / 256, 8192)), dim3(256), 0, s,
-                       ctr, thr, (const v4i*)g->al0, (v4i*)g->al, g->arcs);
-    LPA_HIP(hipGetLastError());
-    g->al_pending = false;  // the rebuild below (or this fill + the scatter) makes al valid
-  }
-  hipLaunchKernelGGL(k_al_scatter, dim3(2048), dim3(256), 0, s, g->chlist, (const uint4*)g->chflag,
-                     (g->n_chunk_scan + 15) / 16, g->cowner, g->cch, ctr,
-                     g->counters + 4 * (par ^ 1), g->cptr,
-                     g->cpos, Ln, gnow ? (int32_t*)nullptr : g->al, thr, fm, g->fr_all + (par ^ 1),
-                     g->frontier, (int64_t)(kFrontierFrac * (double)g->arcs), const_cast<int32_t*>(Lc),
-                     (fold_rebuild && !gnow) ? g->col : (const int32_t*)nullptr, g->arcs, g->gword,
-                     keep_bits ? 1 : 0, g->gbits, g->abits);
-  LPA_HIP(hipGetLastError());
-  LPA_TRACE_POINT("scatter");
-  if (ev_scatter) LPA_HIP(hipEventRecord(ev_scatter, s));  // profiling: scatter | rebuild
-  if (gnow && g->since_reset == kGatherSteps - 1) {
-    // the last gather-mode superstep: al[] for the supersteps after it, one plain rebuild
-    const unsigned grid = cap_grid((g->arcs / 4 + 511) / 512, 8192);
-    hipLaunchKernelGGL(k_al_rebuild<false>, dim3(grid), dim3(256), 0, s, ctr, thr, g->col, g->arcs, Ln, g->al,
-                       g->gword);
-    LPA_HIP(hipGetLastError());
-  } else if (!fold_rebuild && !gnow) {
-    LPA_TRY(launch_rebuild(g, true, thr, Ln, ctr));
-  }
-  LPA_HIP(hipGetLastError());
-  return LPA_OK;
-}
-
 }  // namespace
-
-// the converged supersteps' bins as one k_bins_fused launch per stream (launch_tally)
-bool fused_now(const lpa_graph* g) {
-  return g->fused_bins && g->frontier && g->since_reset >= kDenseSupersteps + 2 && !gather_now(g);
-}
-
-// (the caller-driven delta exchange, lpa_exchange_put_delta: the refresh of the superstep
-// lpa_step just ran, which since_reset already counts -- it is seen as the in-library
-// refresh of that superstep sees it: dense / code-settled supersteps, code refresh allowed)
-int launch_refresh_ext(lpa_graph* g, const int32_t* Lc, const int32_t* Ln, bool diff_done, int par) {
-  const bool back = g->since_reset > 0;
-  if (back) --g->since_reset;
-  const int rc = launch_refresh(g, Lc, Ln, diff_done, par);
-  if (back) ++g->since_reset;
-  return rc;
-}
 
 // Capture `body` (launches on the handle's stream and the streams it forks) into an
 // executable graph.  Captures are serialised process-wide (several handles of one
@@ -4540,29 +2924,28 @@ int run_supersteps(lpa_graph* g, int32_t n, lpa_stats* st, bool last_refresh) {
     // before superstep 3 on a code-capable handle: did the refresh after superstep 2 take
     // the giant codes?  One host read (~20 us of idle GPU) instead of ~10 kernels that
     // return at once in the other case (C3: ~0.1 ms of superstep 3's 0.47)
-    if (g->code_ok && g->since_reset == 2) {
-      LPA_HIP(hipMemcpyAsync(g->h_flag, g->gword + 5, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (code3_read_now(g)) {
+      LPA_HIP(hipMemcpyAsync(g->h_flag, g->gword + GW_CODE, sizeof(int32_t), hipMemcpyDeviceToHost, s));
       LPA_HIP(hipStreamSynchronize(s));
       g->code3 = *g->h_flag != 0;
     }
     if (!first && !gather_now(g)) LPA_TRY(ensure_al(g));  // a lazy reset's al is needed by the hash tallies
     // the last gather-mode superstep's refresh rebuilds al (launched or in its graph)
-    const bool gather_switch = g->gather && g->since_reset == kGatherSteps - 1;
+    const bool gather_switch = g->gather && gather_last_step(g);
     const bool diff_in_tally = !exchanges(g) && !g->serial && !first;
     // converged supersteps on one GPU replay a captured HIP graph of the whole
     // superstep (tally on four streams + diff + refresh; ~25 kernels and the
     // fork/join events): one launch instead of ~40 queue operations.  The graph bakes
     // the label / counter buffers, so there is one per (cur, par) state.
-    // supersteps before `eager` are launched stream-ordered (their schedule differs
-    // from the converged one a captured graph bakes)
+    // supersteps before the converged ones are launched stream-ordered (their schedule
+    // differs from the converged one a captured graph bakes)
     // (supersteps 3 and 4 too: the row settle is launched only in superstep 3, and
     // superstep 4 reads the giant word of the labels it tallies)
-    const int eager = kDenseSupersteps + 2;
+    const bool conv = converged_now(g);
     // supersteps 2 and 3 (not 4: its settle chain on aux0 stops overlapping the hub
     // units inside a graph, 0.67 -> 0.75 ms at C3)
-    const bool early_graph = g->use_graphs && !exchanges(g) && !g->serial && !first && g->since_reset >= 1 &&
-                             g->since_reset <= 2;
-    if (g->use_graphs && !exchanges(g) && !g->serial && g->since_reset >= eager) {
+    const bool early_graph = g->use_graphs && !exchanges(g) && !g->serial && !first && early_graph_window(g);
+    if (g->use_graphs && !exchanges(g) && !g->serial && conv) {
       // (gather mode's converged supersteps have their own graphs: the plain ones and the
       // switch superstep, whose refresh rebuilds al)
       const int key = gather_now(g) ? 16 + (gather_switch ? 4 : 0) + g->cur * 2 + g->par
@@ -4582,7 +2965,7 @@ int run_supersteps(lpa_graph* g, int32_t n, lpa_stats* st, bool last_refresh) {
       ++g->since_reset;
       continue;
     }
-    if (g->use_graphs && exchanges(g) && !g->serial && g->since_reset >= eager) {
+    if (g->use_graphs && exchanges(g) && !g->serial && conv) {
       // P > 1: the tally (no collective inside) replays a captured graph per
       // (cur, par); the exchange, whose delta size the host reads, and the refresh
       // follow on the stream.  A loopback group (ranks = threads of one process) runs
@@ -4602,7 +2985,7 @@ int run_supersteps(lpa_graph* g, int32_t n, lpa_stats* st, bool last_refresh) {
       // launches become one graph launch (C2: supersteps 2-3 0.46 / 0.50 -> 0.41 / 0.45 ms)
       // (superstep 3 after a giant-code refresh has its own schedule: keys 12..15)
       const int key = code_tally3_now(g) ? 12 + g->cur * 2 + g->par
-                                         : 4 + ((g->since_reset - 1) * 2 + g->cur) * 2 + g->par;
+                                         : 4 + (early_graph_index(g) * 2 + g->cur) * 2 + g->par;
       if (!g->gexec[key])
         LPA_TRY(capture_graph(g, &g->gexec[key], [&]() -> int {
           int rc = launch_tally(g, Lown, nullptr, Lc, Ln, true);
@@ -4617,7 +3000,7 @@ int run_supersteps(lpa_graph* g, int32_t n, lpa_stats* st, bool last_refresh) {
     if (bev) LPA_HIP(hipEventRecord(bev[kTallyEv], s));
     bool changes_listed = false;
     if (exchanges(g) && has_collective(g))
-      LPA_TRY(exchange_collective(g, Lc, Ln, g->since_reset == 0, &changes_listed));
+      LPA_TRY(exchange_collective(g, Lc, Ln, at_l0(g), &changes_listed));
     if (bev) LPA_HIP(hipEventRecord(bev[kTallyEv + 1], s));
     // P > 1 without a communicator: the caller completes the superstep with
     // lpa_exchange_put (full vector + al[] rebuild) or lpa_exchange_put_delta
@@ -4628,21 +3011,21 @@ int run_supersteps(lpa_graph* g, int32_t n, lpa_stats* st, bool last_refresh) {
     if ((!exchanges(g) || has_collective(g)) && !early_graph && (last_refresh || t + 1 < n)) {
       LPA_TRY(launch_refresh(g, Lc, Ln, diff_in_tally || changes_listed, g->par,
                              bev ? bev[kTallyEv + 2] : nullptr,
-                             exchanges(g) && g->since_reset >= eager));
+                             exchanges(g) && conv));
       if (gather_switch) g->al_pending = false;
     }
     if (bev) LPA_HIP(hipEventRecord(bev[kTallyEv + 3], s));
     // after the last block-mode superstep the next one tallies every row and unit:
     // the block rows' units staged nothing while k_lpa_block tallied them (set at the
     // next superstep's start, after any caller-driven refresh has written fr_all)
-    if (block_mode_now(g) && g->since_reset + 1 == kDenseSupersteps) g->force_all_next = true;
+    if (last_block_mode_now(g)) g->force_all_next = true;
     // the column-run superstep staged no hub unit words: a frontier superstep after it
     // would merge every unit of a dirty hub row with stale (or never written) words of
     // its unlisted units, so the next superstep tallies every row and unit
     if (first) g->force_all_next = true;
     // a settled superstep 3 (k_settle_*) re-tallies no unit of a settled hub row: their
     // staged words are stale for a frontier superstep 4
-    if (g->since_reset == 2 && g->abits) g->force_all_next = true;
+    if (settle3_now(g)) g->force_all_next = true;
     if (tt) LPA_HIP(hipEventRecord(g->ev[2 * t + 1], s));
     g->cur ^= 1;
     g->par ^= 1;
@@ -4703,23 +3086,6 @@ int run_supersteps(lpa_graph* g, int32_t n, lpa_stats* st, bool last_refresh) {
 int frontier_all(lpa_graph* g, int par) {
   LPA_HIP(hipMemsetD32Async((hipDeviceptr_t)(g->fr_all + par), 1, 1, g->stream));
   return LPA_OK;
-}
-
-int rebuild_arc_labels(lpa_graph* g) {
-  if (g->arcs == 0) return LPA_OK;
-  return launch_rebuild(g, false, 0, g->lab[g->cur], g->counters);
-}
-
-int refresh_after_put(lpa_graph* g) {
-  if (g->arcs == 0) return LPA_OK;
-  if (g->since_reset == 0) return rebuild_arc_labels(g);   // no superstep ran since L0
-  // the refresh of the superstep lpa_step just ran (since_reset counted it already): an
-  // unconditional rebuild (thr = -1: every rebuild_wanted test passes), the giant codes
-  // allowed after superstep 1 or 2 as in the in-library schedule
-  --g->since_reset;
-  const int rc = launch_rebuild(g, true, -1, g->lab[g->cur], g->counters + 4 * (g->par ^ 1));
-  ++g->since_reset;
-  return rc;
 }
 
 int ensure_al(lpa_graph* g) {

@@ -1,0 +1,1356 @@
+// The refresh stage of a superstep (lpa_iter.hip describes the whole superstep): the
+// diff of the two label vectors, the al[] scatter with its frontier marks, the al[]
+// rebuilds (plain, small, LDS hot set, class-blocked pieces), the giant label's pick and
+// bits, the giant-code refresh, and their host schedule (launch_refresh and its callers'
+// forms).
+#include <algorithm>
+
+#include "lpa_codes.h"
+#include "lpa_device.h"
+#include "lpa_schedule.h"
+
+namespace lpa {
+
+using namespace dev;
+
+namespace {
+
+// ---------------------------------------------------------------------------
+// refresh of the replicated neighbour labels al[]
+// ---------------------------------------------------------------------------
+// Scatter chunks: column u's al[] positions cpos[cptr[u] ..) are cut into chunks of
+// kChunkPos, numbered statically at build time (chunks cch[u] .. cch[u+1] - 1,
+// cowner[chunk] = u).  A changed column flags its chunks in the bytemap chflag[]
+// (plain byte stores, no list to build); the scatter walks the bytemap.
+__device__ __forceinline__ void flag_chunks(uint8_t* __restrict__ chflag, const int64_t* __restrict__ cch,
+                                            int64_t u) {
+  int64_t c = cch[u];
+  const int64_t e = cch[u + 1];
+  for (; c < e && (c & 15); ++c) chflag[c] = 1;  // hub columns: thousands of chunks,
+  for (; c + 16 <= e; c += 16)                    // 16 flags per store
+    *reinterpret_cast<uint4*>(chflag + c) = make_uint4(0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u);
+  for (; c < e; ++c) chflag[c] = 1;
+}
+
+// changed vertices of the slot range [s0, s1): a column with one scatter chunk (the
+// vast majority) is appended to chlist[] (LDS queue, one atomic per block), a longer
+// one flags its chunks in chflag[]; the dirty arcs are counted (one atomic per wave);
+// with Lsync != nullptr the new label is also copied into Lc (the next superstep's
+// output vector: frontier, a row the next superstep skips already holds its label
+// there; inside the concurrent tally the scatter does it).  int4 quads (vpad is a
+// multiple of 64), kDiffQuads per block; lanes outside the range masked (the
+// neighbouring slots may belong to a bin another stream is still computing).
+//
+// Frontier superstep (lists != nullptr and *fr_all == 0): only the rows listed for
+// bins [b0, b1) were re-tallied (every other row provably kept its label, and its
+// output slot already holds it), so the diff walks those lists -- grid-stride over
+// their concatenation -- instead of the slot range.
+constexpr int kDiffQuads = 2048;
+// counters[1] value that makes the refresh rebuild al[] (k_dense_decide)
+constexpr unsigned long long kForcedRebuild = 1ull << 62;
+
+// Label-dense supersteps (P = 1): the per-stream diffs only counted the changed slots.
+// More than 1/10 of the slots changed: the refresh rebuilds al[] (counters[1] forced),
+// so no position chunk is ever emitted; otherwise the full diff (mode 2) runs next.
+// A superstep after a giant-code refresh (gword[GW_CODE]) always rebuilds: its al[] entries were
+// never written for the rows that superstep settled from codes.
+__global__ void k_dense_decide(unsigned long long* __restrict__ counters, int64_t n_slots,
+                               const int32_t* __restrict__ gword) {
+  if (threadIdx.x == 0 && ((int64_t)counters[2] * 10 > n_slots || gword[GW_CODE] != 0))
+    counters[1] = kForcedRebuild;
+}
+// fcnt[] slot set by the row settle of a giant superstep (k_settle_*): the bin kernels
+// walk lists of the unsettled rows, but the diff scans every slot (settled rows may
+// have changed label)
+__global__ __launch_bounds__(256) void k_diff(const int4* __restrict__ Lc4,
+                                              const int4* __restrict__ Ln4, int32_t* __restrict__ Lsync,
+                                              int64_t s0, int64_t s1,
+                                              const int64_t* __restrict__ cptr,
+                                              const int64_t* __restrict__ cch,
+                                              uint8_t* __restrict__ chflag,
+                                              int32_t* __restrict__ chlist,
+                                              unsigned long long* __restrict__ counters,
+                                              BinBounds bb, int b0, int b1,
+                                              const int32_t* __restrict__ flist,
+                                              const int32_t* __restrict__ fcnt,
+                                              const int32_t* __restrict__ fr_all, int mode) {
+  // mode 1 (label-dense supersteps): only count the changed slots (counters[2]); mode 2:
+  // the full diff unless k_dense_decide already chose the rebuild (counters[1] forced)
+  if (mode == 2 && counters[1] >= kForcedRebuild) return;
+  if (mode == 1) {
+    unsigned long long c = 0;
+    const int64_t q0 = s0 / 4 + (int64_t)blockIdx.x * kDiffQuads;
+    const int64_t q1 = min((s1 + 3) / 4, q0 + kDiffQuads);
+    for (int64_t q = q0 + threadIdx.x; q < q1; q += 256) {
+      const int4 a = Lc4[q], b = Ln4[q];
+      int chg = (a.x != b.x) | ((a.y != b.y) << 1) | ((a.z != b.z) << 2) | ((a.w != b.w) << 3);
+      if (q * 4 < s0 || q * 4 + 4 > s1) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (q * 4 + k < s0 || q * 4 + k >= s1) chg &= ~(1 << k);
+      }
+      c += (unsigned long long)__popc(chg);
+    }
+    // (the counts summed per block first: one atomic per block on the counter, not one
+    // per wave -- the same-address atomics of ~8 K waves queue at the counter's channel)
+    __shared__ unsigned long long csum;
+    if (threadIdx.x == 0) csum = 0ull;
+    __syncthreads();
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&csum, c);
+    __syncthreads();
+    if (threadIdx.x == 0 && csum) atomicAdd(&counters[2], csum);
+    return;
+  }
+  __shared__ int32_t q_col[kDiffQuads * 4];
+  __shared__ int qn;
+  __shared__ unsigned long long base_s, dsum;
+  const int lane = threadIdx.x & 63;
+  if (threadIdx.x == 0) {
+    qn = 0;
+    dsum = 0ull;
+  }
+  __syncthreads();
+  unsigned long long dirty = 0;
+  auto emit = [&](int64_t u, int32_t nb) {
+    if (Lsync) Lsync[u] = nb;
+    dirty += (unsigned long long)(cptr[u + 1] - cptr[u]);
+    const int64_t nch = cch[u + 1] - cch[u];
+    if (nch == 1) q_col[atomicAdd(&qn, 1)] = (int32_t)u;
+    else if (nch > 1) flag_chunks(chflag, cch, u);
+  };
+  if (flist != nullptr && *fr_all == 0 && fcnt[kFcntSettled] == 0) {
+    // a list holds at most its bin's rows, so the grid (sized for the slot range)
+    // gives each thread <= 32 entries, inside the block's queue
+    int64_t total = 0;
+    for (int b = b0; b < b1; ++b) total += fcnt[b];
+    const int32_t* Lc = reinterpret_cast<const int32_t*>(Lc4);
+    const int32_t* Ln = reinterpret_cast<const int32_t*>(Ln4);
+    for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < total; v += (int64_t)gridDim.x * 256) {
+      int64_t acc = 0;
+      int b = b0;
+      while (v >= acc + fcnt[b]) acc += fcnt[b++];
+      const int64_t u = flist[bb.b[b] + (v - acc)];
+      const int32_t nb = Ln[u];
+      if (Lc[u] != nb) emit(u, nb);
+    }
+  } else {
+    const int64_t q0 = s0 / 4 + (int64_t)blockIdx.x * kDiffQuads;
+    const int64_t q1 = min((s1 + 3) / 4, q0 + kDiffQuads);
+    for (int64_t q = q0 + threadIdx.x; q < q1; q += 256) {
+      const int4 a = Lc4[q], b = Ln4[q];
+      int chg = (a.x != b.x) | ((a.y != b.y) << 1) | ((a.z != b.z) << 2) | ((a.w != b.w) << 3);
+      if (q * 4 < s0 || q * 4 + 4 > s1) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (q * 4 + k < s0 || q * 4 + k >= s1) chg &= ~(1 << k);
+      }
+      if (chg) {
+        const int32_t nb[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if ((chg >> k) & 1) emit(q * 4 + k, nb[k]);
+      }
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) dirty += __shfl_xor(dirty, off, 64);
+  if (lane == 0 && dirty) atomicAdd(&dsum, dirty);
+  __syncthreads();
+  if (threadIdx.x == 0 && dsum) atomicAdd(&counters[1], dsum);
+  const int n = qn;
+  if (n == 0) return;  // uniform
+  if (threadIdx.x == 0) base_s = atomicAdd(&counters[0], (unsigned long long)n);
+  __syncthreads();
+  for (int i = threadIdx.x; i < n; i += 256) chlist[base_s + i] = q_col[i];
+}
+
+// few changes: al[cpos[p]] = L_next[u] for the positions of each changed u.
+// A chunk is (u << 32 | k): positions [cptr[u] + 256 k, ...).  A wave takes 64
+// chunks, one per lane (independent loads of cptr and the label): chunks of <= 16
+// positions are written by their own lane (4 stores in flight per step), longer
+// ones by the whole wave (coalesced cpos).
+// Frontier marks for the next superstep: the row holding arc position p (and, for a
+// hub row, the 512-arc unit holding it) must be re-tallied.
+struct FrontierMarks {
+  const int32_t* crow;       // [arcs] row of each position
+  const int64_t* rp;         // row offsets
+  const int64_t* uoff;       // hub rows: first unit
+  int64_t n_hub;
+  uint8_t* rdirty;           // next parity
+  uint8_t* udirty;           // next parity
+  __device__ __forceinline__ void mark(int64_t p) const {
+    const int32_t r = crow[p];
+    rdirty[r] = 1;
+    if (r < n_hub) udirty[uoff[r] + ((p - rp[r]) >> 9)] = 1;
+  }
+};
+static_assert(kSegArcs == 512, "unit of a position: (p - rp[row]) >> 9");
+
+// Wave-cooperative scatter of every lane's run: al[cpos[b + i]] = lab, i < n
+// (n <= kChunkPos).  The runs are cut into 16-position pieces dealt over the wave's
+// lanes (lane -> piece by a binary search over the inclusive piece prefix), so a
+// wave whose lanes hold runs of 17..256 positions writes them in parallel instead of
+// run after run with the whole wave.  Every lane of the wave must call it.
+// clr (this lane's run): also clear the arc giant bits of its positions (a column that
+// left G, superstep 3's scatter keeping the bits of the bits-mode rebuild: k_al_scatter)
+__device__ __forceinline__ void scatter_runs(int64_t b, int n, int32_t lab, bool clr, const uint32_t* __restrict__ cpos,
+                                             int32_t* __restrict__ al, bool all, const FrontierMarks& fm,
+                                             unsigned long long* __restrict__ abits, int lane) {
+  if (al == nullptr && all) return;  // gather mode without marks: nothing to write (uniform)
+  const int k = (n + 15) >> 4;
+  int incl = k;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int o = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += o;
+  }
+  const int S = __shfl(incl, 63, 64);
+  for (int r0 = 0; r0 < S; r0 += 64) {
+    const int t = r0 + lane;
+    int o = 0;  // the owner: first lane whose inclusive piece count exceeds t
+#pragma unroll
+    for (int st = 32; st >= 1; st >>= 1) {
+      const int ic = __shfl(incl, o + st - 1, 64);
+      if (ic <= t) o += st;
+    }
+    o = o < 64 ? o : 63;
+    const int excl = __shfl(incl, o, 64) - __shfl(k, o, 64);
+    const int64_t bo = __shfl(b, o, 64);
+    const int no = __shfl(n, o, 64);
+    const int32_t lv = __shfl(lab, o, 64);
+    const bool cl = __shfl((int)clr, o, 64) != 0;
+    if (t < S) {
+      const int p0 = (t - excl) * 16;
+      const int cnt = min(16, no - p0);
+      const uint32_t* src = cpos + bo + p0;
+      for (int q = 0; q < cnt; q += 4) {
+        uint32_t p[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) p[u] = q + u < cnt ? src[q + u] : 0u;
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          if (q + u < cnt) {
+            if (al) al[p[u]] = lv;   // gather mode: marks only
+            if (cl) atomicAnd(&abits[p[u] >> 6], ~(1ull << (p[u] & 63u)));
+            if (!all) fm.mark(p[u]);
+          }
+      }
+    }
+  }
+}
+
+// al[i] = L[col[i]] over the whole arc array by the calling grid (grid-stride): each
+// thread keeps 8 gathers in flight (two int4 column quads), col / al streamed
+// non-temporally
+__device__ __forceinline__ void rebuild_all(const int32_t* __restrict__ col, int64_t arcs,
+                                            const int32_t* __restrict__ Ln, int32_t* __restrict__ al) {
+  const int64_t n4 = arcs >> 2;
+  const v4i* __restrict__ c4 = reinterpret_cast<const v4i*>(col);
+  v4i* __restrict__ a4 = reinterpret_cast<v4i*>(al);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; q + stride < n4; q += 2 * stride) {
+    const v4i c0 = __builtin_nontemporal_load(c4 + q);
+    const v4i c1 = __builtin_nontemporal_load(c4 + q + stride);
+    v4i r0, r1;
+    r0.x = Ln[c0.x]; r0.y = Ln[c0.y]; r0.z = Ln[c0.z]; r0.w = Ln[c0.w];
+    r1.x = Ln[c1.x]; r1.y = Ln[c1.y]; r1.z = Ln[c1.z]; r1.w = Ln[c1.w];
+    __builtin_nontemporal_store(r0, a4 + q);
+    __builtin_nontemporal_store(r1, a4 + q + stride);
+  }
+  if (q < n4) {
+    const v4i c0 = __builtin_nontemporal_load(c4 + q);
+    v4i r0;
+    r0.x = Ln[c0.x]; r0.y = Ln[c0.y]; r0.z = Ln[c0.z]; r0.w = Ln[c0.w];
+    __builtin_nontemporal_store(r0, a4 + q);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (arcs & 3)) {
+    const int64_t i = (n4 << 2) + threadIdx.x;
+    al[i] = Ln[col[i]];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_al_scatter(const int32_t* __restrict__ chlist,
+                                                    const uint4* __restrict__ chflag16, int64_t ngroups,
+                                                    const int32_t* __restrict__ cowner,
+                                                    const int64_t* __restrict__ cch,
+                                                    const unsigned long long* __restrict__ counters,
+                                                    unsigned long long* __restrict__ counters_next,
+                                                    const int64_t* __restrict__ cptr,
+                                                    const uint32_t* __restrict__ cpos,
+                                                    const int32_t* __restrict__ Ln,
+                                                    int32_t* __restrict__ al, int64_t thr,
+                                                    FrontierMarks fm, int32_t* __restrict__ fr_all_next,
+                                                    int frontier, int64_t fr_thr,
+                                                    int32_t* __restrict__ Lold,
+                                                    const int32_t* __restrict__ col_fold, int64_t arcs,
+                                                    int32_t* __restrict__ gword, int keep_bits,
+                                                    const uint32_t* __restrict__ gbits,
+                                                    unsigned long long* __restrict__ abits) {
+  // the next superstep's counters (the other parity; no memset launch)
+  if (blockIdx.x == 0 && threadIdx.x < 3) counters_next[threadIdx.x] = 0ull;
+  const bool rebuild = rebuild_wanted(counters, thr);
+  // al changes here (scatter, or the plain folded rebuild), so the arc giant bits go
+  // stale: gword[GW_ABITS_OK] = 0 -- except in superstep 3's scatter (keep_bits, host-set), right
+  // after the bits-mode rebuild whose bits they are: a column that LEFT G (its gbits
+  // bit, the rebuild's bitmap of the same vector and G) clears its positions' bits, one
+  // atomic each (rare: R-MAT superstep 3 moves labels onto G); a column that joined G
+  // leaves its bits clear.  The bits then hold a lower bound of every row's G votes, all
+  // superstep 4's settle needs, and its k_abits_pass is skipped (round 6; exact upkeep
+  // with an atomic per written position cost superstep 3 0.25 ms, round 3).  A wanted,
+  // non-folded rebuild follows this kernel and sets gword[GW_ABITS_OK] itself.
+  const bool keep = keep_bits != 0 && !rebuild;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && (!rebuild || col_fold) && !keep) gword[GW_ABITS_OK] = 0;
+  const int32_t Gk = gword[GW_G];
+  auto left_g = [&](int64_t u, int32_t lab) -> bool {
+    return keep && lab != Gk && ((gbits[u >> 5] >> (u & 31)) & 1u);
+  };
+  // The next superstep tallies every row after a rebuild, with the frontier off, or
+  // when more than fr_thr arcs changed: then nearly every row has a changed neighbour
+  // anyway (R-MAT superstep 3 -> 4: 1.5 % of arcs dirty, 88 % of the arcs in dirty
+  // rows) and the per-position marks would cost more than they save.
+  const bool all = rebuild || !frontier || (int64_t)counters[1] > fr_thr;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *fr_all_next = all ? 1 : 0;
+  const int lane = threadIdx.x & 63;
+  const int64_t wid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  // col_fold (captured converged supersteps): a wanted rebuild is done here, the plain
+  // form, instead of by a k_al_rebuild_hot launch that nearly always returns at once
+  // (one dependent launch fewer per converged superstep)
+  if (rebuild && col_fold) rebuild_all(col_fold, arcs, Ln, al);
+  // one-chunk columns from the list: a lane each, longer rows of positions by the wave
+  if (!rebuild) {
+    const int64_t nl = (int64_t)counters[0];
+    for (int64_t c0 = wid * 64; c0 < nl; c0 += nw * 64) {
+      const int64_t c = c0 + lane;
+      int64_t b = 0;
+      int n = 0;
+      int32_t lab = 0;
+      bool clr = false;
+      if (c < nl) {
+        const int64_t u = chlist[c];
+        b = cptr[u];
+        n = (int)(cptr[u + 1] - b);  // <= kChunkPos
+        lab = Ln[u];
+        Lold[u] = lab;  // frontier sync (after the join)
+        clr = left_g(u, lab);
+      }
+      scatter_runs(b, n, lab, clr, cpos, al, all, fm, abits, lane);
+    }
+  }
+  uint4* __restrict__ flw = const_cast<uint4*>(chflag16);
+  // multi-chunk columns: a wave takes 64 groups of 16 chunk flags, one group per lane,
+  // and clears them.  Lane l of wave w takes group g0 + l * nw + w: the consecutive
+  // chunks of one changed hub column land in different waves (wave-consecutive
+  // groups would hand a column's hundreds of chunks to one wave, one after another)
+  for (int64_t g0 = 0; g0 < ngroups; g0 += nw * 64) {
+    const int64_t gi = g0 + (int64_t)lane * nw + wid;
+    uint4 f = make_uint4(0u, 0u, 0u, 0u);
+    if (gi < ngroups) f = chflag16[gi];
+    const bool any = (f.x | f.y | f.z | f.w) != 0u;
+    if (any) flw[gi] = make_uint4(0u, 0u, 0u, 0u);
+    if (rebuild || __ballot(any) == 0ull) continue;  // the rebuild re-gathers every arc
+    u32 bits = 0u;
+    const u32 fw[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if ((fw[k >> 2] >> (8 * (k & 3))) & 0xFFu) bits |= 1u << k;
+    // every lane pops its next flagged chunk per round: chunks of <= 16 positions are
+    // written by their own lane, longer ones by the whole wave (coalesced cpos)
+    while (__ballot(bits != 0u)) {
+      int64_t b = 0;
+      int n = 0;
+      int32_t lab = 0;
+      bool clr = false;
+      if (bits) {
+        const int t = __ffs(bits) - 1;
+        bits &= bits - 1u;
+        const int64_t cid = gi * 16 + t;
+        const int64_t u = cowner[cid];
+        const int64_t kk = cid - cch[u];
+        b = cptr[u] + kk * kChunkPos;
+        n = (int)min((int64_t)kChunkPos, cptr[u + 1] - b);
+        lab = Ln[u];
+        // frontier sync of a changed label into the next superstep's output vector
+        // (after the join; every changed vertex with local arcs has a chunk 0)
+        if (kk == 0) Lold[u] = lab;
+        clr = left_g(u, lab);
+      }
+      scatter_runs(b, n, lab, clr, cpos, al, all, fm, abits, lane);
+    }
+  }
+}
+
+// After a lazy reset (al0) the first refresh that only scatters needs the L0 arc
+// labels in al first: copied here unless the rebuild that follows rewrites every arc.
+__global__ __launch_bounds__(256) void k_al_fill_unless_rebuild(const unsigned long long* __restrict__ counters,
+                                                                int64_t thr, const v4i* __restrict__ src,
+                                                                v4i* __restrict__ dst, int64_t arcs) {
+  if (rebuild_wanted(counters, thr)) return;
+  const int64_t n4 = arcs >> 2;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x)
+    __builtin_nontemporal_store(__builtin_nontemporal_load(src + q), dst + q);
+  if (blockIdx.x == 0 && threadIdx.x < (arcs & 3)) {
+    const int64_t i = (n4 << 2) + threadIdx.x;
+    reinterpret_cast<int32_t*>(dst)[i] = reinterpret_cast<const int32_t*>(src)[i];
+  }
+}
+
+// many changes: al[i] = L_next[col[i]].  Random label gathers: each thread
+// keeps 8 gathers in flight (two int4 column quads), streams col/al non-temporally.
+template <bool kIfWanted>
+__global__ __launch_bounds__(256) void k_al_rebuild(const unsigned long long* __restrict__ counters,
+                                                    int64_t thr, const int32_t* __restrict__ col,
+                                                    int64_t arcs,
+                                                    const int32_t* __restrict__ Ln,
+                                                    int32_t* __restrict__ al, int32_t* __restrict__ gword) {
+  if (kIfWanted && !rebuild_wanted(counters, thr)) return;
+  if (blockIdx.x == 0 && threadIdx.x == 0) gword[GW_ABITS_OK] = 0;  // no arc giant bits from this form
+  rebuild_all(col, arcs, Ln, al);
+}
+
+// Giant-label bitmap of L (before a rebuild): bit u = (L[u] == G), G = L[0], the label
+// of the highest-degree vertex.  Once the labels concentrate (R-MAT, after superstep
+// 2: ~98.5 % of the arcs point at a column labelled G) the rebuild gathers one BIT per
+// arc -- the hot slots' bits from LDS, the rest from this 1-bit-per-slot array, which
+// stays in L2 (2 MB at C3 against the 64 MB label vector) -- and reads the label
+// vector only for the columns whose bit is clear.  One ballot per 64 slots; lanes
+// 0..7 store the wave's eight 64-bit words (64 contiguous bytes).
+// The giant-label candidate of a label vector: the most frequent label among the
+// kPickK highest-degree vertices (degree ranks k < kPickK; at P > 1 rank k lives at slot
+// (k mod P) S + k / P), and whether it holds >= 1/5 of them (gword[GW_TRY]: the tallies'
+// giant step is worth trying).  On R-MAT and Chung-Lu (oracle, scale 21-22) that label
+// is the degree-weighted mode of the whole vector in every superstep -- the top hub's
+// own label is not (Chung-Lu superstep 2: the mode holds 43 % of the arcs' columns, the
+// top hub's label 0.3 %).  One block, a 2K-slot LDS table.  The choice of G only
+// affects speed: every use of it is exact for any G.
+constexpr int kHotLabels = kHotRankedLabels;  // rank-strided label set (P > 1: power-of-two shares)
+constexpr int kHotLabelsSingle = 40960;    // P = 1: the whole 160 KB of LDS
+// bits mode: 1,310,688 slots' bits (the last LDS word counts the set bits first)
+constexpr int64_t kHotBits = 32ll * (kHotLabelsSingle - 1);
+constexpr int kPickK = 1024;
+__global__ __launch_bounds__(1024) void k_giant_pick(const int32_t* __restrict__ L, int64_t n_real, int64_t S,
+                                                     int P, int32_t* __restrict__ gword) {
+  __shared__ u64 tab[2 * kPickK];
+  __shared__ u64 wbest[kPickK / 64];
+  const int t = threadIdx.x;
+  tab[t] = 0ull;
+  tab[t + kPickK] = 0ull;
+  __syncthreads();
+  const int64_t n = n_real < kPickK ? n_real : kPickK;
+  if (t < n) lds_insert(tab, 32 - 11, 2 * kPickK - 1, (u32)L[(int64_t)(t % P) * S + t / P], 1u);
+  __syncthreads();
+  const u64 b = wave_max_u64(umax64(tab[t], tab[t + kPickK]));
+  if ((t & 63) == 0) wbest[t >> 6] = b;
+  __syncthreads();
+  if (t == 0) {
+    u64 m = 0ull;
+#pragma unroll
+    for (int k = 0; k < kPickK / 64; ++k) m = umax64(m, wbest[k]);
+    const int32_t G = (int32_t)(~(u32)m);
+    if (G != gword[GW_G]) gword[GW_ABITS_OK] = 0;  // the arc giant bits are relative to the old G
+    gword[GW_G] = G;
+    gword[GW_HOT_BITS] = 0;  // k_giant_bits counts the set bits of the hot slots here
+    gword[GW_CODE] = 0;  // no giant-code refresh unless k_code_mode takes it below
+    gword[GW_ABITS_PASS] = 0;  // no k_abits_pass since this refresh
+    gword[GW_PURE_CNT] = 0;  // superstep 4's impure-unit list (k_units_pure)
+    gword[GW_TRY] = n > 0 && 5 * (int64_t)(m >> 32) >= n ? 1 : 0;
+  }
+}
+
+// (abits / nzero: the class-blocked rebuild that follows ORs the arc giant bits of its
+// pieces into abits[0, nzero): zeroed here, one launch ahead)
+// gword[GW_HOT_BITS] counts the set bits of the hot slots, slot i with (i & hmask) < hlim: the first
+// kHotBits slots at P = 1 (hmask all ones), the first hlim slots of every slice of a
+// rank-strided vector (hmask = slice - 1) -- the degree-ranked top set either way
+template <bool kIfWanted>
+__global__ __launch_bounds__(256) void k_giant_bits(const unsigned long long* __restrict__ counters, int64_t thr,
+                                                    const int32_t* __restrict__ L, int64_t n,
+                                                    int32_t* __restrict__ gword,
+                                                    unsigned long long* __restrict__ bits,
+                                                    unsigned long long* __restrict__ abits, int64_t nzero,
+                                                    uint64_t hmask, int64_t hlim) {
+  if (kIfWanted && !rebuild_wanted(counters, thr)) return;
+  // the hot-bit count: summed per block in LDS, one global atomic per block (a returning
+  // atomic per wave on the one word serialised: ~2,500 of them, ~30 us at C3)
+  __shared__ u32 bcnt;
+  if (threadIdx.x == 0) bcnt = 0u;
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nzero; i += (int64_t)gridDim.x * blockDim.x)
+    abits[i] = 0ull;
+  const int32_t G = gword[GW_G];
+  const int lane = threadIdx.x & 63;
+  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t g0 = (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 512; g0 < n; g0 += nw * 512) {
+    int32_t v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int64_t i = g0 + k * 64 + lane;
+      v[k] = i < n ? (int32_t)ld_stream(L + i) : ~G;
+    }
+    unsigned long long mine = 0ull;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const unsigned long long m = __ballot(v[k] == G);
+      if (lane == k) mine = m;
+    }
+    if (lane < 8 && g0 + lane * 64 < n) bits[(g0 >> 6) + lane] = mine;
+    // the hot slots' set bits (the rebuild's bits-mode test without an LDS fill); hlim
+    // and the slice are multiples of 64, so a bit word is hot or cold as a whole
+    const int64_t wi = g0 + lane * 64;
+    const bool hot = lane < 8 && wi < n && (int64_t)((uint64_t)wi & hmask) < hlim;
+    if (__ballot(hot)) {
+      const u32 c = wave_sum_u32(hot ? (u32)__popcll(mine) : 0u);
+      if (lane == 0 && c) atomicAdd(&bcnt, c);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && bcnt) atomicAdd(&gword[GW_HOT_BITS], (int32_t)bcnt);
+}
+
+// al[i] = lab(col[i]) over every arc by the calling grid (one wave per 512-arc batch,
+// grid-stride); bits: also the arc giant bits (abits: bit i = al[i] == G, one ballot
+// per 64 arcs), which the next superstep's full tally settles rows from (k_settle_*).
+template <typename Lab>
+__device__ __forceinline__ void rebuild_stream(Lab lab, int32_t G, bool bits, const int32_t* __restrict__ col,
+                                               int64_t arcs, int32_t* __restrict__ al,
+                                               unsigned long long* __restrict__ abits) {
+  // lane-consecutive arcs: one gather instruction covers 64 consecutive arcs of
+  // a row, whose sorted columns often share lines (hub rows) -> fewer L2 requests.
+  // Full 512-arc batches are software-pipelined: the next batch's column loads are in
+  // flight while this batch's labels are looked up and stored.
+  const int lane = threadIdx.x & 63;
+  const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
+  const int64_t step = nw * 512;
+  const int64_t nfull = arcs & ~(int64_t)511;  // arcs of the full batches
+  int64_t base = ((int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 512;
+  int32_t c[8];
+  if (base < nfull) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) c[k] = __builtin_nontemporal_load(col + base + k * 64 + lane);
+  }
+  for (; base < nfull; base += step) {
+    int32_t cn[8], r[8];
+    const int64_t nb = base + step;
+    if (nb < nfull) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) cn[k] = __builtin_nontemporal_load(col + nb + k * 64 + lane);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[k] = lab(c[k]);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) __builtin_nontemporal_store(r[k], al + base + k * 64 + lane);
+    if (bits) {
+      unsigned long long mine = 0ull;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const unsigned long long m = __ballot(r[k] == G);
+        if (lane == k) mine = m;
+      }
+      if (lane < 8) abits[(base >> 6) + lane] = mine;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) c[k] = cn[k];
+  }
+  // the partial last batch (one wave)
+  if (nfull < arcs && base == nfull) {
+    for (int k = 0; k < 8; ++k) {
+      const int64_t i = base + k * 64 + lane;
+      const bool v = i < arcs;
+      const int32_t x = v ? lab(col[i]) : 0;
+      if (v) al[i] = x;
+      const unsigned long long m = __ballot(v && x == G);
+      if (bits && lane == 0 && base + k * 64 < arcs) abits[(base >> 6) + k] = m;
+    }
+  }
+}
+
+// The same stream in a three-stage software pipeline over 512-arc batches (P = 1 hot
+// kernel): at step t the column loads of batch t + 3 are issued, batch t + 2's probe
+// words fetched (p1: an LDS word, or an L2 word of gbits for a cold column), batch
+// t + 1's labels resolved (p2: from the word, else a gather of L[c]) and batch t stored,
+// so each wave keeps three batches' dependent loads in flight instead of one batch's
+// chain (col -> bit word -> label).  Rings of 3 column sets and 2 word / label sets,
+// six steps unrolled so no set is copied while its loads are in flight.
+// The main loop is branch-free (every stage's batch exists, and p1 / p2 issue their
+// loads unconditionally, at a clamped address where the value is not needed): the
+// vector-memory counter is then tracked exactly, and waiting for batch t's labels does
+// not wait for the loads of batches t + 1 .. t + 3 -- with a conditional load in the
+// loop the compiler waited for every outstanding load (vmcnt(0)) at each step, which
+// serialised the pipeline.  The last few batches run guarded.
+//   fetch(t, c)  batch t's columns        probe(c, w)   p1 words
+//   resolve(c, w, r)  p2 labels          store(t, r)    stores (+ arc giant bits)
+template <typename Pre, typename F, typename Q, typename R, typename St>
+__device__ __forceinline__ void pipe3(int64_t nb, Pre pre, F fetch, Q probe, R resolve, St store) {
+  int32_t c0[8], c1[8], c2[8], r0[8], r1[8];
+  u32 w0[8], w1[8];
+  int64_t t = 0;
+  if (nb <= 0) return;
+  // pre(t, slot): batch t's descriptors (six slots, batch t in slot t mod 6), four
+  // steps ahead of its fetch
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (k < nb) pre(k, k);
+  fetch(0, c0, 0);
+  if (nb > 1) fetch(1, c1, 1);
+  if (nb > 2) fetch(2, c2, 2);
+  probe(c0, w0);
+  if (nb > 1) probe(c1, w1);
+  resolve(c0, w0, r0);
+#define LPA_PIPE_STEP(GUARD, I, CA, CB, CC, WA, WB, RA, RB) \
+  if (!GUARD || t + 4 < nb) pre(t + 4, (I + 4) % 6);      \
+  if (!GUARD || t + 3 < nb) fetch(t + 3, CA, (I + 3) % 6); \
+  if (!GUARD || t + 2 < nb) probe(CC, WA);                 \
+  if (!GUARD || t + 1 < nb) resolve(CB, WB, RB);           \
+  store(t, RA, I);                                         \
+  ++t;                                                     \
+  if (GUARD && t >= nb) break;
+#define LPA_PIPE_CYCLE(GUARD)                                 \
+  LPA_PIPE_STEP(GUARD, 0, c0, c1, c2, w0, w1, r0, r1)        \
+  LPA_PIPE_STEP(GUARD, 1, c1, c2, c0, w1, w0, r1, r0)        \
+  LPA_PIPE_STEP(GUARD, 2, c2, c0, c1, w0, w1, r0, r1)        \
+  LPA_PIPE_STEP(GUARD, 3, c0, c1, c2, w1, w0, r1, r0)        \
+  LPA_PIPE_STEP(GUARD, 4, c1, c2, c0, w0, w1, r0, r1)        \
+  LPA_PIPE_STEP(GUARD, 5, c2, c0, c1, w1, w0, r1, r0)
+  // unguarded cycles: their last step (t + 5) issues pre(t + 9), so t + 9 < nb keeps
+  // every descriptor read inside the list (a piece list has no padding past its end)
+  while (t + 10 <= nb) {
+    LPA_PIPE_CYCLE(false)
+  }
+  while (true) {
+    LPA_PIPE_CYCLE(true)
+  }
+#undef LPA_PIPE_CYCLE
+#undef LPA_PIPE_STEP
+}
+
+// arc giant bits of one 64-lane chunk at arc position st (len lanes live, lanes
+// consecutive): one word, or two when st is not word-aligned (ORed: other chunks share
+// the words; nzero-ed by k_giant_bits beforehand)
+__device__ __forceinline__ void or_arc_bits(unsigned long long* __restrict__ abits, u32 st, unsigned long long m,
+                                            int lane) {
+  const u32 wd = st >> 6, off = st & 63u;
+  if (m && lane == 0) atomicOr(&abits[wd], m << off);
+  if (m && lane == 1 && off && (m >> (64u - off))) atomicOr(&abits[wd + 1], m >> (64u - off));
+}
+
+// the plain stream: this wave's whole 512-arc batches of [0, arcs), then the partial
+// last batch (one wave)
+template <typename P1, typename P2>
+__device__ __forceinline__ void rebuild_pipe(P1 p1, P2 p2, int32_t G, bool bits, const int32_t* __restrict__ col,
+                                             int64_t arcs, int32_t* __restrict__ al,
+                                             unsigned long long* __restrict__ abits) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
+  const int64_t wv = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t nbatch = arcs >> 9;
+  const int64_t nb = wv < nbatch ? (nbatch - wv + nw - 1) / nw : 0;
+  auto base = [&](int64_t t) { return (wv + t * nw) * 512; };
+  auto pre = [](int64_t, int) {};
+  auto fetch = [&](int64_t t, int32_t (&c)[8], int) {
+    const int64_t b = base(t);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) c[k] = __builtin_nontemporal_load(col + b + k * 64 + lane);
+  };
+  auto probe = [&](const int32_t (&c)[8], u32 (&w)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) w[k] = p1(c[k]);
+  };
+  auto resolve = [&](const int32_t (&c)[8], const u32 (&w)[8], int32_t (&r)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[k] = p2(c[k], w[k]);
+  };
+  auto store = [&](int64_t t, const int32_t (&r)[8], int) {
+    const int64_t b = base(t);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) __builtin_nontemporal_store(r[k], al + b + k * 64 + lane);
+    if (bits) {
+      unsigned long long mine = 0ull;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const unsigned long long m = __ballot(r[k] == G);
+        if (lane == k) mine = m;
+      }
+      if (lane < 8) abits[(b >> 6) + lane] = mine;
+    }
+  };
+  pipe3(nb, pre, fetch, probe, resolve, store);
+  // the partial last batch (one wave)
+  const int64_t nfull = nbatch << 9;
+  if (nfull < arcs && wv == nbatch % nw) {
+    for (int k = 0; k < 8; ++k) {
+      const int64_t i = nfull + k * 64 + lane;
+      const bool v = i < arcs;
+      const int32_t c = v ? col[i] : 0;
+      const int32_t x = p2(c, p1(c));
+      if (v) al[i] = x;
+      const unsigned long long m = __ballot(v && x == G);
+      if (bits && lane == 0 && nfull + k * 64 < arcs) abits[(nfull >> 6) + k] = m;
+    }
+  }
+}
+
+// The class-blocked part of a labels-mode rebuild (P = 1).  A labels-mode rebuild is
+// bound by its L2-missing gathers (C3 superstep 1: 3.6x the algorithmic bytes); a block
+// group (blocks b = x mod 8, one XCD under the observed round-robin placement, speed
+// only) streams the pieces of column class x -- the class segments of the rows of degree
+// > block_deg, which keep their columns in (class, column) order -- so an XCD's gathers
+// touch 1/8 of the label lines and its L2 holds far more of them (C3, simulated: 0.18
+// -> 0.02 missing gathers per arc).  8 pieces (<= 64 arcs, lane-consecutive) per batch
+// and wave, in pipe3's pipeline; a lane past its piece carries column 0 (a hot-set LDS
+// read) and stores nothing; the descriptors ride a register ring four batches ahead
+// (scalar loads in the stage that used them cost a round trip per step: the pieces
+// phase ran at ~7 us per batch and wave).  bits: the arc giant bits, ORed.
+#ifdef LPA_BLKTIME
+// diagnostic build only (csrc/Makefile blktime): per block of the last blocked rebuild,
+// the wall clock at its start, after its pieces and at its end
+__device__ unsigned long long g_blk_time[3 * 512];
+extern "C" int lpa_diag_blk_times(unsigned long long* out) {
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_blk_time), sizeof(g_blk_time)) != hipSuccess) return -1;
+  static unsigned long long zero[3 * 512];
+  return hipMemcpyToSymbol(HIP_SYMBOL(g_blk_time), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
+}
+#endif
+struct BlkInfo {
+  int64_t off[kMaxBlkClasses + 1];  // class x: pieces [off[x], off[x + 1]), multiples of 8
+  int64_t a0;                       // listed arcs [0, a0) (0: no blocked part)
+  int phases;                       // classes / 8: group x streams x, x + 8, ...
+};
+template <typename P1, typename P2>
+__device__ __forceinline__ void rebuild_pieces(P1 p1, P2 p2, int32_t G, bool bits, const u64* __restrict__ pieces,
+                                               int64_t q0, int64_t q1, int64_t wi, int64_t nwv,
+                                               const int32_t* __restrict__ col, int32_t* __restrict__ al,
+                                               unsigned long long* __restrict__ abits) {
+  const int lane = threadIdx.x & 63;
+  auto uni = [](int64_t v) -> int64_t {
+    return (int64_t)(((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)((u64)v >> 32)) << 32) |
+                     (u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)v));
+  };
+  const int64_t step = uni(nwv * 8), first = uni(q0 + wi * 8), last = uni(q1);
+  const int64_t nb = first < last ? (last - first + step - 1) / step : 0;
+  // descriptor ring: lane k < 8 of slot j holds piece k of the batch in slot j, loaded
+  // four steps ahead (a vector load, so waiting for it never waits on newer loads);
+  // the stages read it with readlane
+  u64 dr[6];
+  auto pre = [&](int64_t t, int j) {
+    const int64_t qq = first + t * step;
+    dr[j] = lane < 8 ? pieces[qq + lane] : 0ull;
+  };
+  auto desc = [&](int j, int k) -> u64 {
+    return ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(dr[j] >> 32), k) << 32) |
+           (u64)(u32)__builtin_amdgcn_readlane((int)(u32)dr[j], k);
+  };
+  auto fetch = [&](int64_t, int32_t (&c)[8], int j) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const u64 d = desc(j, k);
+      const bool live = lane < (int)(d >> 32);
+      const int32_t x = __builtin_nontemporal_load(col + (u32)d + (live ? lane : 0));
+      c[k] = live ? x : 0;
+    }
+  };
+  // the probe word is read where it is used (an LDS read in the labels / hybrid modes
+  // this path serves): no word ring, 16 VGPRs fewer
+  auto probe = [&](const int32_t (&)[8], u32 (&)[8]) {};
+  auto resolve = [&](const int32_t (&c)[8], const u32 (&)[8], int32_t (&r)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[k] = p2(c[k], p1(c[k]));
+  };
+  auto store = [&](int64_t, const int32_t (&r)[8], int j) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const u64 d = desc(j, k);
+      const int ln = (int)(d >> 32);
+      if (lane < ln) __builtin_nontemporal_store(r[k], al + (u32)d + lane);
+      if (bits) or_arc_bits(abits, (u32)d, __ballot(lane < ln && r[k] == G), lane);
+    }
+  };
+  pipe3(nb, pre, fetch, probe, resolve, store);
+}
+
+// al[] rebuild with an LDS hot set (the slots of the highest-degree vertices: at P = 1
+// the first slots, 30-40 % of all arc targets on R-MAT).  The rebuild is bound by the
+// line traffic of its L2-missing 4-B gathers, and every gather served from LDS is one
+// L2 request fewer.  One 1024-thread block per CU, 160 KB of LDS, in one of two modes
+// that every block picks alike from the same data:
+//   bits    (most hot slots carry the giant label G): LDS holds the giant-label bits of
+//           the first 1.31 M slots, the other columns' bits come from gbits (L2); a
+//           set bit is G, a clear one reads L[c].
+//   labels  LDS holds the labels of the first 40,960 slots; the rest read L[c].
+// kRanked (P > 1, power-of-two slices and rank count): the hottest vertices of rank
+// r's slice are its first slots (degree rank k lives at slot (k mod P) S + k / P),
+// so the global top set is the first H slots of every slice: slot c is hot iff
+// (c mod S) < H, at LDS index (c / S) H + c mod S (H = 2^hot_lg labels or 2^hb_lg bits).
+// kPieces (P = 1, a class-blocked handle: its labels-mode rebuild goes through the pieces):
+// its own instantiation, so that the plain one's registers are allocated without the
+// pieces' descriptor ring (one form for both spilled 16 VGPRs to scratch at the 128 of
+// four waves per SIMD)
+template <bool kIfWanted, bool kRanked, bool kPieces = false>
+__global__ __launch_bounds__(1024) void k_al_rebuild_hot(const unsigned long long* __restrict__ counters,
+                                                         int64_t thr, const int32_t* __restrict__ col,
+                                                         int64_t arcs, const int32_t* __restrict__ Ln,
+                                                         int32_t nhot, int32_t* __restrict__ al,
+                                                         int slice_lg, int hot_lg, int hb_lg,
+                                                         const uint32_t* __restrict__ gbits, int64_t nbits,
+                                                         int32_t* __restrict__ gword,
+                                                         unsigned long long* __restrict__ abits,
+                                                         const u64* __restrict__ pieces, BlkInfo blk,
+                                                         const int32_t* __restrict__ skip) {
+  if (kIfWanted && !rebuild_wanted(counters, thr)) return;
+  if (skip && *skip) return;  // the giant-code refresh replaces this rebuild (k_code_mode)
+  __shared__ u32 hot[kHotLabelsSingle];
+  u32* s_cnt = &hot[kHotLabelsSingle - 1];   // beyond the bit words; labels mode refills it
+  // ---- the giant-label bits of the hot slots, and how many are set ----
+  const int64_t nhb = kRanked ? ((int64_t)(nbits >> slice_lg) << hb_lg) : (nbits < kHotBits ? nbits : kHotBits);
+  const int nhw = (int)((nhb + 31) >> 5);
+  if (threadIdx.x == 0) *s_cnt = 0u;
+  __syncthreads();
+  int cnt = 0;
+  for (int q = threadIdx.x; q < nhw; q += 1024) {
+    int64_t gw = q;
+    if constexpr (kRanked) gw = ((int64_t)(q >> (hb_lg - 5)) << (slice_lg - 5)) + (q & ((1 << (hb_lg - 5)) - 1));
+    const u32 w = gbits[gw];
+    hot[q] = w;
+    cnt += __popc(w);
+  }
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+  if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(s_cnt, (u32)cnt);
+  __syncthreads();
+  const bool bits = 2 * (int64_t)*s_cnt >= nhb && nhb > 0;  // uniform: the same data in every block
+  // hybrid (P = 1): G on >= 1/8 of the bit-range slots but not on half -- labels-mode
+  // gathers that also write the arc giant bits (the next superstep's settle).  (Taking a
+  // cold column's G from its gbits bit instead of its label measured slower: C5 186.7 ->
+  // 176.4 GTEPS.)
+  const bool hyb = !kRanked && !bits && 8 * (int64_t)*s_cnt >= nhb && nhb > 0;
+  const int32_t G = gword[GW_G];
+  // bits / hybrid modes also write the arc giant bits (abits: bit i = al[i] == G, one
+  // ballot per 64 arcs), which the next superstep's full tally settles rows from
+  // (k_settle_*)
+  if (blockIdx.x == 0 && threadIdx.x == 0) gword[GW_ABITS_OK] = (bits || hyb) ? 1 : 0;
+  if (!bits) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < nhot; i += 1024)
+      hot[i] = (u32)(kRanked ? Ln[((int64_t)(i >> hot_lg) << slice_lg) + (i & ((1 << hot_lg) - 1))] : Ln[i]);
+    __syncthreads();
+  }
+  const u32 nh = (u32)nhot;
+  const u32 smask = kRanked ? (1u << slice_lg) - 1u : 0u, hcap = 1u << hot_lg, bcap = 1u << hb_lg;
+  auto lab = [&](int c) -> int32_t {
+    if (bits) {
+      u32 w;
+      if constexpr (kRanked) {
+        const u32 j = (u32)c & smask;
+        w = j < bcap ? hot[((((u32)c >> slice_lg) << hb_lg) + j) >> 5] : gbits[(u32)c >> 5];
+      } else {
+        w = (u32)c < (u32)nhb ? hot[(u32)c >> 5] : gbits[(u32)c >> 5];
+      }
+      return ((w >> ((u32)c & 31u)) & 1u) ? G : Ln[c];
+    }
+    if constexpr (kRanked) {
+      const u32 j = (u32)c & smask;
+      return j < hcap ? (int32_t)hot[(((u32)c >> slice_lg) << hot_lg) + j] : Ln[c];
+    } else {
+      return (u32)c < nh ? (int32_t)hot[c] : Ln[c];
+    }
+  };
+  if constexpr (kRanked) {
+    rebuild_stream(lab, G, bits, col, arcs, al, abits);
+  } else {
+    // branch-free probes (pipe3): both sources are read -- the LDS word at a clamped
+    // index, the gbits word / the label at a fixed address where it is not needed (the
+    // wave's lanes then share one line)
+    const u32 nhbu = (u32)nhb;
+    // (the slots' labels through a buffer descriptor: launch_rebuild takes this kernel at
+    // P = 1 only up to kHotMaxSlots = 2^29 slots, so every byte offset fits the voffset)
+    const auto ln_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Ln, 0, (int)(nbits * 4), 0x00020000);
+    constexpr int kPast = (int)0x80000000u;  // past every record count: no request
+    auto run = [&](auto p1, auto p2, bool wbits) {
+      // uniform: labels / hybrid mode of a blocked handle (the bits mode through the
+      // pieces measured slower, round 6: C5 superstep 3 13.4 -> 17.4 ms, C4 superstep 2
+      // 8.9 -> 12.8 ms -- its lookups hit LDS / L2 anyway, the split arc ranges cost)
+      if (kPieces && !bits) {
+        const int grp = blockIdx.x & 7;
+        const int64_t nwv = (int64_t)(gridDim.x >> 3) * (blockDim.x >> 6);
+        const int64_t wi = (int64_t)(blockIdx.x >> 3) * (blockDim.x >> 6) + (threadIdx.x >> 6);
+#ifdef LPA_BLKTIME
+        if (threadIdx.x == 0 && blockIdx.x < 512) g_blk_time[3 * blockIdx.x] = wall_clock64();
+#endif
+        for (int ph = 0; ph < blk.phases; ++ph)
+          rebuild_pieces(p1, p2, G, wbits, pieces, blk.off[grp + 8 * ph], blk.off[grp + 8 * ph + 1], wi, nwv,
+                         col, al, abits);
+#ifdef LPA_BLKTIME
+        if ((threadIdx.x & 63) == 0 && blockIdx.x < 512) atomicMax(&g_blk_time[3 * blockIdx.x + 1], wall_clock64());
+#endif
+        // then every block: the plain stream over the rows below block_deg
+        rebuild_pipe(p1, p2, G, wbits, col + blk.a0, arcs - blk.a0, al + blk.a0, abits + blk.a0 / 64);
+#ifdef LPA_BLKTIME
+        if ((threadIdx.x & 63) == 0 && blockIdx.x < 512) atomicMax(&g_blk_time[3 * blockIdx.x + 2], wall_clock64());
+#endif
+      } else {
+        rebuild_pipe(p1, p2, G, wbits, col, arcs, al, abits);
+      }
+    };
+    if (bits) {
+      // the gbits words and the labels through buffer descriptors (base + 32-bit offset:
+      // two VGPRs fewer per address under the 128 of four waves per SIMD, where the 64-bit
+      // form spilled 14), and a lane that needs no word or label takes an offset past the
+      // records: the range check drops its request instead of re-reading a fixed line
+      const auto gb_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)gbits, 0, (int)(((nbits + 31) >> 5) * 4), 0x00020000);
+      run(
+          [&](int c) -> u32 {
+            const bool h = (u32)c < nhbu;
+            const u32 hw = hot[(h ? (u32)c : nhbu - 1u) >> 5];
+            const u32 gw = __builtin_amdgcn_raw_buffer_load_b32(gb_rsrc, h ? kPast : (int)(((u32)c >> 5) << 2), 0, 0);
+            return h ? hw : gw;
+          },
+          [&](int c, u32 w) -> int32_t {
+            const bool g = (w >> ((u32)c & 31u)) & 1u;
+            const int32_t x = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(ln_rsrc, g ? kPast : (int)((u32)c << 2), 0, 0);
+            return g ? G : x;
+          },
+          true);
+    } else {
+      run([&](int c) -> u32 { return hot[(u32)c < nh ? (u32)c : nh - 1u]; },
+          [&](int c, u32 w) -> int32_t {
+            const bool h = (u32)c < nh;
+            const int32_t x = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(ln_rsrc, h ? kPast : (int)((u32)c << 2), 0, 0);
+            return h ? (int32_t)w : x;
+          },
+          hyb);
+    }
+  }
+}
+
+// al[] rebuild of a small label vector (P = 1, < kHotMinSlots slots: it stays in L2 /
+// the Infinity Cache, so an LDS hot set saves no misses while every block's 160 KB fill
+// costs as much as the arcs' stream at C2 scale): the same bits / labels modes, the
+// bits-mode test from k_giant_bits' count of the hot slots' set bits (gword[GW_HOT_BITS]).
+template <bool kIfWanted>
+__global__ __launch_bounds__(256) void k_al_rebuild_small(const unsigned long long* __restrict__ counters,
+                                                          int64_t thr, const int32_t* __restrict__ col, int64_t arcs,
+                                                          const int32_t* __restrict__ Ln, int32_t* __restrict__ al,
+                                                          const uint32_t* __restrict__ gbits, int64_t nbits,
+                                                          int32_t* __restrict__ gword,
+                                                          unsigned long long* __restrict__ abits) {
+  if (kIfWanted && !rebuild_wanted(counters, thr)) return;
+  const int64_t nhb = nbits < kHotBits ? nbits : kHotBits;
+  const bool bits = nhb > 0 && 2 * (int64_t)gword[GW_HOT_BITS] >= nhb;  // uniform
+  const int32_t G = gword[GW_G];
+  if (blockIdx.x == 0 && threadIdx.x == 0) gword[GW_ABITS_OK] = bits ? 1 : 0;
+  if (!bits) {  // labels mode: the plain 16 B/lane gather stream (C2: 0.21 -> ~0.17 ms)
+    rebuild_all(col, arcs, Ln, al);
+    return;
+  }
+  auto lab = [&](int c) -> int32_t {
+    if ((gbits[(u32)c >> 5] >> ((u32)c & 31u)) & 1u) return G;
+    return Ln[c];
+  };
+  rebuild_stream(lab, G, true, col, arcs, al, abits);
+}
+
+// gword[GW_CODE] = take the giant-code refresh: a rebuild is wanted, G is worth trying, and the
+// bits-mode rebuild (G on >= half the hot slots) does not apply; no arc giant bits then
+__global__ void k_code_mode(const unsigned long long* __restrict__ counters, int64_t thr, int64_t nhb,
+                            int32_t* __restrict__ gword) {
+  if (threadIdx.x != 0) return;
+  const bool on =
+      rebuild_wanted(counters, thr) && gword[GW_TRY] != 0 && 2 * (int64_t)gword[GW_HOT_BITS] < nhb;
+  gword[GW_CODE] = on ? 1 : 0;
+  if (on) gword[GW_ABITS_OK] = 0;
+}
+
+// code2 for every slot: 16 labels (four int4 loads) -> one word (vpad is a multiple of 64)
+__global__ __launch_bounds__(256) void k_code_build(const int4* __restrict__ L4, int64_t nw,
+                                                   const int32_t* __restrict__ gword, uint32_t* __restrict__ code2) {
+  if (gword[GW_CODE] == 0) return;
+  const u32 G = (u32)gword[GW_G];
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nw; q += (int64_t)gridDim.x * blockDim.x) {
+    u32 w = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int4 v = L4[4 * q + k];
+      w |= (giant_code2((u32)v.x, G) | (giant_code2((u32)v.y, G) << 2) | (giant_code2((u32)v.z, G) << 4) |
+            (giant_code2((u32)v.w, G) << 6))
+           << (8 * k);
+    }
+    code2[q] = w;
+  }
+}
+
+// pipe3 over this wave's whole 512-arc batches in [bat0, bat1) (grid-stride by waves)
+template <typename P1, typename P2, typename St>
+__device__ __forceinline__ void range_pipe(P1 p1, P2 p2, St st, const int32_t* __restrict__ col, int64_t bat0,
+                                           int64_t bat1) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
+  const int64_t wv = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t nb = bat0 + wv < bat1 ? (bat1 - bat0 - wv + nw - 1) / nw : 0;
+  auto base = [&](int64_t t) { return (bat0 + wv + t * nw) * 512; };
+  auto pre = [](int64_t, int) {};
+  auto fetch = [&](int64_t t, int32_t (&c)[8], int) {
+    const int64_t b = base(t);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) c[k] = __builtin_nontemporal_load(col + b + k * 64 + lane);
+  };
+  auto probe = [&](const int32_t (&c)[8], u32 (&w)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) w[k] = p1(c[k]);
+  };
+  auto resolve = [&](const int32_t (&c)[8], const u32 (&w)[8], int32_t (&r)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[k] = p2(c[k], w[k]);
+  };
+  auto store = [&](int64_t t, const int32_t (&r)[8], int) { st(base(t), r); };
+  pipe3(nb, pre, fetch, probe, resolve, store);
+}
+
+// al for [pB, arcs) (pB = code_pcut rounded down to a 512-arc batch) and al2 for [0, pA)
+// (pA = code_pcut rounded up, at most the full batches): the batch across code_pcut gets
+// both; the partial last batch (one wave) writes whichever applies.  One 1024-thread
+// block per CU, 160 KB of LDS: the labelled rows (code_lbin) first, with the 40,960
+// hottest labels in LDS, then the codes, with the 655,360 hottest slots' codes in LDS --
+// the gathers are bound by their lane count, not their bytes, so the LDS share is the
+// lever -- and the others from the 2-bit code array (vpad / 4 bytes: L2-resident at C3).
+// kRanked (a partitioned job's rank, round 6): the hot sets are the first 2^hot_lg labels
+// and the first 2^hc_lg codes of EVERY slice (degree rank k lives at slot (k mod P) S +
+// k / P, so these are the global top degree ranks), at LDS index (c / S) H + c mod S as in
+// k_al_rebuild_hot's ranked form; at P = 1 they are the first slots.
+template <bool kRanked>
+__global__ __launch_bounds__(1024) void k_code_rebuild(const int32_t* __restrict__ gword,
+                                                       const int32_t* __restrict__ col, int64_t arcs,
+                                                       const int32_t* __restrict__ Ln, int64_t nslots,
+                                                       const uint32_t* __restrict__ code2, int64_t p64,
+                                                       uint32_t* __restrict__ al2, int32_t* __restrict__ al,
+                                                       int slice_lg, int hot_lg, int hc_lg) {
+  if (gword[GW_CODE] == 0) return;
+  __shared__ u32 hot[kHotLabelsSingle];
+  const u32 G = (u32)gword[GW_G];
+  const int lane = threadIdx.x & 63;
+  const int64_t nfull = arcs >> 9;
+  const int64_t bA = min((p64 + 511) >> 9, nfull), bB = p64 >> 9;
+  const u32 smask = kRanked ? (1u << slice_lg) - 1u : 0u;
+  // slot c -> its hot-set index (h: whether it has one) for a set of 2^lg per slice
+  auto hot_at = [&](int c, int lg, u32 nflat, bool& h) -> u32 {
+    if constexpr (kRanked) {
+      const u32 j = (u32)c & smask;
+      h = j < (1u << lg);
+      return (((u32)c >> slice_lg) << lg) + j;
+    } else {
+      h = (u32)c < nflat;
+      return (u32)c;
+    }
+  };
+  // ---- the labels of the rows below the cut ----
+  const u32 nh = kRanked ? (u32)((nslots >> slice_lg) << hot_lg)
+                         : (u32)(nslots < kHotLabelsSingle ? nslots : kHotLabelsSingle);
+  for (u32 i = threadIdx.x; i < nh; i += 1024)
+    hot[i] = (u32)Ln[kRanked ? ((int64_t)(i >> hot_lg) << slice_lg) + (i & ((1u << hot_lg) - 1u)) : (int64_t)i];
+  __syncthreads();
+  range_pipe([&](int c) -> u32 {
+               bool h;
+               const u32 k = hot_at(c, hot_lg, nh, h);
+               return hot[h ? k : nh - 1u];
+             },
+             [&](int c, u32 w) -> int32_t {
+               bool h;
+               (void)hot_at(c, hot_lg, nh, h);
+               const int32_t x = Ln[h ? 0 : c];
+               return h ? (int32_t)w : x;
+             },
+             [&](int64_t b, const int32_t (&r)[8]) {
+#pragma unroll
+               for (int k = 0; k < 8; ++k) __builtin_nontemporal_store(r[k], al + b + k * 64 + lane);
+             },
+             col, bB, nfull);
+  // ---- the codes of the rows above ----
+  __syncthreads();
+  // (a multiple of 16 either way: ranked, 2^hc_lg >= 16 codes per slice)
+  const u32 nc = kRanked ? (u32)((nslots >> slice_lg) << hc_lg)
+                         : (u32)(nslots < 16 * kHotLabelsSingle ? nslots : 16 * kHotLabelsSingle);
+  for (u32 q = threadIdx.x; q < nc / 16; q += 1024)
+    hot[q] = code2[kRanked ? ((int64_t)(q >> (hc_lg - 4)) << (slice_lg - 4)) + (q & ((1u << (hc_lg - 4)) - 1u))
+                           : (int64_t)q];
+  __syncthreads();
+  auto cp1 = [&](int c) -> u32 {
+    bool h;
+    const u32 k = hot_at(c, hc_lg, nc, h);
+    const u32 cc = h ? k : nc - 1u;
+    return (hot[cc >> 4] >> (((u32)c & 15u) * 2u)) & 3u;   // (k = c mod 16 where hot)
+  };
+  auto cp2 = [&](int c, u32 w) -> int32_t {
+    bool h;
+    (void)hot_at(c, hc_lg, nc, h);
+    const u32 x = code2[h ? 0u : ((u32)c >> 4)];
+    return (int32_t)(h ? w : ((x >> (((u32)c & 15u) * 2u)) & 3u));
+  };
+  range_pipe(cp1, cp2, [&](int64_t b, const int32_t (&r)[8]) { store_code2(al2, b, r, lane); }, col, 0, bA);
+  // the partial last batch
+  const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
+  const int64_t wv = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int64_t t0 = nfull << 9;
+  if (t0 < arcs && wv == nfull % nw) {
+    int32_t r[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int64_t i = t0 + k * 64 + lane;
+      r[k] = 0;
+      if (i < arcs) {
+        const u32 x = (u32)Ln[col[i]];
+        if (i < p64) r[k] = (int32_t)giant_code2(x, G);
+        else al[i] = (int32_t)x;
+      }
+    }
+    if (t0 < p64) store_code2(al2, t0, r, lane);   // uniform; al2 covers this batch then
+  }
+}
+
+// al[] rebuild: the LDS hot-label kernel on a single-GPU handle (hub slots are
+// [0, kHotLabels) there), the plain one otherwise
+constexpr int64_t kHotMaxSlots = int64_t(1) << 29;  // k_al_rebuild_hot's 32-bit label offsets (P = 1)
+int launch_rebuild(lpa_graph* g, bool if_wanted, int64_t thr, const int32_t* L,
+                   const unsigned long long* ctr) {
+  hipStream_t s = g->stream;
+  const bool code = if_wanted && code_refresh_now(g);
+  // the giant label of the refreshed vector: the rebuild's bits below and the next
+  // superstep's tallies (launch_tally's gsel) read it
+  if (g->V > 0) {
+    hipLaunchKernelGGL(k_giant_pick, dim3(1), dim3(kPickK), 0, s, L, g->V, g->slice, g->nranks, g->gword);
+    LPA_HIP(hipGetLastError());
+  }
+  const bool ranked = rebuild_ranked(g);
+  // hot slots of the bits-mode / code-mode test (k_giant_bits' count in gword[GW_HOT_BITS]): the
+  // first kHotBits slots at P = 1, the first kHotBits / P (whole bit words) of every slice
+  // of a rank-strided vector -- the same degree-ranked top set
+  const uint64_t hmask = ranked ? (uint64_t)(g->slice - 1) : ~0ull;
+  const int64_t hlim = ranked ? std::min<int64_t>(g->slice, kHotBits / g->nranks / 64 * 64) : kHotBits;
+  const int64_t nhot_bits = ranked ? g->nranks * hlim : std::min<int64_t>(g->vpad, kHotBits);
+  if (g->rebuild_hot && g->nranks == 1 && g->vpad < kHotMinSlots) {
+    const int64_t ngrp = (g->vpad + 511) / 512;
+    const unsigned gb = cap_grid((ngrp + 3) / 4, 4096), gr = cap_grid((g->arcs + 2047) / 2048, 8192);
+    if (if_wanted) {
+      hipLaunchKernelGGL(k_giant_bits<true>, dim3(gb), dim3(256), 0, s, ctr, thr, L, g->vpad, g->gword,
+                         (unsigned long long*)g->gbits, g->abits, (int64_t)0, hmask, hlim);
+      hipLaunchKernelGGL(k_al_rebuild_small<true>, dim3(gr), dim3(256), 0, s, ctr, thr, g->col, g->arcs, L, g->al,
+                         g->gbits, g->vpad, g->gword, g->abits);
+    } else {
+      hipLaunchKernelGGL(k_giant_bits<false>, dim3(gb), dim3(256), 0, s, ctr, thr, L, g->vpad, g->gword,
+                         (unsigned long long*)g->gbits, g->abits, (int64_t)0, hmask, hlim);
+      hipLaunchKernelGGL(k_al_rebuild_small<false>, dim3(gr), dim3(256), 0, s, ctr, thr, g->col, g->arcs, L, g->al,
+                         g->gbits, g->vpad, g->gword, g->abits);
+    }
+  } else if (g->rebuild_hot && ((g->nranks == 1 && g->vpad <= kHotMaxSlots) || ranked)) {
+    int dev_cus = 256;
+    (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, g->device);
+    int slice_lg = 0, hot_lg = 0, hb_lg = 0;
+    int32_t nhot = (int32_t)(g->vpad < kHotLabelsSingle ? g->vpad : kHotLabelsSingle);
+    if (ranked) {
+      while ((int64_t(1) << slice_lg) < g->slice) ++slice_lg;
+      while ((int64_t(1) << hot_lg) < kHotLabels / g->nranks) ++hot_lg;
+      nhot = (int32_t)(g->nranks << hot_lg);
+      // bits per slice: the largest power of two with P of them in the LDS bit budget,
+      // at least one word and at most the slice
+      while ((int64_t(2) << hb_lg) * g->nranks <= kHotBits && (int64_t(2) << hb_lg) <= g->slice) ++hb_lg;
+      if (hb_lg < 5 || slice_lg < 5) hb_lg = 0;
+    }
+    // the giant-label bitmap of L first (same wanted-check: both return at once when
+    // the scatter refreshes instead)
+    const int64_t ngrp = (g->vpad + 511) / 512;
+    // class-blocked labels-mode rebuild (P = 1): a grid of whole 8-block groups
+    const bool blk = !ranked && g->blk_pieces && g->blk_a0 > 0 && dev_cus >= 8;
+    if (blk) dev_cus &= ~7;
+    const int64_t nzero = blk ? g->blk_a0 / 64 : 0;
+    if (if_wanted)
+      hipLaunchKernelGGL(k_giant_bits<true>, dim3(cap_grid((ngrp + 3) / 4, 4096)), dim3(256), 0, s, ctr, thr, L,
+                         g->vpad, g->gword, (unsigned long long*)g->gbits, g->abits, nzero, hmask, hlim);
+    else
+      hipLaunchKernelGGL(k_giant_bits<false>, dim3(cap_grid((ngrp + 3) / 4, 4096)), dim3(256), 0, s, ctr, thr, L,
+                         g->vpad, g->gword, (unsigned long long*)g->gbits, g->abits, nzero, hmask, hlim);
+    LPA_HIP(hipGetLastError());
+    // ranked without a usable bit share: nbits 0 keeps every block in labels mode
+    const int64_t nbits = (ranked && hb_lg == 0) ? 0 : g->vpad;
+    BlkInfo binfo;
+    for (int x = 0; x <= kMaxBlkClasses; ++x) binfo.off[x] = g->blk_off[x];
+    binfo.a0 = blk ? g->blk_a0 : 0;
+    binfo.phases = g->blk_classes / 8;
+#define LPA_HOT_LAUNCH(W, R, B)                                                                  \
+  hipLaunchKernelGGL((k_al_rebuild_hot<W, R, B>), dim3(dev_cus), dim3(1024), 0, s, ctr, thr, g->col, \
+                     g->arcs, L, nhot, g->al, slice_lg, hot_lg, hb_lg, g->gbits, nbits, g->gword, g->abits, \
+                     blk ? g->blk_pieces : nullptr, binfo, code ? g->gword + GW_CODE : nullptr)
+    if (code) {
+      hipLaunchKernelGGL(k_code_mode, dim3(1), dim3(64), 0, s, ctr, thr, nhot_bits, g->gword);
+      LPA_HIP(hipGetLastError());
+    }
+    if (if_wanted) {
+      if (ranked) LPA_HOT_LAUNCH(true, true, false);
+      else if (blk) LPA_HOT_LAUNCH(true, false, true);
+      else LPA_HOT_LAUNCH(true, false, false);
+    } else {
+      if (ranked) LPA_HOT_LAUNCH(false, true, false);
+      else if (blk) LPA_HOT_LAUNCH(false, false, true);
+      else LPA_HOT_LAUNCH(false, false, false);
+    }
+#undef LPA_HOT_LAUNCH
+    if (code) {
+      LPA_HIP(hipGetLastError());
+      hipLaunchKernelGGL(k_code_build, dim3(cap_grid((g->vpad / 16 + 255) / 256, 4096)), dim3(256), 0, s,
+                         (const int4*)L, g->vpad / 16, g->gword, g->code2);
+      LPA_HIP(hipGetLastError());
+      // ranked: 2^hc_lg codes of every slice in LDS (P << hc_lg <= 16 kHotLabelsSingle)
+      int hc_lg = 4;
+      while (ranked && (int64_t(g->nranks) << (hc_lg + 1)) <= 16ll * kHotLabelsSingle &&
+             (int64_t(1) << (hc_lg + 1)) <= g->slice)
+        ++hc_lg;
+      if (ranked)
+        hipLaunchKernelGGL(k_code_rebuild<true>, dim3(dev_cus), dim3(1024), 0, s, g->gword, g->col, g->arcs, L,
+                           g->vpad, g->code2, g->code_pcut, g->al2, g->al, slice_lg, hot_lg, hc_lg);
+      else
+        hipLaunchKernelGGL(k_code_rebuild<false>, dim3(dev_cus), dim3(1024), 0, s, g->gword, g->col, g->arcs, L,
+                           g->vpad, g->code2, g->code_pcut, g->al2, g->al, 0, 0, 0);
+    }
+  } else {
+    const unsigned grid = cap_grid((g->arcs / 4 + 511) / 512, 8192);
+    if (if_wanted)
+      hipLaunchKernelGGL(k_al_rebuild<true>, dim3(grid), dim3(256), 0, s, ctr, thr, g->col,
+                         g->arcs, L, g->al, g->gword);
+    else
+      hipLaunchKernelGGL(k_al_rebuild<false>, dim3(grid), dim3(256), 0, s, ctr, thr, g->col,
+                         g->arcs, L, g->al, g->gword);
+  }
+  LPA_HIP(hipGetLastError());
+  return LPA_OK;
+}
+
+}  // namespace
+
+// changed slots in [s0, s1) -> position chunks + dirty-arc count (counters of this
+// superstep's parity)
+int launch_diff(lpa_graph* g, hipStream_t st, const int32_t* Lc, const int32_t* Ln, int64_t s0,
+                int64_t s1, bool sync, int par, int b0, int b1, int mode) {
+  if (s1 <= s0) return LPA_OK;
+  const int64_t nq = (s1 + 3) / 4 - s0 / 4;
+  BinBounds bnd;
+  for (int b = 0; b <= LPA_NBINS; ++b) bnd.b[b] = g->bin_begin[b];
+  // bins [b0, b1) given: the frontier list mode is available (the concurrent tally
+  // of this superstep; its lists are those of g->par)
+  const bool lists = b1 > b0;
+  hipLaunchKernelGGL(k_diff, dim3((unsigned)((nq + kDiffQuads - 1) / kDiffQuads)), dim3(256), 0, st,
+                     (const int4*)Lc, (const int4*)Ln, sync ? const_cast<int32_t*>(Lc) : nullptr, s0, s1,
+                     g->cptr, g->cch, g->chflag, g->chlist, g->counters + 4 * par, bnd, b0, b1,
+                     lists ? g->flist : nullptr, g->fcnt + 16 * g->par, g->fr_all + g->par, mode);
+  LPA_HIP(hipGetLastError());
+  return LPA_OK;
+}
+
+// refresh al[] for L_next (after the exchange, so every rank sees all changes) of the
+// superstep of parity `par`; diff_done: the tally schedule already ran the diff per
+// stream (launch_tally) or the exchange listed the changes
+// fold_rebuild: k_al_scatter does a wanted rebuild itself (captured converged
+// supersteps: saves the rebuild launch, which is almost never wanted there)
+int launch_refresh(lpa_graph* g, const int32_t* Lc, const int32_t* Ln, bool diff_done, int par,
+                   hipEvent_t ev_scatter, bool fold_rebuild) {
+  if (g->arcs == 0) return LPA_OK;
+  hipStream_t s = g->stream;
+  // this superstep's counters (zeroed by the previous k_al_scatter or at build)
+  unsigned long long* ctr = g->counters + 4 * par;
+  // one rank: its isolated slots (and the padding) never change; P > 1: the whole
+  // replicated vector (other ranks' slots change through the exchange)
+  const int64_t nd = !exchanges(g) ? g->bin_begin[BIN_ISO] : g->vpad;
+  // diff_done means, at P = 1, that the tally's per-stream diffs ran (count-only ones in
+  // a label-dense superstep); at P > 1, that the delta exchange queued every change
+  // already (nothing left to count or diff)
+  if (dense_refresh(g) && !(diff_done && exchanges(g))) {
+    // counted changed slots (in the tally, or here) -> rebuild, or the full diff
+    if (!diff_done) LPA_TRY(launch_diff(g, s, Lc, Ln, 0, nd, false, par, 0, 0, 1));
+    hipLaunchKernelGGL(k_dense_decide, dim3(1), dim3(64), 0, s, ctr, nd, g->gword);
+    LPA_HIP(hipGetLastError());
+    LPA_TRY(launch_diff(g, s, Lc, Ln, 0, nd, true, par, 0, 0, 2));
+  } else {
+    if (!diff_done) LPA_TRY(launch_diff(g, s, Lc, Ln, 0, nd, true, par));
+    // P > 1, superstep 2 after a giant-code refresh, its changes exchanged as a delta
+    // (the change chunks are queued): the rows it settled from codes have no al[] entries,
+    // so this refresh rebuilds whatever the change count (k_dense_decide's code clause)
+    if (code_tally_now(g)) {
+      hipLaunchKernelGGL(k_dense_decide, dim3(1), dim3(64), 0, s, ctr, INT64_MAX, g->gword);
+      LPA_HIP(hipGetLastError());
+    }
+  }
+  LPA_TRACE_POINT("diff");
+  // (a handle without the CSC position index rebuilds every time: counters[1] >= 0 > -1)
+  const int64_t thr = g->no_scatter ? -1 : (int64_t)(kRebuildFrac * (double)g->arcs);
+  FrontierMarks fm;
+  fm.crow = g->crow;
+  fm.rp = g->rp;
+  fm.uoff = g->hub_uoff;
+  fm.n_hub = g->n_hub;
+  fm.rdirty = g->rdirty[par ^ 1];
+  fm.udirty = g->udirty[par ^ 1];
+  if (code_tally3_now(g)) {
+    // superstep 3 after a giant-code refresh: its settled rows' al[] entries were never
+    // written, so this refresh rebuilds (k_dense_decide's code clause; n_slots: no count)
+    hipLaunchKernelGGL(k_dense_decide, dim3(1), dim3(64), 0, s, ctr, INT64_MAX, g->gword);
+    LPA_HIP(hipGetLastError());
+  }
+  // gather mode (lpa_build): no al[] to keep -- the scatter only marks the rows the next
+  // superstep re-tallies (and syncs the changed labels into Lc), no rebuild
+  const bool gnow = gather_now(g);
+  // superstep 3's refresh keeps the arc giant bits of superstep 2's bits-mode rebuild
+  // (k_al_scatter; superstep 4's row settle reads them)
+  const bool keep_bits = keep_bits_now(g);
+  if (g->al_pending && !gnow) {  // the column-run superstep after a lazy reset (al holds nothing)
+    hipLaunchKernelGGL(k_al_fill_unless_rebuild, dim3(cap_grid((g->arcs / 4 + 255) / 256, 8192)), dim3(256), 0, s,
+                       ctr, thr, (const v4i*)g->al0, (v4i*)g->al, g->arcs);
+    LPA_HIP(hipGetLastError());
+    g->al_pending = false;  // the rebuild below (or this fill + the scatter) makes al valid
+  }
+  hipLaunchKernelGGL(k_al_scatter, dim3(2048), dim3(256), 0, s, g->chlist, (const uint4*)g->chflag,
+                     (g->n_chunk_scan + 15) / 16, g->cowner, g->cch, ctr,
+                     g->counters + 4 * (par ^ 1), g->cptr,
+                     g->cpos, Ln, gnow ? (int32_t*)nullptr : g->al, thr, fm, g->fr_all + (par ^ 1),
+                     g->frontier, (int64_t)(kFrontierFrac * (double)g->arcs), const_cast<int32_t*>(Lc),
+                     (fold_rebuild && !gnow) ? g->col : (const int32_t*)nullptr, g->arcs, g->gword,
+                     keep_bits ? 1 : 0, g->gbits, g->abits);
+  LPA_HIP(hipGetLastError());
+  LPA_TRACE_POINT("scatter");
+  if (ev_scatter) LPA_HIP(hipEventRecord(ev_scatter, s));  // profiling: scatter | rebuild
+  if (gnow && gather_last_step(g)) {
+    // the last gather-mode superstep: al[] for the supersteps after it, one plain rebuild
+    const unsigned grid = cap_grid((g->arcs / 4 + 511) / 512, 8192);
+    hipLaunchKernelGGL(k_al_rebuild<false>, dim3(grid), dim3(256), 0, s, ctr, thr, g->col, g->arcs, Ln, g->al,
+                       g->gword);
+    LPA_HIP(hipGetLastError());
+  } else if (!fold_rebuild && !gnow) {
+    LPA_TRY(launch_rebuild(g, true, thr, Ln, ctr));
+  }
+  LPA_HIP(hipGetLastError());
+  return LPA_OK;
+}
+
+// (the caller-driven delta exchange, lpa_exchange_put_delta: the refresh of the superstep
+// lpa_step just ran, which since_reset already counts -- it is seen as the in-library
+// refresh of that superstep sees it: dense / code-settled supersteps, code refresh allowed)
+int launch_refresh_ext(lpa_graph* g, const int32_t* Lc, const int32_t* Ln, bool diff_done, int par) {
+  const bool back = g->since_reset > 0;
+  if (back) --g->since_reset;
+  const int rc = launch_refresh(g, Lc, Ln, diff_done, par);
+  if (back) ++g->since_reset;
+  return rc;
+}
+
+int rebuild_arc_labels(lpa_graph* g) {
+  if (g->arcs == 0) return LPA_OK;
+  return launch_rebuild(g, false, 0, g->lab[g->cur], g->counters);
+}
+
+int refresh_after_put(lpa_graph* g) {
+  if (g->arcs == 0) return LPA_OK;
+  if (at_l0(g)) return rebuild_arc_labels(g);   // no superstep ran since L0
+  // the refresh of the superstep lpa_step just ran (since_reset counted it already): an
+  // unconditional rebuild (thr = -1: every rebuild_wanted test passes), the giant codes
+  // allowed after superstep 1 or 2 as in the in-library schedule
+  --g->since_reset;
+  const int rc = launch_rebuild(g, true, -1, g->lab[g->cur], g->counters + 4 * (g->par ^ 1));
+  ++g->since_reset;
+  return rc;
+}
+
+}  // namespace lpa

@@ -81,7 +81,7 @@ def random_multigraph(V, m, seed):
 
 
 def comb_bucket(labels, lg):
-    """k_hub_combine's label-hash bucket (lpa_iter.hip comb_bucket)."""
+    """k_hub_combine's label-hash bucket (lpa_hub.hip comb_bucket)."""
     x = (labels.astype(np.uint64) * np.uint64(0x85EBCA77)) & np.uint64(0xFFFFFFFF)
     return (x >> np.uint64(32 - lg)).astype(np.int64) if lg else np.zeros(labels.shape, np.int64)
 
@@ -161,13 +161,13 @@ def _mul32(x, k):
 
 
 def hash_slot(labels, shift):
-    """lpa_iter.hip hash_slot: shift 26 = the 64 buckets of giant_count (wave bins, block
+    """lpa_device.h hash_slot: shift 26 = the 64 buckets of giant_count (wave bins, block
     rows, units), shift 28 = the 16 buckets of the row bins' giant test."""
     return (_mul32(labels, 0x9E3779B1) >> np.uint64(shift)).astype(np.int64)
 
 
 def giant_code2(labels):
-    """lpa_iter.hip giant_code2 of a label that is not G: 1 + a 3-way label hash."""
+    """lpa_codes.h giant_code2 of a label that is not G: 1 + a 3-way label hash."""
     return (1 + (((_mul32(labels, 0x9E3779B1) >> np.uint64(24)) * np.uint64(3)) >> np.uint64(8))).astype(np.int64)
 
 
@@ -335,7 +335,7 @@ def tie_rows(degrees=TIE_DEGREES, g_mass=90_000, pad_to=0, mult_g=(200, 160, 130
 
 def code_mix(src, dst, V0):
     """R-MAT edges (V0 vertices) plus structures whose superstep-2 mode is NOT the giant
-    label, so that the giant-code settle of superstep 2 (lpa_iter.hip "Giant codes")
+    label, so that the giant-code settle of superstep 2 (lpa_codes.h "Giant codes")
     leaves rows to its exact fallback paths: five 200-cliques (wave-bin rows, 199 arcs,
     their own block's label), a 1,100-clique (block-tier hub rows, glist) and a leader
     l < hub h pair sharing 9,000 two-arc members (rows of 9,000 arcs above the block

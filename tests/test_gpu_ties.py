@@ -33,7 +33,7 @@ STEPS = 8
 PAD = 1 << 22
 K_REBUILD_FRAC = 0.25       # lpa_internal.h kRebuildFrac
 K_FRONTIER_FRAC = 0.005     # kFrontierFrac
-K_HOT_BITS = 32 * (40960 - 1)   # lpa_iter.hip kHotBits: the hot slots of a P = 1 handle
+K_HOT_BITS = 32 * (40960 - 1)   # lpa_refresh.hip kHotBits: the hot slots of a P = 1 handle
 BINS = ("seg", "w16", "w8", "w4", "w2", "g64", "g32", "g16", "g8", "g4", "g2", "g1")
 
 
