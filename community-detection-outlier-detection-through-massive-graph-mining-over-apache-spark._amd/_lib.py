@@ -102,6 +102,14 @@ class LpaTriangleSummary(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LpaPagerankSummary(ctypes.Structure):
+    _fields_ = [("rank_sum", ctypes.c_double), ("max_rank", ctypes.c_double), ("max_rank_id", ctypes.c_int64),
+                ("edges", ctypes.c_int64), ("sinks", ctypes.c_int64), ("max_in_degree", ctypes.c_int64)]
+
+    def to_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class LpaOutlierSummary(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in (
         "n_groups", "k", "threshold", "n_flagged", "n_communities", "n_communities_flagged",
@@ -144,6 +152,8 @@ SIGNATURES = {
     "lpa_quality": (ctypes.c_int, [_vp, _vp, ctypes.c_int32, _vp]),
     "lpa_components": (ctypes.c_int, [_vp, _vp, ctypes.c_int32, _vp, ctypes.POINTER(LpaComponentsSummary)]),
     "lpa_triangle_count": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int32, ctypes.POINTER(LpaTriangleSummary)]),
+    "lpa_pagerank": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _vp, _vp, _vp,
+                                    ctypes.c_int32, ctypes.POINTER(LpaPagerankSummary)]),
     "lpa_loopback_create": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(_vp)]),
     "lpa_loopback_abort": (None, [_vp]),
     "lpa_loopback_destroy": (None, [_vp]),

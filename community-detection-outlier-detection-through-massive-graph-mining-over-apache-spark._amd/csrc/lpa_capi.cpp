@@ -240,6 +240,8 @@ int create_common(int32_t device, hipStream_t stream, const int32_t* src, const 
   if (const char* f = getenv("LPA_TC_SHORT")) g->tc_short = atoi(f) < 0 ? 0 : atoi(f);
   if (const char* f = getenv("LPA_TC_WAVE")) g->tc_wave = atoi(f) < 0 ? 0 : atoi(f) > kTcWaveMax ? kTcWaveMax : atoi(f);
   if (const char* f = getenv("LPA_TC_LDS")) g->tc_lds = atoi(f) < 0 ? 0 : atoi(f) > kTcLdsMax ? kTcLdsMax : atoi(f);
+  if (const char* f = getenv("LPA_PR_SHORT")) g->pr_short = atoi(f) < 0 ? 0 : atoi(f);
+  if (const char* f = getenv("LPA_PR_WAVE")) g->pr_wave = atoi(f) < 0 ? 0 : atoi(f);
   if (const char* f = getenv("LPA_CONV_STREAMS")) g->conv_streams = atoi(f) < 1 ? 1 : atoi(f) > 3 ? 3 : atoi(f);
   // internal builds (the outlier stage's L2 sub-graph): the locality order is a
   // gather-locality heuristic worth its two atomic passes only on a graph that runs
@@ -655,6 +657,37 @@ int lpa_triangle_count(lpa_graph* g, int64_t* count_out, int64_t* simple_degree_
   }
   LPA_HIP(hipSetDevice(g->device));
   return triangle_count(g, count_out, simple_degree_out, out_is_device, summary);
+}
+
+int lpa_pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, int32_t source, double* rank_out,
+                 int64_t* out_degree_out, int64_t* in_degree_out, int32_t out_is_device,
+                 lpa_pagerank_summary* summary) {
+  if (!g) {
+    set_error("null handle");
+    return LPA_EINVAL;
+  }
+  if (max_iter <= 0) {
+    set_error("lpa_pagerank: max_iter must be greater than 0, got %d", max_iter);
+    return LPA_EINVAL;
+  }
+  if (!(reset_prob >= 0.0 && reset_prob <= 1.0)) {   // NaN fails both
+    set_error("lpa_pagerank: reset_prob must belong to [0, 1], got %g", reset_prob);
+    return LPA_EINVAL;
+  }
+  if (source < -1 || (int64_t)source >= g->V) {
+    set_error("lpa_pagerank: source %d is neither -1 nor a vertex of [0, %lld)", source, (long long)g->V);
+    return LPA_EINVAL;
+  }
+  if (!rank_out && g->V > 0) {
+    set_error("lpa_pagerank: null rank output");
+    return LPA_EINVAL;
+  }
+  if (g->m > 0 && !g->e_src) {
+    set_error("lpa_pagerank of a distributed job runs on rank 0 (the rank that keeps the edge list)");
+    return LPA_EINVAL;
+  }
+  LPA_HIP(hipSetDevice(g->device));
+  return pagerank(g, max_iter, reset_prob, source, rank_out, out_degree_out, in_degree_out, out_is_device, summary);
 }
 
 int lpa_degrees(lpa_graph* g, int32_t* deg_out) {

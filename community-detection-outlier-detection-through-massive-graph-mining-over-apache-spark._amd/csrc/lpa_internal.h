@@ -86,6 +86,9 @@ constexpr int kTcWaveMax = 1024;      // a wave per row, the list in 4 KB of the
 constexpr int kTcLdsMax = 15360;      // a block per row, the list in 60 KB of LDS (with the team's
                                       //   offsets under the 64 KB a launch gets without opting in,
                                       //   two blocks per CU; a longer list needs > 1.1e8 simple edges)
+// PageRank (lpa_pr.hip): default in-list lengths of its row forms
+constexpr int kPrShort = 32;          // 8 lanes per row up to this length
+constexpr int kPrWave = 1024;         // a wave per row up to this length; longer: a block of 1024 per row
 __host__ __device__ inline uint32_t col_class(int32_t c, uint32_t ncls) { return ((uint32_t)c >> 10) & (ncls - 1u); }
 
 struct Segment {   // one unit of a seg-bin row
@@ -372,6 +375,10 @@ struct lpa_graph {
   int tc_short = lpa::kTcShort;             // LPA_TC_SHORT (>= 0; 0: no row takes the group form)
   int tc_wave = lpa::kTcWaveMax;            // LPA_TC_WAVE  (0 .. kTcWaveMax)
   int tc_lds = lpa::kTcLdsMax;              // LPA_TC_LDS   (0 .. kTcLdsMax)
+  // PageRank (lpa_pr.hip): in-list lengths up to which a row takes the short form and the
+  // wave form (longer: the block form); a row without in-edges always takes the short form
+  int pr_short = lpa::kPrShort;             // LPA_PR_SHORT (>= 0; 0: no row with an in-edge takes the short form)
+  int pr_wave = lpa::kPrWave;               // LPA_PR_WAVE  (>= 0; 0, or <= LPA_PR_SHORT: no row takes the wave form)
   int serial = 0;                           // LPA_SERIAL=1: all tally kernels on one stream (profiling)
   int use_graphs = 1;                       // LPA_GRAPHS=0: no captured superstep graphs
   // captured supersteps: [0, 4) converged per (cur, par); [4, 12) supersteps 2 and 3 per
@@ -549,5 +556,9 @@ int components(lpa_graph* g, int32_t* comp_out, int32_t out_is_device, int64_t* 
 // triangles per vertex of the simple undirected graph (lpa_tc.hip)
 int triangle_count(lpa_graph* g, int64_t* count_out, int64_t* simple_degree_out, int32_t out_is_device,
                    lpa_triangle_summary* summary);
+
+// static PageRank of the directed multigraph (lpa_pr.hip)
+int pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, int32_t source, double* rank_out,
+             int64_t* out_degree_out, int64_t* in_degree_out, int32_t out_is_device, lpa_pagerank_summary* summary);
 
 }  // namespace lpa

@@ -382,6 +382,57 @@ class Graph:
                                                 ctypes.byref(summ) if stats else None))
         return (count, deg, summ.to_dict()) if stats else count
 
+    # -- PageRank -----------------------------------------------------------------
+    def pagerank(self, max_iter: int, reset_prob: float = 0.15, source=None, out=None, stats: bool = False):
+        """Static PageRank of the directed input multigraph (lpa_pagerank; GraphX
+        ``PageRank.runWithOptions``): exactly ``max_iter`` supersteps from rank 1.0, every
+        kept edge u -> v weighted 1 / outdeg[u] (duplicates are edges), then normalised to
+        sum to ``num_vertices``.  ``source`` (a dense id): the personalised form, which
+        starts and resets at that vertex only and sums to 1.  Host float64 array by default,
+        or written into the float64 device tensor ``out`` (this handle's device,
+        ``num_vertices`` entries).  ``stats=True`` returns ``(rank, out_degree, in_degree,
+        summary)``: the degrees (int64, in the memory ``rank`` is in) count duplicates;
+        ``summary`` is a dict of rank_sum (before normalisation), max_rank, max_rank_id,
+        edges, sinks, max_in_degree.  The ranks are bit-identical across runs, handles and
+        input edge orders.  The labels and the LPA state are not touched."""
+        if not isinstance(max_iter, (int, np.integer)) or isinstance(max_iter, bool):
+            raise TypeError(f"max_iter must be an int, got {type(max_iter).__name__}")
+        if source is not None and (not isinstance(source, (int, np.integer)) or isinstance(source, bool)):
+            raise TypeError(f"source must be a dense vertex id or None, got {type(source).__name__}")
+        V = self.num_vertices
+        src = -1 if source is None else int(source)
+        if source is not None and not 0 <= src < V:
+            raise ValueError(f"source {src} is not a vertex of [0, {V})")
+        odeg = ideg = None
+        if out is not None and _is_device_tensor(out):
+            import torch
+
+            if out.dtype != torch.float64:
+                raise ValueError(f"out must be float64, got {out.dtype}")
+            if out.device.index != self.device:
+                raise ValueError(f"out must be on cuda:{self.device}, got {out.device}")
+            if out.numel() != V or not out.is_contiguous():
+                raise ValueError(f"out must hold {V} contiguous entries")
+            rank, ptr, on_dev = out, out.data_ptr(), 1
+            if stats:
+                odeg = torch.empty(V, dtype=torch.int64, device=out.device)
+                ideg = torch.empty(V, dtype=torch.int64, device=out.device)
+            torch.cuda.current_stream(out.device).synchronize()   # the library works on its own stream
+            odeg_ptr, ideg_ptr = (odeg.data_ptr(), ideg.data_ptr()) if stats else (None, None)
+        elif out is not None:
+            raise ValueError("out must be a float64 device tensor")
+        else:
+            rank = np.empty(V, dtype=np.float64)
+            ptr, on_dev = rank.ctypes.data, 0
+            if stats:
+                odeg = np.empty(V, dtype=np.int64)
+                ideg = np.empty(V, dtype=np.int64)
+            odeg_ptr, ideg_ptr = (odeg.ctypes.data, ideg.ctypes.data) if stats else (None, None)
+        summ = _lib.LpaPagerankSummary()
+        _lib.check(self._lib.lpa_pagerank(self._handle(), int(max_iter), float(reset_prob), src, ptr, odeg_ptr,
+                                          ideg_ptr, on_dev, ctypes.byref(summ) if stats else None))
+        return (rank, odeg, ideg, summ.to_dict()) if stats else rank
+
 
 class Loopback:
     """In-process collective group of ``nranks`` handles on one device (the

@@ -35,6 +35,8 @@ from .graph import Graph
 ID, SRC, DST, LABEL = "id", "src", "dst", "label"
 COMPONENT = "component"
 COUNT = "count"
+PAGERANK = "pagerank"
+WEIGHT = "weight"
 CC_ALGORITHMS = ("graphframes", "graphx")
 
 
@@ -44,6 +46,24 @@ def _check_max_iter(maxIter):
     if maxIter <= 0:
         # GraphX LabelPropagation.run: require(maxSteps > 0, ...)
         raise ValueError(f"requirement failed: Maximum of steps must be greater than 0, but got {maxIter}")
+
+
+def _check_page_rank(resetProbability, maxIter, tol):
+    """The argument checks of GraphFrame.pageRank, before any device work."""
+    if (maxIter is None) == (tol is None):
+        # graphframes.GraphFrame.pageRank (0.6.0)
+        raise ValueError("Exactly one of maxIter or tol should be set.")
+    if tol is not None:
+        raise NotImplementedError(
+            "pageRank(tol=...) (GraphX runUntilConvergence) is not implemented; use maxIter for the static form")
+    if not isinstance(maxIter, (int, np.integer)) or isinstance(maxIter, bool):
+        raise TypeError(f"maxIter must be an int, got {type(maxIter).__name__}")
+    if maxIter <= 0:
+        # GraphX PageRank.runWithOptions: require(numIter > 0, ...)
+        raise ValueError(f"requirement failed: Number of iterations must be greater than 0, but got {maxIter}")
+    if not 0 <= resetProbability <= 1:   # NaN fails both
+        raise ValueError(
+            f"requirement failed: Random reset probability must belong to [0, 1], but got {resetProbability}")
 
 
 def _check_cc_algorithm(algorithm):
@@ -73,6 +93,7 @@ class IndexedGraph:
     dst: np.ndarray          # int32 dense
     integral: bool           # integral ids -> labels are original ids
     dropped_edges: int = 0
+    kept: np.ndarray | None = None   # bool per input edge row: both endpoints are vertex ids
 
     @property
     def num_vertices(self) -> int:
@@ -87,7 +108,8 @@ def index_graph(v: pd.DataFrame, e: pd.DataFrame) -> IndexedGraph:
     s_raw = e[SRC].to_numpy()
     d_raw = e[DST].to_numpy()
     if n == 0:
-        return IndexedGraph(ids, np.empty(0, np.int32), np.empty(0, np.int32), integral, len(e))
+        return IndexedGraph(ids, np.empty(0, np.int32), np.empty(0, np.int32), integral, len(e),
+                            np.zeros(len(e), bool))
     if integral:
         s_raw = s_raw.astype(ids.dtype, copy=False) if pd.api.types.is_integer_dtype(e[SRC].dtype) else s_raw
         d_raw = d_raw.astype(ids.dtype, copy=False) if pd.api.types.is_integer_dtype(e[DST].dtype) else d_raw
@@ -99,7 +121,7 @@ def index_graph(v: pd.DataFrame, e: pd.DataFrame) -> IndexedGraph:
     d_ok[d_ok] = ids[d[d_ok]] == d_raw[d_ok]
     keep = s_ok & d_ok
     return IndexedGraph(ids, s[keep].astype(np.int32), d[keep].astype(np.int32), integral,
-                        int((~keep).sum()))
+                        int((~keep).sum()), keep)
 
 
 def _label_values(ig: IndexedGraph, dense_labels: np.ndarray) -> np.ndarray:
@@ -198,6 +220,55 @@ class GraphFrame:
         out.attrs["transitivity"] = 3.0 * summ["n_triangles"] / wedges if wedges > 0 else 0.0
         return out
 
+    def _source_dense(self, sourceId):
+        """Dense id of ``sourceId`` (None: none); a ValueError when it is no vertex id."""
+        if sourceId is None:
+            return None
+        ids = self._indexed().ids
+        try:
+            pos = int(np.searchsorted(ids, sourceId))
+            found = pos < ids.size and bool(ids[pos] == sourceId)
+        except TypeError:
+            found = False
+        if not found:
+            raise ValueError(f"sourceId {sourceId!r} is not a vertex id")
+        return pos
+
+    def pageRank(self, resetProbability: float = 0.15, sourceId=None, maxIter: int | None = None,
+                 tol: float | None = None) -> "GraphFrame":
+        """``GraphFrame.pageRank(maxIter=...)``: static PageRank (GraphX
+        ``PageRank.runWithOptions``) of the directed multigraph as given -- duplicate edges
+        are edges, a sink's mass is lost every superstep, and the ranks are normalised at the
+        end to sum to the number of vertices.  ``sourceId``: the personalised form (ranks sum
+        to 1).  Returns a **GraphFrame**, as GraphFrames does: ``.vertices`` is the vertex
+        rows (sorted by id) + ``pagerank`` (float64), ``.edges`` the edges whose endpoints
+        are both vertex ids, in input order, + ``weight`` (float64) = 1 / out-degree of
+        ``src``.  ``tol`` (GraphX ``runUntilConvergence``, another algorithm) raises
+        ``NotImplementedError``."""
+        _check_page_rank(resetProbability, maxIter, tol)
+        ig = self._indexed()
+        source = self._source_dense(sourceId)
+        rank, odeg, _, _ = self._gpu_graph().pagerank(int(maxIter), float(resetProbability), source, stats=True)
+        vdf = _attach(self._v, ig, {PAGERANK: rank})
+        edf = self._e[ig.kept].reset_index(drop=True)
+        edf[WEIGHT] = 1.0 / odeg[ig.src].astype(np.float64)
+        return GraphFrame(vdf, edf, device=self._device)
+
+    def inDegrees(self) -> pd.DataFrame:
+        """Vertices + ``inDegree`` (int64): the kept edges ending at each vertex, duplicates
+        counted.  Every vertex has a row, with 0 where GraphFrames' property leaves the
+        vertex out; a method, like ``degrees``."""
+        ig = self._indexed()
+        _, _, ideg, _ = self._gpu_graph().pagerank(1, stats=True)
+        return _attach(self._v, ig, {"inDegree": ideg})
+
+    def outDegrees(self) -> pd.DataFrame:
+        """Vertices + ``outDegree`` (int64): the kept edges leaving each vertex, duplicates
+        counted; zeros included, a method (see ``inDegrees``)."""
+        ig = self._indexed()
+        _, odeg, _, _ = self._gpu_graph().pagerank(1, stats=True)
+        return _attach(self._v, ig, {"outDegree": odeg})
+
     def dense_labels(self, maxIter: int) -> np.ndarray:
         _check_max_iter(maxIter)
         return self._gpu_graph().run(int(maxIter))
@@ -242,6 +313,17 @@ def triangle_count(vertices: pd.DataFrame, edges: pd.DataFrame, device: int = 0)
     gf = GraphFrame(vertices, edges, device=device)
     try:
         return gf.triangleCount()
+    finally:
+        gf.close()
+
+
+def page_rank(vertices: pd.DataFrame, edges: pd.DataFrame, maxIter: int, resetProbability: float = 0.15,
+              sourceId=None, device: int = 0) -> pd.DataFrame:
+    """Function form of ``GraphFrame(vertices, edges).pageRank(resetProbability, sourceId,
+    maxIter=maxIter).vertices``: the vertex table + ``pagerank``."""
+    gf = GraphFrame(vertices, edges, device=device)
+    try:
+        return gf.pageRank(resetProbability=resetProbability, sourceId=sourceId, maxIter=maxIter).vertices
     finally:
         gf.close()
 

@@ -338,6 +338,46 @@ typedef struct lpa_triangle_summary {
 int lpa_triangle_count(lpa_graph* g, int64_t* count_out, int64_t* simple_degree_out,
                        int32_t out_is_device, lpa_triangle_summary* summary);
 
+/*
+ * Static PageRank (GraphX PageRank.runWithOptions / GraphFrame.pageRank(maxIter)) of the
+ * DIRECTED input multigraph as given: every kept edge is an edge, a duplicate one more, a
+ * self-loop one edge from the vertex to itself.  IEEE binary64 throughout.  With
+ * outdeg[u] = the kept edges leaving u, w[u] = 1.0 / outdeg[u] (0.0 for a sink, never
+ * read there), a = reset_prob:
+ *   start   r[v] = 1.0; with a source (source >= 0, a dense id), 1.0 at the source, else 0.0
+ *   step    max_iter times, every read of the previous r:
+ *             c[u] = r[u] * w[u];  s[v] = sum of c[u] over the edges u -> v (0.0 with none)
+ *             r[v] = a + (1.0 - a) * s[v]; with a source, (v == source ? a : 0.0) + (1.0 - a) * s[v]
+ *   finish  S = sum r;  r[v] *= (double)V / S; with a source, r[v] /= S
+ * A sink's mass is lost in a step (GraphX's behaviour); the finish makes up for it.  With
+ * a = 0 and no source a graph in which every walk dies gives S == 0 and whatever IEEE
+ * gives for V / 0.  rank_out (V entries, required) by dense id; out_degree_out and
+ * in_degree_out (nullable, V entries, int64, duplicates counted).  The arrays are host
+ * memory unless out_is_device; summary is nullable.  V == 0: success, nothing written,
+ * summary {0, 0, -1, 0, 0, 0}.  LPA_EINVAL for max_iter <= 0, reset_prob outside [0, 1]
+ * or NaN, source outside [-1, V), a null rank_out with V > 0.  The call blocks until the
+ * work is done.  A pull over the in-lists of a CSR sorted by (dst, src), without a single
+ * floating-point atomic: every sum has a shape fixed by the row's length, the handle's
+ * form boundaries and V, so the ranks are bit-identical across runs, handles and input
+ * edge orders (DESIGN.md "PageRank"); two implementations of the same max_iter = k differ
+ * per vertex by a relative 2 (k (D + 2) + V + 2) 2^-53 at most, D the largest in-degree.
+ * All working memory is stream-ordered temporaries, the labels and every other piece of
+ * lpa_step's state are neither read nor written, nothing is kept on the handle.  On a
+ * distributed job (nranks > 1) only rank 0 keeps the edge list this needs; the other
+ * ranks return LPA_EINVAL.  Since ABI 10.
+ */
+typedef struct lpa_pagerank_summary {
+  double  rank_sum;      /* S before normalisation                               */
+  double  max_rank;      /* largest normalised rank (0 if V == 0)                */
+  int64_t max_rank_id;   /* its dense id, the smallest on a tie; -1 if V == 0    */
+  int64_t edges;         /* kept directed edges, duplicates counted              */
+  int64_t sinks;         /* vertices with out-degree 0                           */
+  int64_t max_in_degree; /* with multiplicity                                    */
+} lpa_pagerank_summary;  /* 48 bytes */
+int lpa_pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, int32_t source /* -1: none */,
+                 double* rank_out, int64_t* out_degree_out, int64_t* in_degree_out,
+                 int32_t out_is_device, lpa_pagerank_summary* summary);
+
 /* Symmetrised degree of every vertex (dense ids), host output. */
 int lpa_degrees(lpa_graph* g, int32_t* deg_out);
 
@@ -350,8 +390,9 @@ int lpa_degrees(lpa_graph* g, int32_t* deg_out);
  * library's LPA_ABI_VERSION, so a binding can check the header it was built for.
  * ABI 7: lpa_graph_create_hostcoll, host_allgathers, the frozen unsized get_info.
  * ABI 8: lpa_components.
- * ABI 9: lpa_triangle_count. */
-#define LPA_ABI_VERSION 9
+ * ABI 9: lpa_triangle_count.
+ * ABI 10: lpa_pagerank. */
+#define LPA_ABI_VERSION 10
 int lpa_abi_version(void);
 int lpa_graph_get_info(const lpa_graph* g, lpa_graph_info* info);
 int lpa_graph_get_info_sized(const lpa_graph* g, lpa_graph_info* info, int64_t info_size);
