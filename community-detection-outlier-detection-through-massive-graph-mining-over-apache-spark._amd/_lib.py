@@ -110,6 +110,14 @@ class LpaPagerankSummary(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LpaSpSummary(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int64) for k in ("arcs", "reached", "max_distance", "batches", "push_levels",
+                                              "pull_levels")]
+
+    def to_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class LpaOutlierSummary(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in (
         "n_groups", "k", "threshold", "n_flagged", "n_communities", "n_communities_flagged",
@@ -154,6 +162,8 @@ SIGNATURES = {
     "lpa_triangle_count": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int32, ctypes.POINTER(LpaTriangleSummary)]),
     "lpa_pagerank": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _vp, _vp, _vp,
                                     ctypes.c_int32, ctypes.POINTER(LpaPagerankSummary)]),
+    "lpa_shortest_paths": (ctypes.c_int, [_vp, _i32p, ctypes.c_int32, _vp, ctypes.c_int32,
+                                          ctypes.POINTER(LpaSpSummary)]),
     "lpa_loopback_create": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(_vp)]),
     "lpa_loopback_abort": (None, [_vp]),
     "lpa_loopback_destroy": (None, [_vp]),

@@ -242,6 +242,8 @@ int create_common(int32_t device, hipStream_t stream, const int32_t* src, const 
   if (const char* f = getenv("LPA_TC_LDS")) g->tc_lds = atoi(f) < 0 ? 0 : atoi(f) > kTcLdsMax ? kTcLdsMax : atoi(f);
   if (const char* f = getenv("LPA_PR_SHORT")) g->pr_short = atoi(f) < 0 ? 0 : atoi(f);
   if (const char* f = getenv("LPA_PR_WAVE")) g->pr_wave = atoi(f) < 0 ? 0 : atoi(f);
+  if (const char* f = getenv("LPA_SP_ALPHA")) g->sp_alpha = atoi(f) < 0 ? 0 : atoi(f);
+  if (const char* f = getenv("LPA_SP_PULL")) g->sp_pull = atoi(f) == 1 ? 1 : 0;
   if (const char* f = getenv("LPA_CONV_STREAMS")) g->conv_streams = atoi(f) < 1 ? 1 : atoi(f) > 3 ? 3 : atoi(f);
   // internal builds (the outlier stage's L2 sub-graph): the locality order is a
   // gather-locality heuristic worth its two atomic passes only on a graph that runs
@@ -688,6 +690,38 @@ int lpa_pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, int32_t sour
   }
   LPA_HIP(hipSetDevice(g->device));
   return pagerank(g, max_iter, reset_prob, source, rank_out, out_degree_out, in_degree_out, out_is_device, summary);
+}
+
+int lpa_shortest_paths(lpa_graph* g, const int32_t* landmarks, int32_t n_landmarks, int32_t* dist_out,
+                       int32_t out_is_device, lpa_sp_summary* summary) {
+  if (!g) {
+    set_error("null handle");
+    return LPA_EINVAL;
+  }
+  if (n_landmarks < 0) {
+    set_error("lpa_shortest_paths: n_landmarks must not be negative, got %d", n_landmarks);
+    return LPA_EINVAL;
+  }
+  if (n_landmarks > 0 && !landmarks) {
+    set_error("lpa_shortest_paths: null landmarks");
+    return LPA_EINVAL;
+  }
+  for (int32_t i = 0; i < n_landmarks; ++i)
+    if (landmarks[i] < 0 || (int64_t)landmarks[i] >= g->V) {
+      set_error("lpa_shortest_paths: landmark %d (position %d) is not a vertex of [0, %lld)", landmarks[i], i,
+                (long long)g->V);
+      return LPA_EINVAL;
+    }
+  if (n_landmarks > 0 && !dist_out && g->V > 0) {
+    set_error("lpa_shortest_paths: null distance output");
+    return LPA_EINVAL;
+  }
+  if (g->m > 0 && !g->e_src) {
+    set_error("lpa_shortest_paths of a distributed job runs on rank 0 (the rank that keeps the edge list)");
+    return LPA_EINVAL;
+  }
+  LPA_HIP(hipSetDevice(g->device));
+  return shortest_paths(g, landmarks, n_landmarks, dist_out, out_is_device, summary);
 }
 
 int lpa_degrees(lpa_graph* g, int32_t* deg_out) {

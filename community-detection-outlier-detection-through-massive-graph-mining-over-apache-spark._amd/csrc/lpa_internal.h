@@ -89,6 +89,11 @@ constexpr int kTcLdsMax = 15360;      // a block per row, the list in 60 KB of L
 // PageRank (lpa_pr.hip): default in-list lengths of its row forms
 constexpr int kPrShort = 32;          // 8 lanes per row up to this length
 constexpr int kPrWave = 1024;         // a wave per row up to this length; longer: a block of 1024 per row
+// shortest paths (lpa_sp.hip): list lengths of its row forms (in-lists in the push, out-lists in
+// the pull) and the default of the push / pull switch
+constexpr int kSpShort = 32;          // 8 lanes per row up to this length
+constexpr int kSpWave = 1024;         // a wave per row up to this length; longer: a block of 1024 per row
+constexpr int kSpAlpha = 14;          // pull when the frontier's in-arcs exceed the unfinished out-arcs / this
 __host__ __device__ inline uint32_t col_class(int32_t c, uint32_t ncls) { return ((uint32_t)c >> 10) & (ncls - 1u); }
 
 struct Segment {   // one unit of a seg-bin row
@@ -379,6 +384,9 @@ struct lpa_graph {
   // wave form (longer: the block form); a row without in-edges always takes the short form
   int pr_short = lpa::kPrShort;             // LPA_PR_SHORT (>= 0; 0: no row with an in-edge takes the short form)
   int pr_wave = lpa::kPrWave;               // LPA_PR_WAVE  (>= 0; 0, or <= LPA_PR_SHORT: no row takes the wave form)
+  // shortest paths (lpa_sp.hip): the push / pull switch of a level
+  int sp_alpha = lpa::kSpAlpha;             // LPA_SP_ALPHA (>= 0; 0: never pull)
+  int sp_pull = 0;                          // LPA_SP_PULL=1: pull at every level
   int serial = 0;                           // LPA_SERIAL=1: all tally kernels on one stream (profiling)
   int use_graphs = 1;                       // LPA_GRAPHS=0: no captured superstep graphs
   // captured supersteps: [0, 4) converged per (cur, par); [4, 12) supersteps 2 and 3 per
@@ -560,5 +568,9 @@ int triangle_count(lpa_graph* g, int64_t* count_out, int64_t* simple_degree_out,
 // static PageRank of the directed multigraph (lpa_pr.hip)
 int pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, int32_t source, double* rank_out,
              int64_t* out_degree_out, int64_t* in_degree_out, int32_t out_is_device, lpa_pagerank_summary* summary);
+
+// landmark shortest paths of the directed graph (lpa_sp.hip); the landmarks are in [0, V)
+int shortest_paths(lpa_graph* g, const int32_t* landmarks, int32_t n_landmarks, int32_t* dist_out,
+                   int32_t out_is_device, lpa_sp_summary* summary);
 
 }  // namespace lpa

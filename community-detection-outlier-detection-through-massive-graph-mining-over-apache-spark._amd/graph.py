@@ -433,6 +433,49 @@ class Graph:
                                           ideg_ptr, on_dev, ctypes.byref(summ) if stats else None))
         return (rank, odeg, ideg, summ.to_dict()) if stats else rank
 
+    # -- shortest paths -------------------------------------------------------------
+    def shortest_paths(self, landmarks, out=None, stats: bool = False):
+        """Landmark shortest paths of the directed input graph (lpa_shortest_paths; GraphX
+        ``lib.ShortestPaths``): ``dist[l, v]`` is the number of edges on a shortest directed
+        path from v to ``landmarks[l]`` along src -> dst, 0 at the landmark, -1 where there is
+        none.  Duplicate edges and self-loops change nothing.  ``landmarks``: dense ids, a
+        landmark may repeat (equal rows).  Host int32 array of shape ``(len(landmarks),
+        num_vertices)`` by default, or written into the contiguous int32 device tensor ``out``
+        of that shape (this handle's device).  ``stats=True`` returns ``(dist, summary)``:
+        ``summary`` is a dict of arcs, reached, max_distance, batches, push_levels,
+        pull_levels.  The distances are identical across runs, handles, input edge orders
+        and push / pull schedules.  The labels and the LPA state are not touched."""
+        lms = list(landmarks) if not isinstance(landmarks, (str, bytes)) else [landmarks]
+        for x in lms:
+            if not isinstance(x, (int, np.integer)) or isinstance(x, (bool, np.bool_)):
+                raise TypeError(f"a landmark must be a dense vertex id (int), got {type(x).__name__}")
+        V = self.num_vertices
+        for x in lms:
+            if not 0 <= int(x) < V:
+                raise ValueError(f"landmark {int(x)} is not a vertex of [0, {V})")
+        n = len(lms)
+        lm = np.asarray(lms, dtype=np.int32).reshape(n)
+        if out is not None and _is_device_tensor(out):
+            import torch
+
+            if out.dtype != torch.int32:
+                raise ValueError(f"out must be int32, got {out.dtype}")
+            if out.device.index != self.device:
+                raise ValueError(f"out must be on cuda:{self.device}, got {out.device}")
+            if tuple(out.shape) != (n, V) or not out.is_contiguous():
+                raise ValueError(f"out must hold ({n}, {V}) contiguous entries")
+            dist, ptr, on_dev = out, out.data_ptr(), 1
+            torch.cuda.current_stream(out.device).synchronize()   # the library works on its own stream
+        elif out is not None:
+            raise ValueError("out must be an int32 device tensor")
+        else:
+            dist = np.empty((n, V), dtype=np.int32)
+            ptr, on_dev = dist.ctypes.data, 0
+        summ = _lib.LpaSpSummary()
+        _lib.check(self._lib.lpa_shortest_paths(self._handle(), lm.ctypes.data_as(_lib._i32p), n, ptr, on_dev,
+                                                ctypes.byref(summ) if stats else None))
+        return (dist, summ.to_dict()) if stats else dist
+
 
 class Loopback:
     """In-process collective group of ``nranks`` handles on one device (the

@@ -37,6 +37,7 @@ COMPONENT = "component"
 COUNT = "count"
 PAGERANK = "pagerank"
 WEIGHT = "weight"
+DISTANCES = "distances"
 CC_ALGORITHMS = ("graphframes", "graphx")
 
 
@@ -254,6 +255,50 @@ class GraphFrame:
         edf[WEIGHT] = 1.0 / odeg[ig.src].astype(np.float64)
         return GraphFrame(vdf, edf, device=self._device)
 
+    def _landmarks_dense(self, landmarks):
+        """(the landmarks as given, repeats collapsed; their dense ids); a TypeError when
+        ``landmarks`` is no list, tuple or array, a ValueError when one is no vertex id."""
+        if isinstance(landmarks, (str, bytes)) or not isinstance(landmarks, (list, tuple, np.ndarray)):
+            raise TypeError(f"landmarks must be a list, tuple or array of vertex ids, got {type(landmarks).__name__}")
+        if isinstance(landmarks, np.ndarray) and landmarks.ndim != 1:
+            raise TypeError(f"landmarks must be one-dimensional, got {landmarks.ndim} dimensions")
+        keys, dense = [], []
+        for lm in landmarks:
+            lm = lm.item() if isinstance(lm, np.generic) else lm
+            try:
+                pos = None if lm is None else self._source_dense(lm)
+            except ValueError:
+                pos = None
+            if pos is None:
+                # GraphFrames: NoSuchVertexException
+                raise ValueError(f"shortestPaths: landmark {lm!r} is not a vertex id")
+            if pos not in dense:
+                keys.append(lm)
+                dense.append(pos)
+        return keys, dense
+
+    def shortestPaths(self, landmarks) -> pd.DataFrame:
+        """``GraphFrame.shortestPaths(landmarks)`` (GraphX ``lib.ShortestPaths``): the vertex
+        rows (sorted by id, all columns kept) + ``distances``, an object column of dicts
+        ``{landmark id: distance}``: the number of edges on a shortest directed path from the
+        vertex to the landmark along src -> dst (0 at the landmark itself).  A landmark that
+        cannot be reached is absent from the dict, as in GraphFrames.  The keys are the
+        caller's own id values, in the order the landmarks were given, repeats collapsed.
+        ``landmarks`` must be a list, tuple or array; a landmark that is no vertex id raises
+        ``ValueError`` (GraphFrames: ``NoSuchVertexException``) before any device work; an
+        empty list gives ``{}`` for every vertex."""
+        keys, dense = self._landmarks_dense(landmarks)
+        ig = self._indexed()
+        V = ig.num_vertices
+        maps = np.empty(V, dtype=object)
+        if not keys:
+            for v in range(V):
+                maps[v] = {}
+        else:
+            dist = self._gpu_graph().shortest_paths(dense)
+            maps[:] = [{keys[l]: int(dist[l, v]) for l in np.flatnonzero(dist[:, v] >= 0)} for v in range(V)]
+        return _attach(self._v, ig, {DISTANCES: maps})
+
     def inDegrees(self) -> pd.DataFrame:
         """Vertices + ``inDegree`` (int64): the kept edges ending at each vertex, duplicates
         counted.  Every vertex has a row, with 0 where GraphFrames' property leaves the
@@ -324,6 +369,15 @@ def page_rank(vertices: pd.DataFrame, edges: pd.DataFrame, maxIter: int, resetPr
     gf = GraphFrame(vertices, edges, device=device)
     try:
         return gf.pageRank(resetProbability=resetProbability, sourceId=sourceId, maxIter=maxIter).vertices
+    finally:
+        gf.close()
+
+
+def shortest_paths(vertices: pd.DataFrame, edges: pd.DataFrame, landmarks, device: int = 0) -> pd.DataFrame:
+    """Function form of ``GraphFrame(vertices, edges).shortestPaths(landmarks)``."""
+    gf = GraphFrame(vertices, edges, device=device)
+    try:
+        return gf.shortestPaths(landmarks)
     finally:
         gf.close()
 

@@ -378,6 +378,42 @@ int lpa_pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, int32_t sour
                  double* rank_out, int64_t* out_degree_out, int64_t* in_degree_out,
                  int32_t out_is_device, lpa_pagerank_summary* summary);
 
+/*
+ * Landmark shortest paths (GraphX lib.ShortestPaths / GraphFrame.shortestPaths(landmarks))
+ * of the DIRECTED input graph: dist_out[l * V + v] is the number of edges on a shortest
+ * directed path from vertex v to landmarks[l] along src -> dst (GraphX sends its messages
+ * from dst to src: distances are TO the landmark), 0 at the landmark itself, -1 where no
+ * path exists.  Duplicate edges and self-loops change nothing; an edge with an end outside
+ * [0, V) is not an edge.  landmarks (dense ids) is always host memory; a landmark may repeat,
+ * its rows are then equal.  dist_out ([n_landmarks][V] row-major int32) is host memory unless
+ * out_is_device; summary is nullable.  n_landmarks == 0: success, nothing written, summary
+ * {arcs, 0, -1, 0, 0, 0} ({0, 0, -1, 0, 0, 0} with V == 0).  LPA_EINVAL for n_landmarks < 0,
+ * a null landmarks or (with V > 0) dist_out when n_landmarks > 0, a landmark outside [0, V).
+ * The call blocks until the work is done.  A multi-source breadth-first search over the
+ * reversed arcs, 64 landmarks to a pass (one bit each of a 64-bit word per vertex), every
+ * level either a push along the frontier's in-lists (64-bit atomic ORs) or a pull over the
+ * out-lists of the unfinished vertices (no atomics), chosen per level by Beamer's rule
+ * (DESIGN.md "Shortest paths").  OR commutes: the distances and every summary field but
+ * push_levels / pull_levels are a function of (V, edge set, landmarks) alone, identical
+ * across runs, handles, input edge orders and schedules; push_levels + pull_levels is the
+ * sum over the passes of (the pass's largest distance + 1).  All working memory is
+ * stream-ordered temporaries, the labels and every other piece of lpa_step's state are
+ * neither read nor written, nothing is kept on the handle.  On a distributed job
+ * (nranks > 1) only rank 0 keeps the edge list this needs; the other ranks return
+ * LPA_EINVAL.  Since ABI 11.
+ */
+typedef struct lpa_sp_summary {
+  int64_t arcs;         /* distinct directed non-loop arcs the search walks              */
+  int64_t reached;      /* finite (landmark, vertex) pairs, the landmarks themselves included */
+  int64_t max_distance; /* largest finite distance; -1 if n_landmarks == 0 or V == 0     */
+  int64_t batches;      /* passes of up to 64 landmarks = ceil(n_landmarks / 64)         */
+  int64_t push_levels;  /* levels expanded frontier -> predecessors (all batches)        */
+  int64_t pull_levels;  /* levels in which unfinished vertices scanned their out-lists   */
+} lpa_sp_summary;       /* 48 bytes */
+int lpa_shortest_paths(lpa_graph* g, const int32_t* landmarks /* host, dense ids */,
+                       int32_t n_landmarks, int32_t* dist_out /* [n_landmarks][V] row-major */,
+                       int32_t out_is_device, lpa_sp_summary* summary /* nullable */);
+
 /* Symmetrised degree of every vertex (dense ids), host output. */
 int lpa_degrees(lpa_graph* g, int32_t* deg_out);
 
@@ -391,8 +427,9 @@ int lpa_degrees(lpa_graph* g, int32_t* deg_out);
  * ABI 7: lpa_graph_create_hostcoll, host_allgathers, the frozen unsized get_info.
  * ABI 8: lpa_components.
  * ABI 9: lpa_triangle_count.
- * ABI 10: lpa_pagerank. */
-#define LPA_ABI_VERSION 10
+ * ABI 10: lpa_pagerank.
+ * ABI 11: lpa_shortest_paths. */
+#define LPA_ABI_VERSION 11
 int lpa_abi_version(void);
 int lpa_graph_get_info(const lpa_graph* g, lpa_graph_info* info);
 int lpa_graph_get_info_sized(const lpa_graph* g, lpa_graph_info* info, int64_t info_size);
