@@ -244,6 +244,8 @@ int create_common(int32_t device, hipStream_t stream, const int32_t* src, const 
   if (const char* f = getenv("LPA_PR_WAVE")) g->pr_wave = atoi(f) < 0 ? 0 : atoi(f);
   if (const char* f = getenv("LPA_SP_ALPHA")) g->sp_alpha = atoi(f) < 0 ? 0 : atoi(f);
   if (const char* f = getenv("LPA_SP_PULL")) g->sp_pull = atoi(f) == 1 ? 1 : 0;
+  if (const char* f = getenv("LPA_SCC_BLOCK"))
+    g->scc_block = atoi(f) < 0 ? 0 : atoi(f) > lpa::kSccTrimCap ? lpa::kSccTrimCap : atoi(f);
   if (const char* f = getenv("LPA_CONV_STREAMS")) g->conv_streams = atoi(f) < 1 ? 1 : atoi(f) > 3 ? 3 : atoi(f);
   // internal builds (the outlier stage's L2 sub-graph): the locality order is a
   // gather-locality heuristic worth its two atomic passes only on a graph that runs
@@ -722,6 +724,29 @@ int lpa_shortest_paths(lpa_graph* g, const int32_t* landmarks, int32_t n_landmar
   }
   LPA_HIP(hipSetDevice(g->device));
   return shortest_paths(g, landmarks, n_landmarks, dist_out, out_is_device, summary);
+}
+
+int lpa_strongly_connected_components(lpa_graph* g, int32_t max_iter, int32_t* comp_out, int32_t out_is_device,
+                                      int64_t* size_out, lpa_scc_summary* summary) {
+  if (!g) {
+    set_error("null handle");
+    return LPA_EINVAL;
+  }
+  if (max_iter <= 0) {
+    set_error("lpa_strongly_connected_components: max_iter must be greater than 0, got %d", max_iter);
+    return LPA_EINVAL;
+  }
+  if (!comp_out && g->V > 0) {
+    set_error("lpa_strongly_connected_components: null component output");
+    return LPA_EINVAL;
+  }
+  if (g->m > 0 && !g->e_src) {
+    set_error(
+        "lpa_strongly_connected_components of a distributed job runs on rank 0 (the rank that keeps the edge list)");
+    return LPA_EINVAL;
+  }
+  LPA_HIP(hipSetDevice(g->device));
+  return strongly_connected_components(g, max_iter, comp_out, out_is_device, size_out, summary);
 }
 
 int lpa_degrees(lpa_graph* g, int32_t* deg_out) {

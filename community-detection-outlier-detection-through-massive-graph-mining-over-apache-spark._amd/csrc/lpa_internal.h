@@ -94,6 +94,14 @@ constexpr int kPrWave = 1024;         // a wave per row up to this length; longe
 constexpr int kSpShort = 32;          // 8 lanes per row up to this length
 constexpr int kSpWave = 1024;         // a wave per row up to this length; longer: a block of 1024 per row
 constexpr int kSpAlpha = 14;          // pull when the frontier's in-arcs exceed the unfinished out-arcs / this
+// strongly connected components (lpa_scc.hip): list lengths of its row forms (out + in lists in the
+// trim, out-lists in the colour push, in-lists in the colour pull and the mark) and the in-block trim
+constexpr int kSccShort = 32;         // 8 lanes per row up to this length
+constexpr int kSccWave = 1024;        // a wave per row up to this length; longer: a block of 1024 per row
+constexpr int kSccTrimCap = 4096;     // vertices the in-block trim's LDS queue holds per level
+constexpr int kSccBlockTrim = 512;    // a trim level of at most this many vertices runs inside one block (measured:
+                                      //   1000 levels of 512 take 17.6 ms there, 24.9 ms as launches; of 1024, 34.5
+                                      //   against 31.9 ms; DESIGN.md "Strongly connected components")
 __host__ __device__ inline uint32_t col_class(int32_t c, uint32_t ncls) { return ((uint32_t)c >> 10) & (ncls - 1u); }
 
 struct Segment {   // one unit of a seg-bin row
@@ -387,6 +395,8 @@ struct lpa_graph {
   // shortest paths (lpa_sp.hip): the push / pull switch of a level
   int sp_alpha = lpa::kSpAlpha;             // LPA_SP_ALPHA (>= 0; 0: never pull)
   int sp_pull = 0;                          // LPA_SP_PULL=1: pull at every level
+  // strongly connected components (lpa_scc.hip): the largest trim level that runs inside one block
+  int scc_block = lpa::kSccBlockTrim;       // LPA_SCC_BLOCK (0 .. kSccTrimCap; 0: every level is a launch)
   int serial = 0;                           // LPA_SERIAL=1: all tally kernels on one stream (profiling)
   int use_graphs = 1;                       // LPA_GRAPHS=0: no captured superstep graphs
   // captured supersteps: [0, 4) converged per (cur, par); [4, 12) supersteps 2 and 3 per
@@ -572,5 +582,9 @@ int pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, int32_t source, 
 // landmark shortest paths of the directed graph (lpa_sp.hip); the landmarks are in [0, V)
 int shortest_paths(lpa_graph* g, const int32_t* landmarks, int32_t n_landmarks, int32_t* dist_out,
                    int32_t out_is_device, lpa_sp_summary* summary);
+
+// strongly connected components of the directed graph, GraphX's rounds (lpa_scc.hip)
+int strongly_connected_components(lpa_graph* g, int32_t max_iter, int32_t* comp_out, int32_t out_is_device,
+                                  int64_t* size_out, lpa_scc_summary* summary);
 
 }  // namespace lpa

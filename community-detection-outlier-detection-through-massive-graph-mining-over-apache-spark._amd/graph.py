@@ -476,6 +476,58 @@ class Graph:
                                                 ctypes.byref(summ) if stats else None))
         return (dist, summ.to_dict()) if stats else dist
 
+    # -- strongly connected components ------------------------------------------------
+    def strongly_connected_components(self, max_iter=None, out=None, sizes: bool = False):
+        """Strongly connected components of the directed input graph
+        (lpa_strongly_connected_components; GraphX ``lib.StronglyConnectedComponents``): at most
+        ``max_iter`` rounds of trim, forward colouring and backward sweep; ``None`` runs to
+        convergence.  Converged, ``comp[v]`` is the smallest dense id of v's SCC; stopped early,
+        a vertex whose SCC has not been written yet holds its own id (``max_iter=1`` gives the
+        identity), exactly as GraphX.  Duplicate edges change nothing; a self-loop changes only
+        the round in which its vertex leaves.  Host int32 array by default, or written into the
+        int32 device tensor ``out`` (this handle's device, ``num_vertices`` entries).
+        ``sizes=True`` returns ``(comp, sizes, summary)``: ``sizes[c]`` (int64, in the memory
+        ``comp`` is in) holds the member count at every component id c and 0 elsewhere;
+        ``summary`` is a dict of n_components, n_singletons, largest_size, largest_id, rounds,
+        trimmed, unresolved (0 exactly when converged).  The result is identical across runs,
+        handles, input edge orders and kernel schedules.  The labels and the LPA state are not
+        touched."""
+        if max_iter is None:
+            max_iter = 2 ** 31 - 1
+        if not isinstance(max_iter, (int, np.integer)) or isinstance(max_iter, (bool, np.bool_)):
+            raise TypeError(f"max_iter must be an int or None, got {type(max_iter).__name__}")
+        if max_iter <= 0:
+            raise ValueError(f"max_iter must be greater than 0, got {max_iter}")
+        max_iter = min(int(max_iter), 2 ** 31 - 1)
+        V = self.num_vertices
+        size = None
+        if out is not None and _is_device_tensor(out):
+            import torch
+
+            if out.dtype != torch.int32:
+                raise ValueError(f"out must be int32, got {out.dtype}")
+            if out.device.index != self.device:
+                raise ValueError(f"out must be on cuda:{self.device}, got {out.device}")
+            if out.numel() != V or not out.is_contiguous():
+                raise ValueError(f"out must hold {V} contiguous entries")
+            comp, ptr, on_dev = out, out.data_ptr(), 1
+            if sizes:
+                size = torch.empty(V, dtype=torch.int64, device=out.device)
+            torch.cuda.current_stream(out.device).synchronize()   # the library works on its own stream
+            size_ptr = size.data_ptr() if sizes else None
+        elif out is not None:
+            raise ValueError("out must be an int32 device tensor")
+        else:
+            comp = np.empty(V, dtype=np.int32)
+            ptr, on_dev = comp.ctypes.data, 0
+            if sizes:
+                size = np.empty(V, dtype=np.int64)
+            size_ptr = size.ctypes.data if sizes else None
+        summ = _lib.LpaSccSummary()
+        _lib.check(self._lib.lpa_strongly_connected_components(self._handle(), max_iter, ptr, on_dev, size_ptr,
+                                                               ctypes.byref(summ) if sizes else None))
+        return (comp, size, summ.to_dict()) if sizes else comp
+
 
 class Loopback:
     """In-process collective group of ``nranks`` handles on one device (the

@@ -67,6 +67,15 @@ def _check_page_rank(resetProbability, maxIter, tol):
             f"requirement failed: Random reset probability must belong to [0, 1], but got {resetProbability}")
 
 
+def _check_scc_max_iter(maxIter):
+    """The argument check of GraphFrame.stronglyConnectedComponents, before any device work."""
+    if not isinstance(maxIter, (int, np.integer)) or isinstance(maxIter, (bool, np.bool_)):
+        raise TypeError(f"maxIter must be an int, got {type(maxIter).__name__}")
+    if maxIter <= 0:
+        # GraphX StronglyConnectedComponents.run: require(numIter > 0, ...)
+        raise ValueError(f"requirement failed: Number of iterations must be greater than 0, but got {maxIter}")
+
+
 def _check_cc_algorithm(algorithm):
     if algorithm not in CC_ALGORITHMS:
         # graphframes.lib.ConnectedComponents.setAlgorithm: require(supportedAlgorithms.contains(value), ...)
@@ -193,6 +202,20 @@ class GraphFrame:
         _check_cc_algorithm(algorithm)
         ig = self._indexed()
         dense = self._gpu_graph().components()
+        return _attach(self._v, ig, {COMPONENT: _label_values(ig, dense)})
+
+    def stronglyConnectedComponents(self, maxIter: int) -> pd.DataFrame:
+        """``GraphFrame.stronglyConnectedComponents(maxIter)`` (GraphX
+        ``lib.StronglyConnectedComponents``): vertices + ``component`` (int64).  Once the
+        rounds have converged it is the smallest member of each vertex's strongly connected
+        component -- its original id for integral ids (the value GraphFrames returns), its
+        dense index in ascending id order otherwise, as for ``label``.  ``maxIter`` bounds
+        GraphX's rounds (trim, forward colouring, backward sweep) and the result when it stops
+        them early is GraphX's too: a vertex whose component has not been written yet holds
+        its own id.  ``maxIter`` is required, as in GraphFrames."""
+        _check_scc_max_iter(maxIter)
+        ig = self._indexed()
+        dense = self._gpu_graph().strongly_connected_components(int(maxIter))
         return _attach(self._v, ig, {COMPONENT: _label_values(ig, dense)})
 
     def triangleCount(self) -> pd.DataFrame:
@@ -349,6 +372,17 @@ def connected_components(vertices: pd.DataFrame, edges: pd.DataFrame, device: in
     gf = GraphFrame(vertices, edges, device=device)
     try:
         return gf.connectedComponents()
+    finally:
+        gf.close()
+
+
+def strongly_connected_components(vertices: pd.DataFrame, edges: pd.DataFrame, maxIter: int,
+                                  device: int = 0) -> pd.DataFrame:
+    """Function form of ``GraphFrame(vertices, edges).stronglyConnectedComponents(maxIter)``."""
+    _check_scc_max_iter(maxIter)
+    gf = GraphFrame(vertices, edges, device=device)
+    try:
+        return gf.stronglyConnectedComponents(maxIter)
     finally:
         gf.close()
 

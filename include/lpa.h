@@ -414,6 +414,53 @@ int lpa_shortest_paths(lpa_graph* g, const int32_t* landmarks /* host, dense ids
                        int32_t n_landmarks, int32_t* dist_out /* [n_landmarks][V] row-major */,
                        int32_t out_is_device, lpa_sp_summary* summary /* nullable */);
 
+/*
+ * Strongly connected components (GraphX lib.StronglyConnectedComponents /
+ * GraphFrame.stronglyConnectedComponents(maxIter)) of the DIRECTED input graph.  Duplicate
+ * edges change nothing; an edge with an end outside [0, V) is not an edge; a self-loop is kept
+ * as a fact about its vertex: it never changes the converged result, but it does change the
+ * round in which the vertex leaves.  GraphX's rounds, restated:
+ *   state   comp[v] = v, every vertex alive, none marked, rounds = 0
+ *   round   while a vertex is alive and rounds < max_iter: ++rounds, then
+ *     1. write  every marked v: comp[v] = colour[v], v leaves; none marked
+ *     2. trim   to the fixpoint: every alive v without an arc to an alive vertex or without an
+ *               arc from one leaves, keeping comp[v] = v (a self-loop counts as both: such a
+ *               vertex is never trimmed)
+ *     3. only if rounds < max_iter:
+ *        colour  colour[v] = the smallest alive u (v included) with a directed path u -> v
+ *                inside the alive subgraph
+ *        mark    every v with colour[v] == v, and every v that reaches such a root of its own
+ *                colour through arcs whose ends both carry that colour: whole SCCs, each
+ *                coloured by its smallest member
+ * Converged (summary.unresolved == 0): comp_out[v], by dense id, is the SMALLEST dense id of
+ * v's SCC, for integral ids the value GraphFrames returns.  Stopped early by max_iter, a
+ * vertex whose SCC has not been written yet holds its own id; max_iter = 1 gives the identity
+ * (GraphX's behaviour).  Every step is a unique fixpoint: comp_out and every summary field are
+ * functions of (V, arc set, loop set, max_iter) alone, identical across runs, handles, input
+ * edge orders and kernel schedules.  size_out (nullable, V entries): size_out[c] = the vertices
+ * with comp_out == c, 0 at every other index.  Both arrays are host memory unless
+ * out_is_device; summary is nullable.  V == 0: success, nothing written, summary
+ * {0, 0, 0, -1, 0, 0, 0}.  LPA_EINVAL for max_iter <= 0 and for a null comp_out with V > 0.
+ * The call blocks until the work is done.  Counter-driven peeling for the trim, a
+ * label-correcting atomicMin propagation for the colours, a backward breadth-first search for
+ * the marks (DESIGN.md "Strongly connected components").  All working memory is stream-ordered
+ * temporaries, the labels and every other piece of lpa_step's state are neither read nor
+ * written, nothing is kept on the handle.  On a distributed job (nranks > 1) only rank 0 keeps
+ * the edge list this needs; the other ranks return LPA_EINVAL.  Since ABI 12.
+ */
+typedef struct lpa_scc_summary {
+  int64_t n_components;  /* distinct values of comp_out                                  */
+  int64_t n_singletons;  /* values held by exactly one vertex                            */
+  int64_t largest_size;  /* 0 if V == 0                                                   */
+  int64_t largest_id;    /* smallest id on a tie; -1 if V == 0                            */
+  int64_t rounds;        /* rounds entered                                                */
+  int64_t trimmed;       /* vertices removed by step 2, all rounds                        */
+  int64_t unresolved;    /* vertices still alive at return (0 <=> converged)              */
+} lpa_scc_summary;       /* 56 bytes */
+int lpa_strongly_connected_components(lpa_graph* g, int32_t max_iter, int32_t* comp_out,
+                                      int32_t out_is_device, int64_t* size_out /* nullable, as lpa_components */,
+                                      lpa_scc_summary* summary /* nullable */);
+
 /* Symmetrised degree of every vertex (dense ids), host output. */
 int lpa_degrees(lpa_graph* g, int32_t* deg_out);
 
@@ -428,8 +475,9 @@ int lpa_degrees(lpa_graph* g, int32_t* deg_out);
  * ABI 8: lpa_components.
  * ABI 9: lpa_triangle_count.
  * ABI 10: lpa_pagerank.
- * ABI 11: lpa_shortest_paths. */
-#define LPA_ABI_VERSION 11
+ * ABI 11: lpa_shortest_paths.
+ * ABI 12: lpa_strongly_connected_components. */
+#define LPA_ABI_VERSION 12
 int lpa_abi_version(void);
 int lpa_graph_get_info(const lpa_graph* g, lpa_graph_info* info);
 int lpa_graph_get_info_sized(const lpa_graph* g, lpa_graph_info* info, int64_t info_size);
