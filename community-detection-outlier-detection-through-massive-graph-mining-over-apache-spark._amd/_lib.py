@@ -110,6 +110,15 @@ class LpaPagerankSummary(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LpaPprSummary(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int64) for k in ("edges", "sinks", "max_in_degree", "batches", "batch_width",
+                                              "nonzero")] + [("rank_sum_min", ctypes.c_double),
+                                                             ("rank_sum_max", ctypes.c_double)]
+
+    def to_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class LpaSpSummary(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in ("arcs", "reached", "max_distance", "batches", "push_levels",
                                               "pull_levels")]
@@ -170,6 +179,8 @@ SIGNATURES = {
     "lpa_triangle_count": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int32, ctypes.POINTER(LpaTriangleSummary)]),
     "lpa_pagerank": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _vp, _vp, _vp,
                                     ctypes.c_int32, ctypes.POINTER(LpaPagerankSummary)]),
+    "lpa_parallel_pagerank": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_double, _i32p, ctypes.c_int32, _vp,
+                                             ctypes.c_int32, _vp, ctypes.POINTER(LpaPprSummary)]),
     "lpa_shortest_paths": (ctypes.c_int, [_vp, _i32p, ctypes.c_int32, _vp, ctypes.c_int32,
                                           ctypes.POINTER(LpaSpSummary)]),
     "lpa_strongly_connected_components": (ctypes.c_int, [_vp, ctypes.c_int32, _vp, ctypes.c_int32, _vp,

@@ -242,6 +242,10 @@ int create_common(int32_t device, hipStream_t stream, const int32_t* src, const 
   if (const char* f = getenv("LPA_TC_LDS")) g->tc_lds = atoi(f) < 0 ? 0 : atoi(f) > kTcLdsMax ? kTcLdsMax : atoi(f);
   if (const char* f = getenv("LPA_PR_SHORT")) g->pr_short = atoi(f) < 0 ? 0 : atoi(f);
   if (const char* f = getenv("LPA_PR_WAVE")) g->pr_wave = atoi(f) < 0 ? 0 : atoi(f);
+  if (const char* f = getenv("LPA_PPR_BATCH")) {
+    const int b = atoi(f);
+    g->ppr_batch = b == 4 || b == 8 || b == 16 ? b : lpa::kPprBatch;
+  }
   if (const char* f = getenv("LPA_SP_ALPHA")) g->sp_alpha = atoi(f) < 0 ? 0 : atoi(f);
   if (const char* f = getenv("LPA_SP_PULL")) g->sp_pull = atoi(f) == 1 ? 1 : 0;
   if (const char* f = getenv("LPA_SCC_BLOCK"))
@@ -692,6 +696,48 @@ int lpa_pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, int32_t sour
   }
   LPA_HIP(hipSetDevice(g->device));
   return pagerank(g, max_iter, reset_prob, source, rank_out, out_degree_out, in_degree_out, out_is_device, summary);
+}
+
+int lpa_parallel_pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, const int32_t* sources,
+                          int32_t n_sources, double* rank_out, int32_t out_is_device, double* rank_sum_out,
+                          lpa_ppr_summary* summary) {
+  if (!g) {
+    set_error("null handle");
+    return LPA_EINVAL;
+  }
+  if (max_iter <= 0) {
+    set_error("lpa_parallel_pagerank: max_iter must be greater than 0, got %d", max_iter);
+    return LPA_EINVAL;
+  }
+  if (!(reset_prob >= 0.0 && reset_prob <= 1.0)) {   // NaN fails both
+    set_error("lpa_parallel_pagerank: reset_prob must belong to [0, 1], got %g", reset_prob);
+    return LPA_EINVAL;
+  }
+  if (n_sources < 0) {
+    set_error("lpa_parallel_pagerank: n_sources must not be negative, got %d", n_sources);
+    return LPA_EINVAL;
+  }
+  if (n_sources > 0 && !sources) {
+    set_error("lpa_parallel_pagerank: null sources");
+    return LPA_EINVAL;
+  }
+  for (int32_t i = 0; i < n_sources; ++i)
+    if (sources[i] < 0 || (int64_t)sources[i] >= g->V) {
+      set_error("lpa_parallel_pagerank: source %d (position %d) is not a vertex of [0, %lld)", sources[i], i,
+                (long long)g->V);
+      return LPA_EINVAL;
+    }
+  if (n_sources > 0 && !rank_out && g->V > 0) {
+    set_error("lpa_parallel_pagerank: null rank output");
+    return LPA_EINVAL;
+  }
+  if (g->m > 0 && !g->e_src) {
+    set_error("lpa_parallel_pagerank of a distributed job runs on rank 0 (the rank that keeps the edge list)");
+    return LPA_EINVAL;
+  }
+  LPA_HIP(hipSetDevice(g->device));
+  return parallel_pagerank(g, max_iter, reset_prob, sources, n_sources, rank_out, out_is_device, rank_sum_out,
+                           summary);
 }
 
 int lpa_shortest_paths(lpa_graph* g, const int32_t* landmarks, int32_t n_landmarks, int32_t* dist_out,

@@ -89,6 +89,8 @@ constexpr int kTcLdsMax = 15360;      // a block per row, the list in 60 KB of L
 // PageRank (lpa_pr.hip): default in-list lengths of its row forms
 constexpr int kPrShort = 32;          // 8 lanes per row up to this length
 constexpr int kPrWave = 1024;         // a wave per row up to this length; longer: a block of 1024 per row
+// parallel personalized PageRank (lpa_ppr.hip): sources to a pass (4, 8 or 16)
+constexpr int kPprBatch = 16;         // the default (DESIGN.md "Parallel personalized PageRank": the measured table)
 // shortest paths (lpa_sp.hip): list lengths of its row forms (in-lists in the push, out-lists in
 // the pull) and the default of the push / pull switch
 constexpr int kSpShort = 32;          // 8 lanes per row up to this length
@@ -392,6 +394,8 @@ struct lpa_graph {
   // wave form (longer: the block form); a row without in-edges always takes the short form
   int pr_short = lpa::kPrShort;             // LPA_PR_SHORT (>= 0; 0: no row with an in-edge takes the short form)
   int pr_wave = lpa::kPrWave;               // LPA_PR_WAVE  (>= 0; 0, or <= LPA_PR_SHORT: no row takes the wave form)
+  // parallel personalized PageRank (lpa_ppr.hip): sources to a pass
+  int ppr_batch = lpa::kPprBatch;           // LPA_PPR_BATCH (4, 8 or 16; anything else: the default)
   // shortest paths (lpa_sp.hip): the push / pull switch of a level
   int sp_alpha = lpa::kSpAlpha;             // LPA_SP_ALPHA (>= 0; 0: never pull)
   int sp_pull = 0;                          // LPA_SP_PULL=1: pull at every level
@@ -575,9 +579,38 @@ int components(lpa_graph* g, int32_t* comp_out, int32_t out_is_device, int64_t* 
 int triangle_count(lpa_graph* g, int64_t* count_out, int64_t* simple_degree_out, int32_t out_is_device,
                    lpa_triangle_summary* summary);
 
+// The in-list CSR of the directed multigraph as the PageRank calls walk it (lpa_pr.hip
+// pr_build; lpa_pr.hip's header describes the stages): every array is a stream-ordered
+// temporary on the handle's stream, released by the destructor.
+struct PrCsr {
+  hipStream_t s = nullptr;
+  int64_t* op = nullptr;     // [V + 1] the first edge of every source in source order: outdeg[u] = op[u + 1] - op[u]
+  int64_t* rp = nullptr;     // [V + 1] row offsets (rp[V] = E): indeg[v] = rp[v + 1] - rp[v]
+  int32_t* col = nullptr;    // [E] the slot of every in-edge's source, a row ascending
+  int32_t* slot = nullptr;   // [V] the vertex's slot in c[]: its rank in (outdeg descending, id) order
+  double* w = nullptr;       // [V] 1.0 / outdeg, 0.0 for a sink
+  int32_t* lists = nullptr;  // [2 V] the wave-form rows, ascending; at + V the block-form rows
+  int64_t E = 0;             // kept edges
+  uint32_t n_wave = 0, n_block = 0;   // the lists' lengths
+  uint32_t sinks = 0, max_in = 0;     // vertices without an out-edge; the longest in-list
+  void* ptrs[8] = {};
+  int n = 0;
+  PrCsr() = default;
+  PrCsr(const PrCsr&) = delete;
+  PrCsr& operator=(const PrCsr&) = delete;
+  ~PrCsr();
+};
+// keys, two-stage sort, slots, rows, w, the form lists (boundaries g->pr_short / g->pr_wave)
+// and the counters, for V > 0; reads V, m, e_src / e_dst and the stream, synchronises it once
+int pr_build(lpa_graph* g, PrCsr* b);
+
 // static PageRank of the directed multigraph (lpa_pr.hip)
 int pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, int32_t source, double* rank_out,
              int64_t* out_degree_out, int64_t* in_degree_out, int32_t out_is_device, lpa_pagerank_summary* summary);
+
+// personalised PageRank from n_sources sources at once (lpa_ppr.hip); the sources are in [0, V)
+int parallel_pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, const int32_t* sources, int32_t n_sources,
+                      double* rank_out, int32_t out_is_device, double* rank_sum_out, lpa_ppr_summary* summary);
 
 // landmark shortest paths of the directed graph (lpa_sp.hip); the landmarks are in [0, V)
 int shortest_paths(lpa_graph* g, const int32_t* landmarks, int32_t n_landmarks, int32_t* dist_out,

@@ -21,6 +21,8 @@
 //            r[v] = base(v) + (1 - a) s[v], c'[slot[v]] = r[v] w[v]; c double-buffered
 //   finish   S = sum r (per-block partials of a fixed grid, then one block), r *= V / S
 //            (with a source: r /= S); summary in two block-reduced passes
+// keys .. rows with w, the form lists and the counters are pr_build(), which the parallel
+// personalized call (lpa_ppr.hip) shares; iterate and finish are this file's own.
 //
 // Row forms, by in-degree L (boundaries: lpa_graph::pr_short / pr_wave):
 //   short   L <= pr_short   8 lanes per row, 32 rows per block, rows in id order (rp, w, r
@@ -122,22 +124,16 @@ __global__ __launch_bounds__(256) void k_pr_col(const u64* __restrict__ keys, in
   GRID_STRIDE(i, E) col[i] = (int32_t)(u32)keys[i];
 }
 
-// w, r0, c0 of every vertex and its form flags (fw: a wave row, fb: a block row); cnt[0]
-// the longest in-list, cnt[1] the sinks (two atomics per wave, at its end)
-__global__ __launch_bounds__(256) void k_pr_init(const int64_t* __restrict__ op, const int64_t* __restrict__ rp,
-                                                 int64_t V, int32_t source, int64_t short_max, int64_t wave_max,
-                                                 const int32_t* __restrict__ slot, double* __restrict__ w,
-                                                 double* __restrict__ r, double* __restrict__ c,
-                                                 uint8_t* __restrict__ fw, uint8_t* __restrict__ fb,
-                                                 u32* __restrict__ cnt) {
+// w of every vertex and its form flags (fw: a wave row, fb: a block row); cnt[0] the
+// longest in-list, cnt[1] the sinks (two atomics per wave, at its end)
+__global__ __launch_bounds__(256) void k_pr_rows(const int64_t* __restrict__ op, const int64_t* __restrict__ rp,
+                                                 int64_t V, int64_t short_max, int64_t wave_max,
+                                                 double* __restrict__ w, uint8_t* __restrict__ fw,
+                                                 uint8_t* __restrict__ fb, u32* __restrict__ cnt) {
   u32 lmax = 0, sinks = 0;
   GRID_STRIDE(v, V) {
     const int64_t o = op[v + 1] - op[v], L = rp[v + 1] - rp[v];
-    const double wv = o == 0 ? 0.0 : 1.0 / (double)o;
-    const double rv = source < 0 || v == (int64_t)source ? 1.0 : 0.0;
-    w[v] = wv;
-    r[v] = rv;
-    c[slot[v]] = rv * wv;
+    w[v] = o == 0 ? 0.0 : 1.0 / (double)o;
     fw[v] = L > short_max && L <= wave_max ? 1 : 0;   // short_max >= 0: L = 0 is in neither list
     fb[v] = L > short_max && L > wave_max ? 1 : 0;
     sinks += o == 0 ? 1u : 0u;
@@ -151,6 +147,17 @@ __global__ __launch_bounds__(256) void k_pr_init(const int64_t* __restrict__ op,
   if ((threadIdx.x & 63) == 0) {
     if (lmax) atomicMax(&cnt[0], lmax);
     if (sinks) atomicAdd(&cnt[1], sinks);
+  }
+}
+
+// r0 and c0 of every vertex
+__global__ __launch_bounds__(256) void k_pr_start(int64_t V, int32_t source, const double* __restrict__ w,
+                                                  const int32_t* __restrict__ slot, double* __restrict__ r,
+                                                  double* __restrict__ c) {
+  GRID_STRIDE(v, V) {
+    const double rv = source < 0 || v == (int64_t)source ? 1.0 : 0.0;
+    r[v] = rv;
+    c[slot[v]] = rv * w[v];
   }
 }
 
@@ -372,46 +379,48 @@ inline unsigned grid_rows(int64_t nrows, int per_block, int64_t cap) {
 
 }  // namespace
 
-// Reads V, m, e_src / e_dst, the stream and the pr_* boundaries of the handle, nothing of
-// the LPA state; every array is a stream-ordered temporary.
-int pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, int32_t source, double* rank_out,
-             int64_t* out_degree_out, int64_t* in_degree_out, int32_t out_is_device, lpa_pagerank_summary* summary) {
+PrCsr::~PrCsr() {
+  for (int i = 0; i < n; ++i) tmp_free(ptrs[i], s);
+}
+
+// The build half of a PageRank call.  Reads V (> 0), m, e_src / e_dst, the stream and the
+// pr_* boundaries of the handle, nothing of the LPA state; the arrays of *b outlive the call,
+// everything else is freed in stream order before it returns.
+int pr_build(lpa_graph* g, PrCsr* b) {
   hipStream_t s = g->stream;
   const int64_t V = g->V, m = g->m;
-  if (summary) *summary = lpa_pagerank_summary{0.0, 0.0, -1, 0, 0, 0};
-  if (V == 0) return LPA_OK;
+  b->s = s;
+  const auto keep = [&](auto** p, int64_t count) {
+    LPA_TRY(tmp_alloc((void**)p, sizeof(**p) * (size_t)(count > 0 ? count : 1), s));
+    b->ptrs[b->n++] = *p;
+    return (int)LPA_OK;
+  };
   Tmp tmp(s);
   u32 *cnt = nullptr, *pw = nullptr, *pb = nullptr;
-  int64_t *op = nullptr, *rp = nullptr;
-  int32_t *col = nullptr, *lists = nullptr;
   uint8_t *fw = nullptr, *fb = nullptr;
-  double *w = nullptr, *r = rank_out, *c[2] = {nullptr, nullptr};
-  LPA_TRY(tmp.get(&op, V + 1));
-  LPA_TRY(tmp.get(&rp, V + 1));
-  LPA_TRY(tmp.get(&lists, 2 * V));
+  LPA_TRY(keep(&b->op, V + 1));
+  LPA_TRY(keep(&b->rp, V + 1));
+  LPA_TRY(keep(&b->lists, 2 * V));
   LPA_TRY(tmp.get(&cnt, 2));
   LPA_TRY(tmp.get(&fw, V));
   LPA_TRY(tmp.get(&fb, V));
   LPA_TRY(tmp.get(&pw, V + 1));
   LPA_TRY(tmp.get(&pb, V + 1));
-  LPA_TRY(tmp.get(&w, V));
-  if (!out_is_device) LPA_TRY(tmp.get(&r, V));
-  LPA_TRY(tmp.get(&c[0], V));
-  LPA_TRY(tmp.get(&c[1], V));
+  LPA_TRY(keep(&b->w, V));
   LPA_HIP(hipMemsetAsync(cnt, 0, sizeof(u32) * 2, s));
-  // ---- build ----
+  int64_t *op = b->op, *rp = b->rp;
   u64* keys = nullptr;   // [2 m]: the keys and the sort's other buffer
   u64* ok = nullptr;     // [2 V]: the vertex order's keys and their sort's other buffer
-  int32_t* slot = nullptr;
   LPA_TRY(tmp.get(&ok, 2 * V));
-  LPA_TRY(tmp.get(&slot, V));
+  LPA_TRY(keep(&b->slot, V));
+  int32_t* slot = b->slot;
   // the halves hold values up to V (a dropped edge); the sort is stable, so the passes
   // over the high half keep the source order inside every row
   const int bits = bits_for((uint64_t)V);
   int lo[4], hi[4], ns = 0;
-  for (int b = 0; b < bits; b += 8, ++ns) {
-    lo[ns] = b;
-    hi[ns] = 32 + b;
+  for (int bit = 0; bit < bits; bit += 8, ++ns) {
+    lo[ns] = bit;
+    hi[ns] = 32 + bit;
   }
   if (m > 0) {
     LPA_TRY(tmp.get(&keys, 2 * m));
@@ -438,25 +447,50 @@ int pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, int32_t source, 
   } else {
     LPA_HIP(hipMemsetAsync(rp, 0, sizeof(int64_t) * (size_t)(V + 1), s));
   }
-  hipLaunchKernelGGL(k_pr_init, dim3(grid_bh(V)), dim3(256), 0, s, op, rp, V, source, (int64_t)g->pr_short,
-                     (int64_t)g->pr_wave, slot, w, r, c[0], fw, fb, cnt);
+  hipLaunchKernelGGL(k_pr_rows, dim3(grid_bh(V)), dim3(256), 0, s, op, rp, V, (int64_t)g->pr_short,
+                     (int64_t)g->pr_wave, b->w, fw, fb, cnt);
   LPA_HIP(hipGetLastError());
   LPA_TRY(exclusive_scan_u8_u32(fw, pw, V, s));
   LPA_TRY(exclusive_scan_u8_u32(fb, pb, V, s));
-  hipLaunchKernelGGL(k_pr_lists, dim3(grid_for(V)), dim3(256), 0, s, fw, fb, pw, pb, V, lists);
+  hipLaunchKernelGGL(k_pr_lists, dim3(grid_for(V)), dim3(256), 0, s, fw, fb, pw, pb, V, b->lists);
   LPA_HIP(hipGetLastError());
-  int64_t E = 0;
-  u32 h[2] = {0, 0}, hc[2] = {0, 0};   // the list lengths; the longest in-list and the sinks
-  LPA_HIP(hipMemcpyAsync(&E, rp + V, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  LPA_HIP(hipMemcpyAsync(&h[0], pw + V, sizeof(u32), hipMemcpyDeviceToHost, s));
-  LPA_HIP(hipMemcpyAsync(&h[1], pb + V, sizeof(u32), hipMemcpyDeviceToHost, s));
+  u32 hc[2] = {0, 0};   // the longest in-list and the sinks
+  LPA_HIP(hipMemcpyAsync(&b->E, rp + V, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  LPA_HIP(hipMemcpyAsync(&b->n_wave, pw + V, sizeof(u32), hipMemcpyDeviceToHost, s));
+  LPA_HIP(hipMemcpyAsync(&b->n_block, pb + V, sizeof(u32), hipMemcpyDeviceToHost, s));
   LPA_HIP(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, s));
   LPA_HIP(hipStreamSynchronize(s));
-  LPA_TRY(tmp.get(&col, E));
-  if (E > 0) {
-    hipLaunchKernelGGL(k_pr_col, dim3(grid_for(E)), dim3(256), 0, s, keys, E, col);
+  b->max_in = hc[0];
+  b->sinks = hc[1];
+  LPA_TRY(keep(&b->col, b->E));
+  if (b->E > 0) {
+    hipLaunchKernelGGL(k_pr_col, dim3(grid_for(b->E)), dim3(256), 0, s, keys, b->E, b->col);
     LPA_HIP(hipGetLastError());
   }
+  return LPA_OK;
+}
+
+// Every array is a stream-ordered temporary.
+int pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, int32_t source, double* rank_out,
+             int64_t* out_degree_out, int64_t* in_degree_out, int32_t out_is_device, lpa_pagerank_summary* summary) {
+  hipStream_t s = g->stream;
+  const int64_t V = g->V;
+  if (summary) *summary = lpa_pagerank_summary{0.0, 0.0, -1, 0, 0, 0};
+  if (V == 0) return LPA_OK;
+  PrCsr csr;
+  LPA_TRY(pr_build(g, &csr));
+  const int64_t *op = csr.op, *rp = csr.rp;
+  const int32_t *col = csr.col, *lists = csr.lists, *slot = csr.slot;
+  const double* w = csr.w;
+  const int64_t E = csr.E;
+  const u32 h[2] = {csr.n_wave, csr.n_block}, hc[2] = {csr.max_in, csr.sinks};
+  Tmp tmp(s);
+  double *r = rank_out, *c[2] = {nullptr, nullptr};
+  if (!out_is_device) LPA_TRY(tmp.get(&r, V));
+  LPA_TRY(tmp.get(&c[0], V));
+  LPA_TRY(tmp.get(&c[1], V));
+  hipLaunchKernelGGL(k_pr_start, dim3(grid_for(V)), dim3(256), 0, s, V, source, w, slot, r, c[0]);
+  LPA_HIP(hipGetLastError());
   // ---- iterate ----
   const Update up{reset_prob, 1.0 - reset_prob, source, w, slot};
   const unsigned g_short = grid_rows(V, 256 / kShortLanes, 65536);

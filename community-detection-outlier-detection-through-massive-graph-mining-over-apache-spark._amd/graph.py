@@ -433,6 +433,60 @@ class Graph:
                                           ideg_ptr, on_dev, ctypes.byref(summ) if stats else None))
         return (rank, odeg, ideg, summ.to_dict()) if stats else rank
 
+    # -- parallel personalized PageRank -------------------------------------------------
+    def parallel_pagerank(self, sources, max_iter: int, reset_prob: float = 0.15, out=None, stats: bool = False):
+        """Personalised PageRank from every one of ``sources`` (dense ids) in one call
+        (lpa_parallel_pagerank; GraphX ``PageRank.runParallelPersonalizedPageRank``): row l of
+        the result is what ``pagerank(max_iter, reset_prob, source=sources[l])`` specifies, each
+        row summing to 1.  The in-list CSR is built once and the sources run ``batch_width`` to a
+        pass (``LPA_PPR_BATCH`` = 4, 8 or 16 when the handle is created), one gathered in-edge
+        serving the whole pass.  A source may repeat: its rows are then equal (GraphX keeps
+        only the last of a repeat and returns 0 / 0 for the earlier ones; that accident is not
+        reproduced).  Host float64 array of shape ``(len(sources), num_vertices)`` by default,
+        or written into the contiguous float64 device tensor ``out`` of that shape (this
+        handle's device).  ``stats=True`` returns ``(ranks, rank_sums, summary)``:
+        ``rank_sums[l]`` (host float64) is row l's sum before normalisation, ``summary`` a dict
+        of edges, sinks, max_in_degree, batches, batch_width, nonzero, rank_sum_min,
+        rank_sum_max.  A row is bit-identical across runs, handles, input edge orders, the
+        position of its source in ``sources`` and whatever other sources share the call; it
+        agrees with ``pagerank``'s personalised ranks within that call's bound, not bit for
+        bit.  The labels and the LPA state are not touched."""
+        if not isinstance(max_iter, (int, np.integer)) or isinstance(max_iter, (bool, np.bool_)):
+            raise TypeError(f"max_iter must be an int, got {type(max_iter).__name__}")
+        srcs = list(sources) if not isinstance(sources, (str, bytes)) else [sources]
+        for x in srcs:
+            if not isinstance(x, (int, np.integer)) or isinstance(x, (bool, np.bool_)):
+                raise TypeError(f"a source must be a dense vertex id (int), got {type(x).__name__}")
+        V = self.num_vertices
+        for x in srcs:
+            if not 0 <= int(x) < V:
+                raise ValueError(f"source {int(x)} is not a vertex of [0, {V})")
+        n = len(srcs)
+        sv = np.asarray(srcs, dtype=np.int32).reshape(n)
+        if out is not None and _is_device_tensor(out):
+            import torch
+
+            if out.dtype != torch.float64:
+                raise ValueError(f"out must be float64, got {out.dtype}")
+            if out.device.index != self.device:
+                raise ValueError(f"out must be on cuda:{self.device}, got {out.device}")
+            if tuple(out.shape) != (n, V) or not out.is_contiguous():
+                raise ValueError(f"out must hold ({n}, {V}) contiguous entries")
+            ranks, ptr, on_dev = out, out.data_ptr(), 1
+            torch.cuda.current_stream(out.device).synchronize()   # the library works on its own stream
+        elif out is not None:
+            raise ValueError("out must be a float64 device tensor")
+        else:
+            ranks = np.empty((n, V), dtype=np.float64)
+            ptr, on_dev = ranks.ctypes.data, 0
+        sums = np.empty(n, dtype=np.float64)
+        summ = _lib.LpaPprSummary()
+        _lib.check(self._lib.lpa_parallel_pagerank(self._handle(), int(max_iter), float(reset_prob),
+                                                   sv.ctypes.data_as(_lib._i32p), n, ptr, on_dev,
+                                                   sums.ctypes.data if stats else None,
+                                                   ctypes.byref(summ) if stats else None))
+        return (ranks, sums, summ.to_dict()) if stats else ranks
+
     # -- shortest paths -------------------------------------------------------------
     def shortest_paths(self, landmarks, out=None, stats: bool = False):
         """Landmark shortest paths of the directed input graph (lpa_shortest_paths; GraphX

@@ -36,6 +36,7 @@ ID, SRC, DST, LABEL = "id", "src", "dst", "label"
 COMPONENT = "component"
 COUNT = "count"
 PAGERANK = "pagerank"
+PAGERANKS = "pageranks"
 WEIGHT = "weight"
 DISTANCES = "distances"
 CC_ALGORITHMS = ("graphframes", "graphx")
@@ -65,6 +66,21 @@ def _check_page_rank(resetProbability, maxIter, tol):
     if not 0 <= resetProbability <= 1:   # NaN fails both
         raise ValueError(
             f"requirement failed: Random reset probability must belong to [0, 1], but got {resetProbability}")
+
+
+def _check_parallel_page_rank(resetProbability, sourceIds, maxIter):
+    """The argument checks of GraphFrame.parallelPersonalizedPageRank that need no vertex
+    table, before any device work."""
+    if sourceIds is None or (isinstance(sourceIds, (list, tuple, np.ndarray)) and len(sourceIds) == 0):
+        # graphframes.GraphFrame.parallelPersonalizedPageRank (0.6.0)
+        raise ValueError("Source vertices Ids sourceIds must be provided")
+    if maxIter is None:
+        raise ValueError("Max number of iterations maxIter must be provided")
+    if isinstance(sourceIds, (str, bytes)) or not isinstance(sourceIds, (list, tuple, np.ndarray)):
+        raise TypeError(f"sourceIds must be a list, tuple or array of vertex ids, got {type(sourceIds).__name__}")
+    if isinstance(sourceIds, np.ndarray) and sourceIds.ndim != 1:
+        raise TypeError(f"sourceIds must be one-dimensional, got {sourceIds.ndim} dimensions")
+    _check_page_rank(resetProbability, maxIter, None)
 
 
 def _check_scc_max_iter(maxIter):
@@ -278,6 +294,45 @@ class GraphFrame:
         edf[WEIGHT] = 1.0 / odeg[ig.src].astype(np.float64)
         return GraphFrame(vdf, edf, device=self._device)
 
+    def parallelPersonalizedPageRank(self, resetProbability: float = 0.15, sourceIds=None,
+                                     maxIter: int | None = None) -> "GraphFrame":
+        """``GraphFrame.parallelPersonalizedPageRank(resetProbability, sourceIds, maxIter)``
+        (GraphX ``PageRank.runParallelPersonalizedPageRank``): the personalised static PageRank
+        of ``pageRank(maxIter=..., sourceId=s)`` for every s of ``sourceIds`` in one call.
+        Returns a **GraphFrame**, as GraphFrames does: ``.vertices`` is the vertex rows (sorted
+        by id) + ``pageranks``, an object column of float64 arrays of length
+        ``len(sourceIds)`` whose entry i belongs to ``sourceIds[i]``, in the order given;
+        ``.edges`` the edges whose endpoints are both vertex ids, in input order, + ``weight``
+        (float64) = 1 / out-degree of ``src``.  A source may repeat: its entries are then equal
+        (GraphX keeps only the last of a repeat and gives 0 / 0 for the earlier ones; that
+        accident is not reproduced).  ``sourceIds`` (a non-empty list, tuple or 1-D array) and
+        ``maxIter`` are required; an id that is no vertex id raises ``ValueError`` before any
+        device work."""
+        _check_parallel_page_rank(resetProbability, sourceIds, maxIter)
+        dense = []
+        for sid in sourceIds:
+            sid = sid.item() if isinstance(sid, np.generic) else sid
+            try:
+                pos = None if sid is None else self._source_dense(sid)
+            except ValueError:
+                pos = None
+            if pos is None:
+                raise ValueError(f"parallelPersonalizedPageRank: sourceIds entry {sid!r} is not a vertex id")
+            dense.append(pos)
+        ig = self._indexed()
+        g = self._gpu_graph()
+        ranks = g.parallel_pagerank(dense, int(maxIter), float(resetProbability))
+        _, odeg, _, _ = g.pagerank(1, stats=True)
+        V = ig.num_vertices
+        per_vertex = np.empty(V, dtype=object)   # element by element: numpy would make a list of rows 2-D
+        by_vertex = np.ascontiguousarray(ranks.T)
+        for v in range(V):
+            per_vertex[v] = by_vertex[v]
+        vdf = _attach(self._v, ig, {PAGERANKS: per_vertex})
+        edf = self._e[ig.kept].reset_index(drop=True)
+        edf[WEIGHT] = 1.0 / odeg[ig.src].astype(np.float64)
+        return GraphFrame(vdf, edf, device=self._device)
+
     def _landmarks_dense(self, landmarks):
         """(the landmarks as given, repeats collapsed; their dense ids); a TypeError when
         ``landmarks`` is no list, tuple or array, a ValueError when one is no vertex id."""
@@ -403,6 +458,18 @@ def page_rank(vertices: pd.DataFrame, edges: pd.DataFrame, maxIter: int, resetPr
     gf = GraphFrame(vertices, edges, device=device)
     try:
         return gf.pageRank(resetProbability=resetProbability, sourceId=sourceId, maxIter=maxIter).vertices
+    finally:
+        gf.close()
+
+
+def parallel_personalized_page_rank(vertices: pd.DataFrame, edges: pd.DataFrame, sourceIds, maxIter: int,
+                                    resetProbability: float = 0.15, device: int = 0) -> pd.DataFrame:
+    """Function form of ``GraphFrame(vertices, edges).parallelPersonalizedPageRank(
+    resetProbability, sourceIds, maxIter).vertices``: the vertex table + ``pageranks``."""
+    gf = GraphFrame(vertices, edges, device=device)
+    try:
+        return gf.parallelPersonalizedPageRank(resetProbability=resetProbability, sourceIds=sourceIds,
+                                               maxIter=maxIter).vertices
     finally:
         gf.close()
 

@@ -379,6 +379,55 @@ int lpa_pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, int32_t sour
                  int32_t out_is_device, lpa_pagerank_summary* summary);
 
 /*
+ * Parallel personalized PageRank (GraphX PageRank.runParallelPersonalizedPageRank /
+ * GraphFrame.parallelPersonalizedPageRank(resetProbability, sourceIds, maxIter)): n_sources
+ * personalised ranks of the DIRECTED input multigraph in one call.  Row l of rank_out is
+ * exactly what lpa_pagerank specifies for source = sources[l] (the same graph, w, a, start,
+ * step and finish, IEEE binary64 without contraction into fused multiply-adds):
+ *   start   r_l[v] = (v == sources[l]) ? 1.0 : 0.0
+ *   step    max_iter times, every read of the previous r_l:
+ *             c_l[u] = r_l[u] * w[u];  s_l[v] = sum of c_l[u] over the edges u -> v
+ *             r_l[v] = (v == sources[l] ? a : 0.0) + (1.0 - a) * s_l[v]
+ *   finish  S_l = sum_v r_l[v];  r_l[v] /= S_l
+ * A source may repeat: its rows are then equal (GraphX keeps only the last of a repeat and
+ * returns 0 / 0 for the earlier ones; that accident is not reproduced).  S_l == 0 (a = 0 and
+ * a walk that dies) gives whatever IEEE gives.  sources (dense ids) is always host memory;
+ * rank_out ([n_sources][V] row-major: rank_out[l * V + v]) is host memory unless
+ * out_is_device; rank_sum_out (nullable, n_sources entries: S_l) is always host memory;
+ * summary is nullable.  n_sources == 0 or V == 0: success, nothing written, summary all zeros
+ * except that edges, sinks and max_in_degree are still filled when V > 0.  LPA_EINVAL for
+ * max_iter <= 0, reset_prob outside [0, 1] or NaN, n_sources < 0, a null sources or (with
+ * V > 0) rank_out when n_sources > 0, a source outside [0, V).  The call blocks until the
+ * work is done.  The in-list CSR of lpa_pagerank is built once per call; the sources then
+ * run batch_width to a pass (LPA_PPR_BATCH = 4, 8 or 16 at handle creation; anything else:
+ * the default), their c[] and r[] values interleaved so that one gathered in-edge serves
+ * the whole pass from 8 batch_width contiguous bytes (DESIGN.md "Parallel personalized
+ * PageRank").  No floating-point atomics: every column's sums have a shape fixed by the
+ * row's length, the handle's form boundaries, V and the batch width, so row l and S_l are
+ * a function of (V, edge multiset, form boundaries, batch width, max_iter, reset_prob,
+ * sources[l]) alone: bit-identical across runs, handles, input edge orders, the position of
+ * the source in sources and whatever other sources share the call.  They agree with
+ * lpa_pagerank's personalised ranks within its bound, 2 (k (D + 2) + V + 2) 2^-53 relative;
+ * they need not be bit-equal to them.  The batch width changes bits within that bound, never
+ * an integer of the summary.  All working memory is stream-ordered temporaries, the labels
+ * and every other piece of lpa_step's state are neither read nor written, nothing is kept on
+ * the handle.  On a distributed job (nranks > 1) only rank 0 keeps the edge list this needs;
+ * the other ranks return LPA_EINVAL.  Since ABI 13.
+ */
+typedef struct lpa_ppr_summary {
+  int64_t edges, sinks, max_in_degree;   /* as lpa_pagerank_summary                          */
+  int64_t batches;       /* passes = ceil(n_sources / batch_width); 0 with none             */
+  int64_t batch_width;   /* sources to a pass on this handle                                */
+  int64_t nonzero;       /* (source, vertex) pairs with rank > 0                            */
+  double  rank_sum_min, rank_sum_max;  /* smallest / largest S_l (0.0 with no source)        */
+} lpa_ppr_summary;       /* 64 bytes */
+int lpa_parallel_pagerank(lpa_graph* g, int32_t max_iter, double reset_prob,
+                          const int32_t* sources /* host, dense ids */, int32_t n_sources,
+                          double* rank_out /* [n_sources][V] row-major */, int32_t out_is_device,
+                          double* rank_sum_out /* nullable, host, n_sources: S_l */,
+                          lpa_ppr_summary* summary /* nullable */);
+
+/*
  * Landmark shortest paths (GraphX lib.ShortestPaths / GraphFrame.shortestPaths(landmarks))
  * of the DIRECTED input graph: dist_out[l * V + v] is the number of edges on a shortest
  * directed path from vertex v to landmarks[l] along src -> dst (GraphX sends its messages
@@ -476,8 +525,9 @@ int lpa_degrees(lpa_graph* g, int32_t* deg_out);
  * ABI 9: lpa_triangle_count.
  * ABI 10: lpa_pagerank.
  * ABI 11: lpa_shortest_paths.
- * ABI 12: lpa_strongly_connected_components. */
-#define LPA_ABI_VERSION 12
+ * ABI 12: lpa_strongly_connected_components.
+ * ABI 13: lpa_parallel_pagerank. */
+#define LPA_ABI_VERSION 13
 int lpa_abi_version(void);
 int lpa_graph_get_info(const lpa_graph* g, lpa_graph_info* info);
 int lpa_graph_get_info_sized(const lpa_graph* g, lpa_graph_info* info, int64_t info_size);
