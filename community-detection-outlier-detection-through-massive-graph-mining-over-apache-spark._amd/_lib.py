@@ -135,6 +135,23 @@ class LpaSccSummary(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LpaLouvainLevel(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int64) for k in ("vertices", "communities", "rounds", "damped_rounds", "moves",
+                                              "numerator")]
+
+    def to_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class LpaLouvainSummary(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int64) for k in ("n_communities", "n_singletons", "largest_size", "largest_id",
+                                              "levels", "rounds", "damped_rounds", "moves", "arcs", "intra_arcs",
+                                              "numerator")] + [("modularity", ctypes.c_double)]
+
+    def to_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class LpaOutlierSummary(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in (
         "n_groups", "k", "threshold", "n_flagged", "n_communities", "n_communities_flagged",
@@ -185,6 +202,8 @@ SIGNATURES = {
                                           ctypes.POINTER(LpaSpSummary)]),
     "lpa_strongly_connected_components": (ctypes.c_int, [_vp, ctypes.c_int32, _vp, ctypes.c_int32, _vp,
                                                          ctypes.POINTER(LpaSccSummary)]),
+    "lpa_louvain": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int32, _vp,
+                                   ctypes.POINTER(LpaLouvainLevel), ctypes.c_int32, ctypes.POINTER(LpaLouvainSummary)]),
     "lpa_loopback_create": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(_vp)]),
     "lpa_loopback_abort": (None, [_vp]),
     "lpa_loopback_destroy": (None, [_vp]),

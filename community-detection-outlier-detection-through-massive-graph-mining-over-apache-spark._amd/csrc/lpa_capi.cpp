@@ -250,6 +250,14 @@ int create_common(int32_t device, hipStream_t stream, const int32_t* src, const 
   if (const char* f = getenv("LPA_SP_PULL")) g->sp_pull = atoi(f) == 1 ? 1 : 0;
   if (const char* f = getenv("LPA_SCC_BLOCK"))
     g->scc_block = atoi(f) < 0 ? 0 : atoi(f) > lpa::kSccTrimCap ? lpa::kSccTrimCap : atoi(f);
+  if (const char* f = getenv("LPA_LV_SHORT")) g->lv_short = atoi(f) < 0 ? 0 : atoi(f);
+  if (const char* f = getenv("LPA_LV_WAVE")) g->lv_wave = atoi(f) < 0 ? 0 : atoi(f);
+  if (const char* f = getenv("LPA_LV_TABLE")) {
+    const int t = atoi(f) < 0 ? 0 : atoi(f) > lpa::kLvBlockSlots ? lpa::kLvBlockSlots : atoi(f);
+    int p = 0;
+    for (int q = 1; q <= t; q <<= 1) p = q;
+    g->lv_table = p;
+  }
   if (const char* f = getenv("LPA_CONV_STREAMS")) g->conv_streams = atoi(f) < 1 ? 1 : atoi(f) > 3 ? 3 : atoi(f);
   // internal builds (the outlier stage's L2 sub-graph): the locality order is a
   // gather-locality heuristic worth its two atomic passes only on a graph that runs
@@ -793,6 +801,36 @@ int lpa_strongly_connected_components(lpa_graph* g, int32_t max_iter, int32_t* c
   }
   LPA_HIP(hipSetDevice(g->device));
   return strongly_connected_components(g, max_iter, comp_out, out_is_device, size_out, summary);
+}
+
+int lpa_louvain(lpa_graph* g, int32_t max_levels, int32_t max_rounds, int32_t* comm_out, int32_t out_is_device,
+                int64_t* size_out, lpa_louvain_level* levels_out, int32_t levels_cap, lpa_louvain_summary* summary) {
+  if (!g) {
+    set_error("null handle");
+    return LPA_EINVAL;
+  }
+  if (max_levels <= 0) {
+    set_error("lpa_louvain: max_levels must be greater than 0, got %d", max_levels);
+    return LPA_EINVAL;
+  }
+  if (max_rounds <= 0) {
+    set_error("lpa_louvain: max_rounds must be greater than 0, got %d", max_rounds);
+    return LPA_EINVAL;
+  }
+  if (!comm_out && g->V > 0) {
+    set_error("lpa_louvain: null community output");
+    return LPA_EINVAL;
+  }
+  if (levels_cap < 0 || (levels_cap > 0 && !levels_out)) {
+    set_error("lpa_louvain: levels_cap %d without a levels_out to hold it", levels_cap);
+    return LPA_EINVAL;
+  }
+  if (g->m > 0 && !g->e_src) {
+    set_error("lpa_louvain of a distributed job runs on rank 0 (the rank that keeps the edge list)");
+    return LPA_EINVAL;
+  }
+  LPA_HIP(hipSetDevice(g->device));
+  return louvain(g, max_levels, max_rounds, comm_out, out_is_device, size_out, levels_out, levels_cap, summary);
 }
 
 int lpa_degrees(lpa_graph* g, int32_t* deg_out) {

@@ -104,6 +104,12 @@ constexpr int kSccTrimCap = 4096;     // vertices the in-block trim's LDS queue 
 constexpr int kSccBlockTrim = 512;    // a trim level of at most this many vertices runs inside one block (measured:
                                       //   1000 levels of 512 take 17.6 ms there, 24.9 ms as launches; of 1024, 34.5
                                       //   against 31.9 ms; DESIGN.md "Strongly connected components")
+// Louvain (lpa_louvain.hip): list lengths of the move kernel's row forms and the slots of their LDS
+// tally tables; a row of more than half its form's slots takes a region of the global spill table
+constexpr int kLvShort = 32;          // 8 lanes per row up to this length, no table
+constexpr int kLvWave = 256;          // a wave per row up to this length; longer: a block of 1024 per row
+constexpr int kLvWaveSlots = 512;     // (community, weight) slots of a wave's table: 6 KB, 24 KB a block of 4 waves
+constexpr int kLvBlockSlots = 4096;   // ... of the block form's table: 48 KB, under the 64 KB of a plain launch
 __host__ __device__ inline uint32_t col_class(int32_t c, uint32_t ncls) { return ((uint32_t)c >> 10) & (ncls - 1u); }
 
 struct Segment {   // one unit of a seg-bin row
@@ -401,6 +407,13 @@ struct lpa_graph {
   int sp_pull = 0;                          // LPA_SP_PULL=1: pull at every level
   // strongly connected components (lpa_scc.hip): the largest trim level that runs inside one block
   int scc_block = lpa::kSccBlockTrim;       // LPA_SCC_BLOCK (0 .. kSccTrimCap; 0: every level is a launch)
+  // Louvain (lpa_louvain.hip): list lengths up to which a row takes the short form and the wave form
+  // (longer: the block form), and the slots of the block form's LDS table (the wave form's: the
+  // smaller of this and kLvWaveSlots)
+  int lv_short = lpa::kLvShort;             // LPA_LV_SHORT (>= 0; 0: no row with an entry takes the short form)
+  int lv_wave = lpa::kLvWave;               // LPA_LV_WAVE  (>= 0; 0, or <= LPA_LV_SHORT: no row takes the wave form)
+  int lv_table = lpa::kLvBlockSlots;        // LPA_LV_TABLE (0 .. kLvBlockSlots, rounded down to a power of two;
+                                            //   0: every wave-form and block-form row spills)
   int serial = 0;                           // LPA_SERIAL=1: all tally kernels on one stream (profiling)
   int use_graphs = 1;                       // LPA_GRAPHS=0: no captured superstep graphs
   // captured supersteps: [0, 4) converged per (cur, par); [4, 12) supersteps 2 and 3 per
@@ -482,6 +495,9 @@ void scratch_free(lpa_graph* g, void* p);
 // given bit shifts (8-bit digits), in order.  Result ends in `keys`.
 int radix_sort_u64(u64* keys, u64* tmp, int64_t n, const int* shifts, int nshifts,
                    hipStream_t s);
+// the same sort carrying a 64-bit payload with every key (tkeys / tvals: same length)
+int radix_sort_u64_kv(u64* keys, u64* vals, u64* tkeys, u64* tvals, int64_t n, const int* shifts, int nshifts,
+                      hipStream_t s);
 // exclusive scan of int32 input into int64 output (n + 1 entries: out[n] = total)
 int exclusive_scan_i32_i64(const int32_t* in, int64_t* out, int64_t n, hipStream_t s);
 int exclusive_scan_i64(const int64_t* in, int64_t* out, int64_t n, hipStream_t s);
@@ -619,5 +635,9 @@ int shortest_paths(lpa_graph* g, const int32_t* landmarks, int32_t n_landmarks, 
 // strongly connected components of the directed graph, GraphX's rounds (lpa_scc.hip)
 int strongly_connected_components(lpa_graph* g, int32_t max_iter, int32_t* comp_out, int32_t out_is_device,
                                   int64_t* size_out, lpa_scc_summary* summary);
+
+// Louvain community detection on the symmetrised multigraph (lpa_louvain.hip)
+int louvain(lpa_graph* g, int32_t max_levels, int32_t max_rounds, int32_t* comm_out, int32_t out_is_device,
+            int64_t* size_out, lpa_louvain_level* levels_out, int32_t levels_cap, lpa_louvain_summary* summary);
 
 }  // namespace lpa

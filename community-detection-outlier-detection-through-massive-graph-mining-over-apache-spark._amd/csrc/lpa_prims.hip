@@ -285,6 +285,87 @@ __global__ __launch_bounds__(kThreads) void k_rs_scatter(const u64* __restrict__
   }
 }
 
+// The key-plus-payload form of k_rs_scatter: the tile's keys are ranked into LDS as there,
+// each with its position in the tile (16 bits), and the payload of a key is fetched by that
+// position when the key is written out -- a gather inside the tile's 32 KB of payloads, which
+// the tile's own first pass has just pulled through the cache, and a coalesced store.
+__global__ __launch_bounds__(kThreads) void k_rs_scatter_kv(const u64* __restrict__ in, const u64* __restrict__ vin,
+                                                            u64* __restrict__ out, u64* __restrict__ vout, int64_t n,
+                                                            int shift, const u32* __restrict__ offs,
+                                                            const u32* __restrict__ hist, int64_t nblk) {
+  static_assert(kTile <= 65536, "tile positions are staged as 16-bit words");
+  __shared__ u64 sk[kTile];
+  __shared__ uint16_t sq[kTile];  // the tile position a staged key came from
+  __shared__ u32 lstart[256];
+  __shared__ u32 run[256];
+  __shared__ u32 gofs[256];
+  __shared__ u32 wsum[kThreads / 64];
+  __shared__ u32 wcnt[kThreads / 64][256];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  gofs[tid] = offs[(int64_t)tid * nblk + blockIdx.x];
+  const u32 c = hist[(int64_t)tid * nblk + blockIdx.x];
+  u32 incl = c;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const u32 o = (u32)__shfl_up((int)incl, off, 64);
+    if (lane >= off) incl += o;
+  }
+  if (lane == 63) wsum[w] = incl;
+#pragma unroll
+  for (int i = 0; i < kThreads / 64; ++i) wcnt[i][tid] = 0;
+  __syncthreads();
+  u32 wbase = 0;
+  for (int ww = 0; ww < w; ++ww) wbase += wsum[ww];
+  lstart[tid] = wbase + incl - c;
+  run[tid] = wbase + incl - c;
+  __syncthreads();
+  const int64_t base = (int64_t)blockIdx.x * kTile;
+  const int64_t nv64 = n - base;
+  const int nvalid = nv64 < kTile ? (int)nv64 : kTile;
+  const u64 lt = (1ull << lane) - 1ull;
+  for (int i = 0; i < kItems; ++i) {
+    const int q = i * kThreads + tid;
+    const bool ok = q < nvalid;
+    const u64 k = ok ? in[base + q] : 0ull;
+    const u32 dg = (u32)((k >> shift) & 255u);
+    u64 peers = __ballot(ok);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      bool bit = (dg >> b) & 1u;
+      u64 bb = __ballot(bit);
+      peers &= bit ? bb : ~bb;
+    }
+    const u32 rank = (u32)__popcll(peers & lt);
+    if (ok && rank == 0) wcnt[w][dg] = (u32)__popcll(peers);
+    __syncthreads();
+    if (ok) {
+      u32 pos = run[dg] + rank;
+      for (int ww = 0; ww < w; ++ww) pos += wcnt[ww][dg];
+      sk[pos] = k;
+      sq[pos] = (uint16_t)q;
+    }
+    __syncthreads();
+    u32 tot = 0;
+#pragma unroll
+    for (int ww = 0; ww < kThreads / 64; ++ww) {
+      tot += wcnt[ww][tid];
+      wcnt[ww][tid] = 0;
+    }
+    run[tid] += tot;
+    __syncthreads();
+  }
+  for (int i = 0; i < kItems; ++i) {
+    const int q = i * kThreads + tid;
+    if (q < nvalid) {
+      const u64 k = sk[q];
+      const u32 dg = (u32)((k >> shift) & 255u);
+      const u32 dst = gofs[dg] + (u32)q - lstart[dg];
+      out[dst] = k;
+      vout[dst] = vin[base + sq[q]];
+    }
+  }
+}
+
 }  // namespace
 
 // Stream-ordered scratch on the device's default memory pool, whose release threshold
@@ -386,6 +467,45 @@ int radix_sort_u64(u64* keys, u64* tmp, int64_t n, const int* shifts, int nshift
     b = t;
   }
   if (rc == LPA_OK && a != keys) LPA_HIP(hipMemcpyAsync(keys, a, sizeof(u64) * n, hipMemcpyDeviceToDevice, s));
+  tmp_free(hist, s);
+  tmp_free(offs, s);
+  return rc;
+}
+
+int radix_sort_u64_kv(u64* keys, u64* vals, u64* tkeys, u64* tvals, int64_t n, const int* shifts, int nshifts,
+                      hipStream_t s) {
+  if (n <= 1 || nshifts == 0) return LPA_OK;
+  if (n >= (int64_t)UINT32_MAX) {
+    set_error("radix_sort_u64_kv: %lld keys exceed the 32-bit offset range", (long long)n);
+    return LPA_EINVAL;
+  }
+  const int64_t nblk = (n + kTile - 1) / kTile;
+  const int64_t nh = 256 * nblk;
+  u32* hist = nullptr;
+  u32* offs = nullptr;
+  LPA_TRY(tmp_alloc((void**)&hist, sizeof(u32) * nh, s));
+  LPA_TRY(tmp_alloc((void**)&offs, sizeof(u32) * (nh + 1), s));
+  u64 *a = keys, *b = tkeys, *va = vals, *vb = tvals;
+  int rc = LPA_OK;
+  for (int p = 0; p < nshifts && rc == LPA_OK; ++p) {
+    hipLaunchKernelGGL(k_rs_hist, dim3((unsigned)nblk), dim3(kThreads), 0, s, a, n, shifts[p], hist, nblk);
+    LPA_HIP(hipGetLastError());
+    rc = scan_impl<u32, u32>(hist, offs, nh, s);
+    if (rc != LPA_OK) break;
+    hipLaunchKernelGGL(k_rs_scatter_kv, dim3((unsigned)nblk), dim3(kThreads), 0, s, a, va, b, vb, n, shifts[p], offs,
+                       hist, nblk);
+    LPA_HIP(hipGetLastError());
+    u64* t = a;
+    a = b;
+    b = t;
+    t = va;
+    va = vb;
+    vb = t;
+  }
+  if (rc == LPA_OK && a != keys) {
+    LPA_HIP(hipMemcpyAsync(keys, a, sizeof(u64) * n, hipMemcpyDeviceToDevice, s));
+    LPA_HIP(hipMemcpyAsync(vals, va, sizeof(u64) * n, hipMemcpyDeviceToDevice, s));
+  }
   tmp_free(hist, s);
   tmp_free(offs, s);
   return rc;

@@ -582,6 +582,67 @@ class Graph:
                                                                ctypes.byref(summ) if sizes else None))
         return (comp, size, summ.to_dict()) if sizes else comp
 
+    # -- Louvain ------------------------------------------------------------------------
+    def louvain(self, max_levels: int = 64, max_rounds: int = 1000, out=None, stats: bool = False):
+        """Louvain community detection on the symmetrised multigraph the labels are voted on
+        and ``quality`` scores (lpa_louvain): a synchronous, deterministic Louvain in exact
+        integer arithmetic -- every round each vertex proposes its best neighbouring community
+        by the modularity gain (ties to the smaller id, two singletons merge towards the
+        smaller id), all proposals are applied if the modularity rises, otherwise only those to
+        a smaller id, otherwise the level ends; the communities then become the vertices of the
+        next level, at most ``max_levels`` levels of at most ``max_rounds`` rounds each.
+        ``comm[v]`` is the smallest dense id of v's community.  A path or a cycle of n vertices
+        is the slow case, about n / 2 rounds in the first level: ``max_rounds`` is the bound.
+        Host int32 array by default, or written into the int32 device tensor ``out`` (this
+        handle's device, ``num_vertices`` entries).  ``stats=True`` returns ``(comm, sizes,
+        levels, summary)``: ``sizes[c]`` (int64, in the memory ``comm`` is in) holds the member
+        count at every community id c and 0 elsewhere; ``levels`` is a list of dicts of
+        vertices, communities, rounds, damped_rounds, moves, numerator, one per level;
+        ``summary`` a dict of n_communities, n_singletons, largest_size, largest_id, levels,
+        rounds, damped_rounds, moves, arcs, intra_arcs, numerator, modularity.  The result is
+        identical across runs, handles, input edge orders and directions, and kernel
+        schedules.  The labels and the LPA state are not touched."""
+        for name, x in (("max_levels", max_levels), ("max_rounds", max_rounds)):
+            if not isinstance(x, (int, np.integer)) or isinstance(x, (bool, np.bool_)):
+                raise TypeError(f"{name} must be an int, got {type(x).__name__}")
+            if x <= 0:
+                raise ValueError(f"{name} must be greater than 0, got {x}")
+        max_levels = min(int(max_levels), 2 ** 31 - 1)
+        max_rounds = min(int(max_rounds), 2 ** 31 - 1)
+        V = self.num_vertices
+        size = None
+        if out is not None and _is_device_tensor(out):
+            import torch
+
+            if out.dtype != torch.int32:
+                raise ValueError(f"out must be int32, got {out.dtype}")
+            if out.device.index != self.device:
+                raise ValueError(f"out must be on cuda:{self.device}, got {out.device}")
+            if out.numel() != V or not out.is_contiguous():
+                raise ValueError(f"out must hold {V} contiguous entries")
+            comm, ptr, on_dev = out, out.data_ptr(), 1
+            if stats:
+                size = torch.empty(V, dtype=torch.int64, device=out.device)
+            torch.cuda.current_stream(out.device).synchronize()   # the library works on its own stream
+            size_ptr = size.data_ptr() if stats else None
+        elif out is not None:
+            raise ValueError("out must be an int32 device tensor")
+        else:
+            comm = np.empty(V, dtype=np.int32)
+            ptr, on_dev = comm.ctypes.data, 0
+            if stats:
+                size = np.empty(V, dtype=np.int64)
+            size_ptr = size.ctypes.data if stats else None
+        cap = min(max_levels, 1024)   # level rows returned; later levels (unseen so far) count in the summary only
+        rows = (_lib.LpaLouvainLevel * cap)()
+        summ = _lib.LpaLouvainSummary()
+        _lib.check(self._lib.lpa_louvain(self._handle(), max_levels, max_rounds, ptr, on_dev, size_ptr,
+                                         rows if stats else None, cap if stats else 0,
+                                         ctypes.byref(summ) if stats else None))
+        if not stats:
+            return comm
+        return comm, size, [rows[i].to_dict() for i in range(min(int(summ.levels), cap))], summ.to_dict()
+
 
 class Loopback:
     """In-process collective group of ``nranks`` handles on one device (the

@@ -92,6 +92,15 @@ def _check_scc_max_iter(maxIter):
         raise ValueError(f"requirement failed: Number of iterations must be greater than 0, but got {maxIter}")
 
 
+def _check_louvain(maxLevels, maxRounds):
+    """The argument checks of GraphFrame.louvain, before any device work."""
+    for name, x in (("maxLevels", maxLevels), ("maxRounds", maxRounds)):
+        if not isinstance(x, (int, np.integer)) or isinstance(x, (bool, np.bool_)):
+            raise TypeError(f"{name} must be an int, got {type(x).__name__}")
+        if x <= 0:
+            raise ValueError(f"{name} must be greater than 0, but got {x}")
+
+
 def _check_cc_algorithm(algorithm):
     if algorithm not in CC_ALGORITHMS:
         # graphframes.lib.ConnectedComponents.setAlgorithm: require(supportedAlgorithms.contains(value), ...)
@@ -233,6 +242,27 @@ class GraphFrame:
         ig = self._indexed()
         dense = self._gpu_graph().strongly_connected_components(int(maxIter))
         return _attach(self._v, ig, {COMPONENT: _label_values(ig, dense)})
+
+    def louvain(self, maxLevels: int = 64, maxRounds: int = 1000) -> pd.DataFrame:
+        """Louvain community detection -- this package's own addition, not a GraphFrames call
+        (like ``clusteringCoefficient`` and ``outlierScores``): a modularity-maximising
+        detector on the same symmetrised multigraph ``labelPropagation`` votes on, synchronous
+        and deterministic, in exact integer arithmetic (``Graph.louvain`` states the rounds).
+        Returns the vertex rows sorted by id + ``label`` (int64): the smallest member of each
+        vertex's community -- its original id for integral ids, its dense index in ascending
+        id order otherwise, as ``labelPropagation``'s ``label``.  ``outlierScores(labels=...)``
+        takes the result as it takes ``labelPropagation``'s.  ``.attrs["modularity"]`` is the
+        modularity of the partition, ``.attrs["levels"]`` the list of per-level dicts
+        (vertices, communities, rounds, damped_rounds, moves, numerator).  ``maxLevels`` bounds
+        the aggregation levels, ``maxRounds`` the rounds of one level (a path or a cycle of n
+        vertices needs about n / 2)."""
+        _check_louvain(maxLevels, maxRounds)
+        ig = self._indexed()
+        dense, _, levels, summ = self._gpu_graph().louvain(int(maxLevels), int(maxRounds), stats=True)
+        out = _attach(self._v, ig, {LABEL: _label_values(ig, dense)})
+        out.attrs["modularity"] = summ["modularity"]
+        out.attrs["levels"] = levels
+        return out
 
     def triangleCount(self) -> pd.DataFrame:
         """``GraphFrame.triangleCount``: vertices + ``count`` (int64), the number of
@@ -438,6 +468,17 @@ def strongly_connected_components(vertices: pd.DataFrame, edges: pd.DataFrame, m
     gf = GraphFrame(vertices, edges, device=device)
     try:
         return gf.stronglyConnectedComponents(maxIter)
+    finally:
+        gf.close()
+
+
+def louvain(vertices: pd.DataFrame, edges: pd.DataFrame, maxLevels: int = 64, maxRounds: int = 1000,
+            device: int = 0) -> pd.DataFrame:
+    """Function form of ``GraphFrame(vertices, edges).louvain(maxLevels, maxRounds)``."""
+    _check_louvain(maxLevels, maxRounds)
+    gf = GraphFrame(vertices, edges, device=device)
+    try:
+        return gf.louvain(maxLevels, maxRounds)
     finally:
         gf.close()
 

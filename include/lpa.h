@@ -510,6 +510,85 @@ int lpa_strongly_connected_components(lpa_graph* g, int32_t max_iter, int32_t* c
                                       int32_t out_is_device, int64_t* size_out /* nullable, as lpa_components */,
                                       lpa_scc_summary* summary /* nullable */);
 
+/*
+ * Louvain community detection on the symmetrised multigraph lpa_step votes on and lpa_quality
+ * scores: a synchronous, deterministic Louvain (the Lu-Halappanavar-Kalyanaraman singleton rule
+ * plus a monotone acceptance test), defined in exact integer arithmetic.  This is the package's
+ * own call (GraphFrames has none); its labels go wherever lpa_run's go (lpa_outlier, lpa_quality).
+ *
+ * Graph.  Every kept input edge u -> v (both ends in [0, V)) gives the arcs u -> v and v -> u; a
+ *   self-loop gives two arcs at its vertex; duplicates count.  A = total arcs.  At any level a
+ *   vertex u has a self weight s[u] (arcs u -> u), off-diagonal weights w(u,v) = w(v,u) for
+ *   u != v, and a degree k[u] = s[u] + sum_v w(u,v); sum k = A at every level.  Level 0:
+ *   s[u] = 2 x (self-loops at u), w(u,v) = the input edges between u and v in either direction.
+ * State of a level with n vertices: c[u] = u, D[c] = sum of k over the members, size[c] = the
+ *   members.  The score numerator is N = A x I - sum_c D[c]^2, where
+ *   I = sum_u (s[u] + sum_{v != u, c[v] = c[u]} w(u,v)).  Modularity is N / A^2.
+ * A round.  All reads are of the state at the start of the round.  For every u, with own
+ *   community a = c[u] and K(u,x) = sum_{v != u, c[v] = x} w(u,v):
+ *     score(x) = A x K(u,x) - k[u] x (D[x] - (x == a ? k[u] : 0)).
+ *     The candidates are the x != a with K(u,x) > 0; the best b has the largest score, ties to
+ *     the smallest x.  u proposes a move to b iff score(b) > score(a), and not
+ *     (size[a] == 1 and size[b] == 1 and b > a).  A blocked or failed best is not replaced by
+ *     the second best.
+ *   No proposals: the phase ends and the round is not counted.  Otherwise rounds += 1; apply all
+ *   proposals; if the new N is greater than the old N, the round is accepted.  If not, apply
+ *   only the proposals with b < a; if there is at least one and N rises, the round is accepted
+ *   and counted in damped_rounds.  Otherwise the labels stay as they were and the phase ends.
+ *   The phase also ends when its rounds == max_rounds.  N rises strictly with every accepted
+ *   round, so a phase always terminates.
+ * A level.  A phase with no accepted move ends the algorithm, and that level is not counted.
+ *   Otherwise aggregate: the surviving community ids, in ascending order, become vertices
+ *   0, 1, ... of the next level; w'(i,j) is the summed w between members of i and of j, i != j;
+ *   s'(i) = sum of s over the members + sum of w(u,v) over ordered pairs u != v inside i.
+ *   levels += 1; stop at max_levels.
+ * Result.  comm_out[v], by dense id, is the SMALLEST original dense id in v's final community
+ *   (the convention of lpa_components).  V == 0 or A == 0: the identity, 0 levels, modularity
+ *   0.0.  Vertices without off-diagonal arcs never move.
+ * A path or a cycle is the slow case of any synchronous min-label scheme: about n / 2 rounds in
+ * the first level; max_rounds is the caller's bound.
+ * Limits.  A <= 3,037,000,499, so that A^2 < 2^63: every score, N and D^2 fit int64; above
+ * that the call returns LPA_EINVAL with a message.  LPA_EINVAL for max_levels <= 0, for
+ * max_rounds <= 0 and for a null comm_out with V > 0.
+ * comm_out and every integer of the level rows and the summary are functions of (V, the edge
+ * multiset as undirected pairs, max_levels, max_rounds) alone: identical across runs, handles,
+ * input edge orders and directions, and kernel schedules.  size_out (nullable, V entries):
+ * size_out[c] = the vertices with comm_out == c, 0 at every other index.  Both arrays are host
+ * memory unless out_is_device.  levels_out (nullable, host, levels_cap rows): row l describes
+ * counted level l; the levels past levels_cap are run and summed in the summary, not written.
+ * The call blocks until the work is done.  Degree-binned move kernels with LDS tally tables and
+ * an exact global spill table (DESIGN.md "Louvain").  All working memory is stream-ordered
+ * temporaries, the labels and every other piece of lpa_step's state are neither read nor
+ * written, nothing is kept on the handle.  On a distributed job (nranks > 1) only rank 0 keeps
+ * the edge list this needs; the other ranks return LPA_EINVAL.  Since ABI 14.
+ */
+typedef struct lpa_louvain_level {
+  int64_t vertices;       /* vertices of the level                                        */
+  int64_t communities;    /* communities it ends with = vertices of the next level        */
+  int64_t rounds;         /* rounds with at least one proposal (a rejected last one too)  */
+  int64_t damped_rounds;  /* accepted rounds that applied only the moves to a smaller id  */
+  int64_t moves;          /* moves applied by the accepted rounds                         */
+  int64_t numerator;      /* N at the end of the level                                    */
+} lpa_louvain_level;      /* 48 bytes */
+typedef struct lpa_louvain_summary {
+  int64_t n_communities;  /* distinct values of comm_out                                  */
+  int64_t n_singletons;   /* values held by exactly one vertex                            */
+  int64_t largest_size;   /* 0 if V == 0                                                  */
+  int64_t largest_id;     /* smallest id on a tie; -1 if V == 0                           */
+  int64_t levels;         /* counted levels                                               */
+  int64_t rounds;         /* sums over the counted levels ...                             */
+  int64_t damped_rounds;
+  int64_t moves;
+  int64_t arcs;           /* A                                                            */
+  int64_t intra_arcs;     /* I of the result                                              */
+  int64_t numerator;      /* N of the result                                              */
+  double modularity;      /* (double)numerator / ((double)arcs * arcs), 0.0 if arcs == 0  */
+} lpa_louvain_summary;    /* 96 bytes */
+int lpa_louvain(lpa_graph* g, int32_t max_levels, int32_t max_rounds, int32_t* comm_out, int32_t out_is_device,
+                int64_t* size_out /* nullable, [V], where comm_out is */,
+                lpa_louvain_level* levels_out /* nullable, host */, int32_t levels_cap,
+                lpa_louvain_summary* summary /* nullable */);
+
 /* Symmetrised degree of every vertex (dense ids), host output. */
 int lpa_degrees(lpa_graph* g, int32_t* deg_out);
 
@@ -526,8 +605,9 @@ int lpa_degrees(lpa_graph* g, int32_t* deg_out);
  * ABI 10: lpa_pagerank.
  * ABI 11: lpa_shortest_paths.
  * ABI 12: lpa_strongly_connected_components.
- * ABI 13: lpa_parallel_pagerank. */
-#define LPA_ABI_VERSION 13
+ * ABI 13: lpa_parallel_pagerank.
+ * ABI 14: lpa_louvain. */
+#define LPA_ABI_VERSION 14
 int lpa_abi_version(void);
 int lpa_graph_get_info(const lpa_graph* g, lpa_graph_info* info);
 int lpa_graph_get_info_sized(const lpa_graph* g, lpa_graph_info* info, int64_t info_size);
