@@ -70,6 +70,7 @@ class LpaGraphInfo(ctypes.Structure):
         ("exchanges_post_missed", ctypes.c_int64),
         ("gather_mode", ctypes.c_int64),
         ("host_allgathers", ctypes.c_int64),
+        ("sparse_refreshes", ctypes.c_int64),
     ]
 
     def to_dict(self):

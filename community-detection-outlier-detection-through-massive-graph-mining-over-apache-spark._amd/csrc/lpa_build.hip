@@ -466,6 +466,8 @@ int init_labels(lpa_graph* g) {
     LPA_HIP(hipMemsetAsync(g->gword + GW_ABITS_OK, 0, sizeof(int32_t), g->stream));  // abits stale
     LPA_HIP(hipMemsetAsync(g->gword + GW_ABITS_PASS, 0, sizeof(int32_t), g->stream));  // no abits pass ran
     LPA_HIP(hipMemsetAsync(g->gword + GW_CODE, 0, sizeof(int32_t), g->stream));  // no code refresh pending
+    // al[] is dense again (al0 / the L0 rebuild below); GW_AL_SPARSE, GW_AL_GB, GW_SPARSE_CNT
+    LPA_HIP(hipMemsetAsync(g->gword + GW_AL_SPARSE, 0, 3 * sizeof(int32_t), g->stream));
   }
   g->cur = 0;
   g->since_reset = 0;

@@ -237,6 +237,7 @@ int create_common(int32_t device, hipStream_t stream, const int32_t* src, const 
   if (const char* f = getenv("LPA_FUSED_BINS")) g->fused_bins = atoi(f) < 0 ? 0 : atoi(f) > 2 ? 2 : atoi(f);
   if (const char* f = getenv("LPA_UNITS_PURE")) g->units_pure = atoi(f) ? 1 : 0;
   if (const char* f = getenv("LPA_KEEP_BITS")) g->keep_bits = atoi(f) ? 1 : 0;
+  if (const char* f = getenv("LPA_SPARSE_AL")) g->sparse_al = atoi(f) ? 1 : 0;
   if (const char* f = getenv("LPA_TC_SHORT")) g->tc_short = atoi(f) < 0 ? 0 : atoi(f);
   if (const char* f = getenv("LPA_TC_WAVE")) g->tc_wave = atoi(f) < 0 ? 0 : atoi(f) > kTcWaveMax ? kTcWaveMax : atoi(f);
   if (const char* f = getenv("LPA_TC_LDS")) g->tc_lds = atoi(f) < 0 ? 0 : atoi(f) > kTcLdsMax ? kTcLdsMax : atoi(f);
@@ -883,6 +884,13 @@ int fill_info(const lpa_graph* g, lpa_graph_info* info) {
     LPA_HIP(hipMemcpyAsync(&w, g->gword + GW_CODE, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
     LPA_HIP(hipStreamSynchronize(g->stream));
     info->code_refresh = w;
+  }
+  if (g->sparse_al && g->gword) {  // counted on the device (the rebuild's mode is decided there)
+    LPA_HIP(hipSetDevice(g->device));
+    int32_t w = 0;
+    LPA_HIP(hipMemcpyAsync(&w, g->gword + GW_SPARSE_CNT, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    LPA_HIP(hipStreamSynchronize(g->stream));
+    info->sparse_refreshes = w;
   }
   return LPA_OK;
 }

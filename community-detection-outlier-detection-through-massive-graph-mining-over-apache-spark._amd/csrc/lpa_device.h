@@ -18,6 +18,59 @@ __device__ __forceinline__ u32 ld_stream(const int32_t* p) {
   return (u32)__builtin_nontemporal_load(p);
 }
 
+// ---------------------------------------------------------------------------
+// Votes from a possibly sparse al[] (gword[GW_AL_SPARSE], lpa_internal.h): arc i votes Gb
+// when its arc giant bit is set, al[i] otherwise.  `on` is all ones while al[] is sparse
+// and 0 while it is dense: the bit word is then read at index 0 and masked off, so a
+// reader issues the same loads either way (no branch around a load: the tallies' rings
+// count on exact vmcnt tracking) and a dense al[] costs one cached word per chunk.
+// ---------------------------------------------------------------------------
+struct ArcLabels {
+  const int32_t* p;
+  const uint32_t* bits;
+  u32 on, Gb, last;
+};
+__device__ __forceinline__ ArcLabels arc_labels(const ArcSrc& s) {
+  ArcLabels A;
+  A.p = s.p;
+  A.bits = s.bits;
+  A.on = s.gword[GW_AL_SPARSE] != 0 ? ~0u : 0u;
+  A.Gb = (u32)s.gword[GW_AL_GB];
+  A.last = s.last;
+  return A;
+}
+// one arc's vote, both loads issued at once (the readers that use a label where they load it)
+__device__ __forceinline__ u32 arc_label(const ArcLabels& A, int64_t i) {
+  const u32 x = ld_stream(A.p + i);
+  const u32 w = A.bits[(u32)(i >> 5) & A.on] & A.on;
+  return ((w >> ((u32)i & 31u)) & 1u) ? A.Gb : x;
+}
+// The ring readers (a wave per row or unit, its arcs [base, base + 64 NC) lane-consecutive)
+// load the bit words with the labels -- lane l the word (base >> 5) + l, 2 NC + 1 of them,
+// one register per ring slot -- and apply them where the labels are tallied, so no wait
+// lands between a slot's loads and its use.
+template <int NC>
+__device__ __forceinline__ u32 arc_bits_load(const ArcLabels& A, int64_t base, int lane) {
+  const u32 l = (u32)lane < 2u * NC ? (u32)lane : 2u * NC;
+  u32 idx = (u32)(base >> 5) + l;
+  idx = idx < A.last ? idx : A.last;
+  return A.bits[idx & A.on];
+}
+template <int NC>
+__device__ __forceinline__ void arc_bits_apply(u32 (&lab)[NC], u32 bw, const ArcLabels& A, int64_t base) {
+  if (A.on == 0u) return;  // dense (uniform; no load inside the branch): nothing to apply
+  const u32 o = (u32)__builtin_amdgcn_readfirstlane((int)((u32)base & 31u));
+  const u64 on = ~0ull;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const u64 w0 = (u32)__builtin_amdgcn_readlane((int)bw, 2 * c);
+    const u64 w1 = (u32)__builtin_amdgcn_readlane((int)bw, 2 * c + 1);
+    const u64 w2 = (u32)__builtin_amdgcn_readlane((int)bw, 2 * c + 2);
+    const u64 m = ((((w1 << 32) | w0) >> o) | (((w2 << 32) << (32u - o)))) & on;
+    lab[c] = __builtin_amdgcn_inverse_ballot_w64(m) ? A.Gb : lab[c];
+  }
+}
+
 __device__ __forceinline__ u64 tally(u32 cnt, u32 label) {
   return ((u64)cnt << 32) | (u64)(u32)(~label);
 }

@@ -198,6 +198,12 @@ enum GwordSlot {
   GW_PURE_ALL = 10,   // superstep 4's k_lpa_units: 0 = the impure-unit list, 1 = every unit
                       //   (its "fr_all", k_units_pure)
   GW_PURE_CNT = 11,   // ... and that list's length (zeroed by k_giant_pick)
+  GW_AL_SPARSE = 12,  // al[] is sparse (one-GPU bits-mode rebuild): an arc whose abits bit is set votes
+                      //   gword[GW_AL_GB] and its al[] entry is undefined; a clear bit's entry is current.
+                      //   Cleared by every other full rebuild (k_giant_bits ahead of the LDS / small /
+                      //   code forms, k_al_rebuild, the folded rebuild of k_al_scatter) and by a reset.
+  GW_AL_GB = 13,      // Gb: the giant label of the vector the sparse rebuild read
+  GW_SPARSE_CNT = 14, // refreshes that left al[] sparse since the build or the last reset
 };
 constexpr int kGwordLen = 16;
 // Slots of lpa_graph::gdec (kGdecLen words): superstep 2's hub decision in block mode
@@ -210,6 +216,17 @@ enum GdecSlot {
                       //   their whole ranges (their "fr_all")
 };
 constexpr int kGdecLen = 4;
+
+// What a tally kernel takes its votes from: al[] (or, in gather mode, col[]), with the arc
+// giant bits and the gword a sparse al[] is read through (gword[GW_AL_SPARSE], device-side:
+// the captured supersteps replay with whatever state the last rebuild left).  bits: abits as
+// 32-bit words, last = its highest word index.
+struct ArcSrc {
+  const int32_t* p;
+  const uint32_t* bits;
+  const int32_t* gword;
+  uint32_t last;
+};
 
 }  // namespace lpa
 
@@ -247,6 +264,7 @@ struct lpa_graph {
                           // (0: a launch per bin, 2: the wave bins keep theirs)
   int units_pure = 1;     // LPA_UNITS_PURE=0: superstep 4 re-tallies every hub unit
   int keep_bits = 1;      // LPA_KEEP_BITS=0: superstep 3's scatter drops the arc giant bits
+  int sparse_al = 1;      // LPA_SPARSE_AL=0: a bits-mode rebuild also stores the giant label (dense al[])
   int conv_streams = 2;   // LPA_CONV_STREAMS: streams of a converged superstep's tally (1-3)
   int64_t vpad = 0;       // nranks * slice
   int64_t own_begin = 0;  // rank * slice

@@ -200,13 +200,19 @@ __device__ __forceinline__ void hash_batch(u64* tab, uint16_t* lst, int& cnt, in
 }
 
 template <int NC>
-__device__ __forceinline__ void load_labels(u32 (&lab)[NC], const int32_t* __restrict__ al,
+__device__ __forceinline__ void load_labels(u32 (&lab)[NC], const ArcLabels& al,
                                             int64_t b, int64_t e, int lane) {
+  // (the batch's arc giant bit words in one load, applied to the loaded labels: a bit
+  // word per vote cost C5's superstep 2 1.3 ms in k_lpa_block with al[] dense)
+  const u32 bw = arc_bits_load<NC>(al, b, lane);
 #pragma unroll
   for (int u = 0; u < NC; ++u) {
     const int64_t i = b + u * 64 + lane;
-    lab[u] = i < e ? ld_stream(al + i) : kNone;
+    lab[u] = i < e ? ld_stream(al.p + i) : kNone;
   }
+  arc_bits_apply<NC>(lab, bw, al, b);
+#pragma unroll
+  for (int u = 0; u < NC; ++u) lab[u] = b + u * 64 + lane < e ? lab[u] : kNone;
 }
 
 // ---------------------------------------------------------------------------
@@ -344,6 +350,12 @@ __device__ __forceinline__ u32 arc_vote(const int32_t* __restrict__ src, const i
   if constexpr (kG) return (u32)L[(int32_t)ld_stream(src + i)];
   else return ld_stream(src + i);
 }
+// ... from a possibly sparse al[] (lpa_device.h arc_label)
+template <bool kG>
+__device__ __forceinline__ u32 arc_vote(const ArcLabels& src, const int32_t* __restrict__ L, int64_t i) {
+  if constexpr (kG) return (u32)L[(int32_t)ld_stream(src.p + i)];
+  else return arc_label(src, i);
+}
 
 // the mode of each G-lane group's votes (kNone: no vote), written to Ln[v] by the group's
 // first lane when live
@@ -381,7 +393,7 @@ __device__ __forceinline__ void group_tally(u32 lab, int32_t* __restrict__ Ln, i
 
 // G lanes per row (G <= 64, all 64 lanes of the wave call it: ballot peel)
 template <int G, bool kG = false>
-__device__ __forceinline__ void group_row(const int64_t* __restrict__ rp, const int32_t* __restrict__ al,
+__device__ __forceinline__ void group_row(const int64_t* __restrict__ rp, const ArcLabels& al,
                                           int32_t* __restrict__ Ln, int64_t v, bool live, int lane,
                                           u64* tab = nullptr, const int32_t* __restrict__ Lg = nullptr) {
   const int j = lane & (G - 1);
@@ -399,7 +411,7 @@ __device__ __forceinline__ void group_row(const int64_t* __restrict__ rp, const 
 // of its own passes blockIdx / gridDim, k_bins_fused its share of one launch)
 template <int G, bool kG = false>
 __device__ __forceinline__ void group_bin(int64_t bid, int64_t nblk, const int64_t* __restrict__ rp,
-                                          const int32_t* __restrict__ al, int32_t* __restrict__ Ln,
+                                          const ArcLabels& al, int32_t* __restrict__ Ln,
                                           int64_t vbeg, int64_t vend, const int32_t* __restrict__ flist,
                                           const int32_t* __restrict__ fcnt_b, const int32_t* __restrict__ fr_all,
                                           const int32_t* __restrict__ Lg) {
@@ -417,13 +429,13 @@ __device__ __forceinline__ void group_bin(int64_t bid, int64_t nblk, const int64
 
 template <int G, bool kG = false>
 __global__ __launch_bounds__(256) void k_lpa_group(const int64_t* __restrict__ rp,
-                                                   const int32_t* __restrict__ al,
+                                                   const ArcSrc asrc,
                                                    int32_t* __restrict__ Ln, int64_t vbeg,
                                                    int64_t vend, const int32_t* __restrict__ flist,
                                                    const int32_t* __restrict__ fcnt_b,
                                                    const int32_t* __restrict__ fr_all,
                                                    const int32_t* __restrict__ Lg) {
-  group_bin<G, kG>(blockIdx.x, gridDim.x, rp, al, Ln, vbeg, vend, flist, fcnt_b, fr_all, Lg);
+  group_bin<G, kG>(blockIdx.x, gridDim.x, rp, arc_labels(asrc), Ln, vbeg, vend, flist, fcnt_b, fr_all, Lg);
 }
 
 // ---------------------------------------------------------------------------
@@ -450,47 +462,35 @@ __device__ __forceinline__ RowSpan row_span(const int64_t* __restrict__ rp, cons
 
 __device__ __forceinline__ int span_len(const RowSpan& r) { return (int)(r.e - r.b); }
 
-// unconditional loads of a row's labels (address clamped into the row)
-template <int NC>
-__device__ __forceinline__ void row_load(u32 (&raw)[NC], const int32_t* __restrict__ al,
-                                         const RowSpan& r, int lane) {
-  const int d = span_len(r);
-  if (__builtin_amdgcn_readfirstlane(d) == 0) {  // frontier-clean row: no loads
-#pragma unroll
-    for (int c = 0; c < NC; ++c) raw[c] = kNone;
-    return;
-  }
-  const int last = d > 0 ? d - 1 : 0;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int off = c * 64 + lane;
-    raw[c] = ld_stream(al + r.b + (off < last ? off : last));
-  }
-}
-
 // branch-free form (k_lpa_wave's ring): an empty span (past the bin's end) loads
 // al[0] and its labels are never read -- no control flow for the waitcnt pass to merge
+// (bw: the row's arc giant bit words, applied by row_tally -- arc_bits_load)
 template <int NC, bool kG = false>
-__device__ __forceinline__ void row_load_nb(u32 (&raw)[NC], const int32_t* __restrict__ al,
+__device__ __forceinline__ void row_load_nb(u32 (&raw)[NC], u32& bw, const ArcLabels& al,
                                             const RowSpan& r, int lane, const int32_t* __restrict__ Lg = nullptr) {
   const int d = span_len(r);
   const int last = d > 0 ? d - 1 : 0;
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     const int off = c * 64 + lane;
-    raw[c] = arc_vote<kG>(al, Lg, r.b + (off < last ? off : last));
+    raw[c] = arc_vote<kG>(al.p, Lg, r.b + (off < last ? off : last));
   }
+  if constexpr (kG) bw = 0u;
+  else bw = arc_bits_load<NC>(al, r.b, lane);
 }
 
-template <int NC>
-__device__ __forceinline__ void row_tally(const u32 (&raw)[NC], const RowSpan& r, int64_t v,
-                                          int32_t* __restrict__ Ln, u64* tab, uint16_t* lst, int lane,
+template <int NC, bool kG = false>
+__device__ __forceinline__ void row_tally(const u32 (&raw)[NC], u32 bw, const ArcLabels& al, const RowSpan& r,
+                                          int64_t v, int32_t* __restrict__ Ln, u64* tab, uint16_t* lst, int lane,
                                           u64 lt, int pmax, bool giant, u32 G) {
   const int d = span_len(r);
   if (d == 0) return;
   u32 lab[NC];
 #pragma unroll
-  for (int c = 0; c < NC; ++c) lab[c] = c * 64 + lane < d ? raw[c] : kNone;
+  for (int c = 0; c < NC; ++c) lab[c] = raw[c];
+  if constexpr (!kG) arc_bits_apply<NC>(lab, bw, al, r.b);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) lab[c] = c * 64 + lane < d ? lab[c] : kNone;
   int lg = ceil_log2(2u * (u32)d);
   lg = lg < 6 ? 6 : lg;
   const int nch = (d + 63) >> 6;
@@ -572,7 +572,7 @@ constexpr int wave_ring_depth() { return NC <= 2 ? 6 : NC <= 4 ? 4 : 3; }
 // list entries)
 template <int NC, bool kG = false>
 __device__ __forceinline__ void wave_bin(int64_t bid, int64_t nblk, u64* tab_all, uint16_t* lst_all,
-                                         const int64_t* __restrict__ rp, const int32_t* __restrict__ al,
+                                         const int64_t* __restrict__ rp, const ArcLabels& al,
                                          int32_t* __restrict__ Ln, int64_t vbeg, int64_t vend,
                                          const int32_t* __restrict__ flist, const int32_t* __restrict__ fcnt_b,
                                          const int32_t* __restrict__ fr_all, int pmax,
@@ -599,16 +599,16 @@ __device__ __forceinline__ void wave_bin(int64_t bid, int64_t nblk, u64* tab_all
   nxt.b = nxt.e = 0;
   nxt.v = 0;
   int p = 0;  // current row: work item ib + p * stride
-  u32 rl[D][NC];
+  u32 rl[D][NC], rb[D];
 #pragma unroll
-  for (int k = 0; k < D - 1; ++k) row_load_nb<NC, kG>(rl[k], al, span_at(cur, nxt, k), lane, Lg);
+  for (int k = 0; k < D - 1; ++k) row_load_nb<NC, kG>(rl[k], rb[k], al, span_at(cur, nxt, k), lane, Lg);
   while (true) {
 #pragma unroll
     for (int k = 0; k < D; ++k) {
-      row_load_nb<NC, kG>(rl[(k + D - 1) % D], al, span_at(cur, nxt, p + D - 1), lane, Lg);
+      row_load_nb<NC, kG>(rl[(k + D - 1) % D], rb[(k + D - 1) % D], al, span_at(cur, nxt, p + D - 1), lane, Lg);
       const RowSpan s = span_at(cur, nxt, p);
       const int64_t v = (int64_t)__builtin_amdgcn_readlane(cur.v, p);
-      row_tally<NC>(rl[k], s, v, Ln, tab, lst, lane, lt, pmax, giant, G);
+      row_tally<NC, kG>(rl[k], rb[k], al, s, v, Ln, tab, lst, lane, lt, pmax, giant, G);
       if (ib + (int64_t)(p + 1) * stride >= br.n) return;
       ++p;
       if (p == 32) nxt = span_batch(rp, br, ib + 64 * stride, stride, lane);
@@ -623,7 +623,7 @@ __device__ __forceinline__ void wave_bin(int64_t bid, int64_t nblk, u64* tab_all
 
 template <int NC, bool kG = false>
 __global__ __launch_bounds__(256) void k_lpa_wave(const int64_t* __restrict__ rp,
-                                                  const int32_t* __restrict__ al,
+                                                  const ArcSrc asrc,
                                                   int32_t* __restrict__ Ln, int64_t vbeg,
                                                   int64_t vend, const int32_t* __restrict__ flist,
                                                   const int32_t* __restrict__ fcnt_b,
@@ -632,8 +632,8 @@ __global__ __launch_bounds__(256) void k_lpa_wave(const int64_t* __restrict__ rp
                                                   const int32_t* __restrict__ Lg) {
   __shared__ u64 tab_all[4 * 2 * 64 * NC];
   __shared__ uint16_t lst_all[4 * 64 * NC];
-  wave_bin<NC, kG>(blockIdx.x, gridDim.x, tab_all, lst_all, rp, al, Ln, vbeg, vend, flist, fcnt_b, fr_all, pmax,
-                   gsel, Lg);
+  wave_bin<NC, kG>(blockIdx.x, gridDim.x, tab_all, lst_all, rp, arc_labels(asrc), Ln, vbeg, vend, flist, fcnt_b,
+                   fr_all, pmax, gsel, Lg);
 }
 
 // ---------------------------------------------------------------------------
@@ -650,7 +650,7 @@ __global__ __launch_bounds__(256) void k_lpa_wave(const int64_t* __restrict__ rp
 // ---------------------------------------------------------------------------
 template <int kLg, int kBlockWaves>
 __global__ __launch_bounds__(64 * kBlockWaves) void k_lpa_block(const int64_t* __restrict__ rp,
-                                                               const int32_t* __restrict__ al,
+                                                               const ArcSrc asrc,
                                                                int32_t* __restrict__ Ln, int64_t h0,
                                                                int64_t h1,
                                                                const int32_t* __restrict__ flist,
@@ -672,6 +672,7 @@ __global__ __launch_bounds__(64 * kBlockWaves) void k_lpa_block(const int64_t* _
   const bool all = *fr_all != 0;
   const int64_t n = all ? h1 - h0 : (int64_t)*fcnt0;
   if ((int64_t)blockIdx.x >= n) return;  // uniform
+  const ArcLabels al = arc_labels(asrc);
   for (int i = threadIdx.x; i < kSlots; i += kT) tab[i] = 0ull;
   if (threadIdx.x < kGB) ghist[threadIdx.x] = 0u;
   if (threadIdx.x < 2) gcnt[threadIdx.x] = gmax[threadIdx.x] = 0u;
@@ -784,8 +785,8 @@ __device__ __forceinline__ void rows_rp(const int64_t* __restrict__ rp, int64_t 
   rpe = rp[min(r0 + RB, vend)];
 }
 
-template <int G, bool kG = false>
-__device__ __forceinline__ void rows_labels(u32 (&lab)[kChunks], const int32_t* __restrict__ al,
+template <int G, bool kG = false, typename Src = const int32_t*>
+__device__ __forceinline__ void rows_labels(u32 (&lab)[kChunks], const Src& al,
                                             int64_t r0, int64_t vend, int64_t rpl, int64_t rpe,
                                             int lane, const int32_t* __restrict__ Lg = nullptr) {
   constexpr int RB = 512 / G;
@@ -844,7 +845,7 @@ constexpr int kRowsGB = 16;  // giant-label histogram buckets per row (group) of
 // 64 / G * kRowsGB histogram buckets)
 template <int G, bool kG = false>
 __device__ __forceinline__ void rows_bin(int64_t bid, int64_t nblk, u64* htab_all, u32* ghist_all,
-                                         const int64_t* __restrict__ rp, const int32_t* __restrict__ al,
+                                         const int64_t* __restrict__ rp, const ArcLabels& al,
                                          int32_t* __restrict__ Ln, int64_t vbeg, int64_t vend,
                                          const int32_t* __restrict__ flist, const int32_t* __restrict__ fcnt_b,
                                          const int32_t* __restrict__ fr_all, int sort_after,
@@ -881,6 +882,64 @@ __device__ __forceinline__ void rows_bin(int64_t bid, int64_t nblk, u64* htab_al
   u32* hg = ghist_all + w * (64 / G * kGB) + (lane / G) * kGB;
   const int gj = lane & (G - 1);   // G >= kGB when giant: lane gj < kGB owns bucket gj
   if (gj < kGB) hg[gj] = 0u;
+  const int gbase = lane & ~(G - 1);
+  const u64 gm = G == 64 ? ~0ull : ((1ull << (G & 63)) - 1ull);
+  auto tally_batch = [&](const u32 (&lab)[kChunks], u32 vbits, int64_t r0) {
+#pragma unroll
+    for (int c = 0; c < kChunks; ++c) {
+      const u32 lb = (vbits >> c) & 1u ? lab[c] : kNone;
+      u64 act = __ballot(lb != kNone);
+      u64 best = 0ull;
+      if constexpr (G >= kGB) if (giant) {
+        const u64 gb = __ballot(lb == Gl);
+        const u32 cg = (u32)__popcll((gb >> gbase) & gm);
+        if (lb != Gl && lb != kNone) atomicAdd(&hg[hash_slot(lb, 28)], 1u);
+        __builtin_amdgcn_wave_barrier();  // no reordering across (LDS ops of a wave complete in order)
+        u32 mx = 0u;
+        if (gj < kGB) {
+          mx = hg[gj];
+          hg[gj] = 0u;
+        }
+        for (int off = G >> 1; off > 0; off >>= 1) mx = max(mx, (u32)lane::lane_xor(mx, off, lane));
+        const bool dec = cg > mx;
+        if (__ballot(lb != kNone && !dec) == 0ull) {  // uniform: every row decided
+          best = dec ? tally(cg, Gl) : 0ull;
+          act = 0ull;
+        }
+      }
+      for (int round = 0; act; ++round) {
+        // uniform: a label-dense chunk after sort_after rounds
+        if (round == sort_after) {
+          best = group_mode_hash<G>(lb, lane, htab);
+          break;
+        }
+        const u64 my = (act >> gbase) & gm;
+        const int lead = gbase + (my ? (__ffsll((unsigned long long)my) - 1) : 0);
+        const u32 x = group_lead<G>(lb, act, lane, lead);
+        const u64 mm = __ballot(((act >> lane) & 1ull) && lb == x);
+        const u32 cn = (u32)__popcll((mm >> gbase) & gm);
+        if (my) best = umax64(best, tally(cn, x));
+        act &= ~mm;
+        act &= ~decided_groups<G>(act, my, best, gbase, gm);
+      }
+      const int64_t row = r0 + c * (64 / G) + lane / G;
+      if ((lane & (G - 1)) == 0 && row < vend && best) Ln[row] = (int32_t)(~(u32)best);
+    }
+  };
+  // a sparse al[] (gword[GW_AL_SPARSE]; uniform): one batch at a time, every vote through its arc
+  // giant bit (arc_label).  The rings below keep reading a dense al[] as they did; the
+  // supersteps that read a sparse one settle their rows from the bits first and come here in
+  // list mode (above), so this loop only serves a settle that did not apply.
+  if (!kG && al.on) {
+    for (; bi < nb; bi += stride) {
+      int64_t rpl, rpe;
+      rows_rp<G>(rp, vbeg + bi * RB, vend, lane, rpl, rpe);
+      u32 lab[kChunks];
+      rows_labels<G, false, ArcLabels>(lab, al, vbeg + bi * RB, vend, rpl, rpe, lane, Lg);
+      tally_batch(lab, 0xFFu, vbeg + bi * RB);
+    }
+    return;
+  }
   if constexpr (G == 64 && !kG) {
     // g64 (33-64 arcs, eight rows per batch): the two-batch form -- the ring's extra
     // label set cost C2 (SBM, nearly every row here) 61.5 -> 57.6 GTEPS (same box)
@@ -888,7 +947,7 @@ __device__ __forceinline__ void rows_bin(int64_t bid, int64_t nblk, u64* htab_al
     rows_rp<G>(rp, vbeg + bi * RB, vend, lane, rpl0, rpe0);
     if (bi + stride < nb) rows_rp<G>(rp, vbeg + (bi + stride) * RB, vend, lane, rpl1, rpe1);
     u32 lab[kChunks];
-    rows_labels<G, kG>(lab, al, vbeg + bi * RB, vend, rpl0, rpe0, lane, Lg);
+    rows_labels<G, kG>(lab, al.p, vbeg + bi * RB, vend, rpl0, rpe0, lane, Lg);
     const int gbase = lane & ~(G - 1);
     const u64 gm = G == 64 ? ~0ull : ((1ull << (G & 63)) - 1ull);
     while (true) {
@@ -897,7 +956,7 @@ __device__ __forceinline__ void rows_bin(int64_t bid, int64_t nblk, u64* htab_al
       if (bn + stride < nb) rows_rp<G>(rp, vbeg + (bn + stride) * RB, vend, lane, rpl2, rpe2);
       u32 labn[kChunks];
       if (bn < nb) {
-        rows_labels<G, kG>(labn, al, vbeg + bn * RB, vend, rpl1, rpe1, lane, Lg);
+        rows_labels<G, kG>(labn, al.p, vbeg + bn * RB, vend, rpl1, rpe1, lane, Lg);
       } else {
   #pragma unroll
         for (int c = 0; c < kChunks; ++c) labn[c] = kNone;
@@ -955,50 +1014,6 @@ __device__ __forceinline__ void rows_bin(int64_t bid, int64_t nblk, u64* htab_al
 
     return;
   } else {
-  const int gbase = lane & ~(G - 1);
-  const u64 gm = G == 64 ? ~0ull : ((1ull << (G & 63)) - 1ull);
-  auto tally_batch = [&](const u32 (&lab)[kChunks], u32 vbits, int64_t r0) {
-#pragma unroll
-    for (int c = 0; c < kChunks; ++c) {
-      const u32 lb = (vbits >> c) & 1u ? lab[c] : kNone;
-      u64 act = __ballot(lb != kNone);
-      u64 best = 0ull;
-      if constexpr (G >= kGB) if (giant) {
-        const u64 gb = __ballot(lb == Gl);
-        const u32 cg = (u32)__popcll((gb >> gbase) & gm);
-        if (lb != Gl && lb != kNone) atomicAdd(&hg[hash_slot(lb, 28)], 1u);
-        __builtin_amdgcn_wave_barrier();  // no reordering across (LDS ops of a wave complete in order)
-        u32 mx = 0u;
-        if (gj < kGB) {
-          mx = hg[gj];
-          hg[gj] = 0u;
-        }
-        for (int off = G >> 1; off > 0; off >>= 1) mx = max(mx, (u32)lane::lane_xor(mx, off, lane));
-        const bool dec = cg > mx;
-        if (__ballot(lb != kNone && !dec) == 0ull) {  // uniform: every row decided
-          best = dec ? tally(cg, Gl) : 0ull;
-          act = 0ull;
-        }
-      }
-      for (int round = 0; act; ++round) {
-        // uniform: a label-dense chunk after sort_after rounds
-        if (round == sort_after) {
-          best = group_mode_hash<G>(lb, lane, htab);
-          break;
-        }
-        const u64 my = (act >> gbase) & gm;
-        const int lead = gbase + (my ? (__ffsll((unsigned long long)my) - 1) : 0);
-        const u32 x = group_lead<G>(lb, act, lane, lead);
-        const u64 mm = __ballot(((act >> lane) & 1ull) && lb == x);
-        const u32 cn = (u32)__popcll((mm >> gbase) & gm);
-        if (my) best = umax64(best, tally(cn, x));
-        act &= ~mm;
-        act &= ~decided_groups<G>(act, my, best, gbase, gm);
-      }
-      const int64_t row = r0 + c * (64 / G) + lane / G;
-      if ((lane & (G - 1)) == 0 && row < vend && best) Ln[row] = (int32_t)(~(u32)best);
-    }
-  };
   if constexpr (kG) {
     // gather mode (al = col): a vote is a column load and a dependent label gather, so
     // the ring runs them a step apart -- at the tally of batch i the gathers of batch
@@ -1010,10 +1025,10 @@ __device__ __forceinline__ void rows_bin(int64_t bid, int64_t nblk, u64* htab_al
     u32 cc[D][kChunks], labg[D][kChunks], vb[D];
 #pragma unroll
     for (int k = 0; k < D; ++k) rows_rp_nb<G>(rp, vbeg + (bi + k * stride) * RB, vend, lane, rpl[k], rpe[k]);
-    rows_labels_nb<G, false>(cc[0], vb[0], al, vbeg + bi * RB, vend, rpl[0], rpe[0], lane);
+    rows_labels_nb<G, false>(cc[0], vb[0], al.p, vbeg + bi * RB, vend, rpl[0], rpe[0], lane);
 #pragma unroll
     for (int c = 0; c < kChunks; ++c) labg[0][c] = (u32)Lg[(int32_t)(cc[0][c])];
-    rows_labels_nb<G, false>(cc[1], vb[1], al, vbeg + (bi + stride) * RB, vend, rpl[1], rpe[1], lane);
+    rows_labels_nb<G, false>(cc[1], vb[1], al.p, vbeg + (bi + stride) * RB, vend, rpl[1], rpe[1], lane);
     while (true) {
 #pragma unroll
       for (int k = 0; k < D; ++k) {
@@ -1022,7 +1037,7 @@ __device__ __forceinline__ void rows_bin(int64_t bid, int64_t nblk, u64* htab_al
         rows_rp_nb<G>(rp, vbeg + (bi + D * stride) * RB, vend, lane, rpl[k], rpe[k]);
 #pragma unroll
         for (int c = 0; c < kChunks; ++c) labg[k1][c] = (u32)Lg[(int32_t)(cc[k1][c])];
-        rows_labels_nb<G, false>(cc[k2], vb[k2], al, vbeg + (bi + 2 * stride) * RB, vend, rpl[k2], rpe[k2], lane);
+        rows_labels_nb<G, false>(cc[k2], vb[k2], al.p, vbeg + (bi + 2 * stride) * RB, vend, rpl[k2], rpe[k2], lane);
         __builtin_amdgcn_sched_barrier(0);
         tally_batch(labg[k], vb[k], vbeg + bi * RB);
         bi += stride;
@@ -1042,14 +1057,14 @@ __device__ __forceinline__ void rows_bin(int64_t bid, int64_t nblk, u64* htab_al
 #pragma unroll
   for (int k = 0; k < D; ++k) rows_rp_nb<G>(rp, vbeg + (bi + k * stride) * RB, vend, lane, rpl[k], rpe[k]);
 #pragma unroll
-  for (int k = 0; k < D - 1; ++k) rows_labels_nb<G, kG>(lab[k], vb[k], al, vbeg + (bi + k * stride) * RB, vend, rpl[k], rpe[k], lane, Lg);
+  for (int k = 0; k < D - 1; ++k) rows_labels_nb<G, kG>(lab[k], vb[k], al.p, vbeg + (bi + k * stride) * RB, vend, rpl[k], rpe[k], lane, Lg);
   while (true) {
 #pragma unroll
     for (int k = 0; k < D; ++k) {
       __builtin_amdgcn_sched_barrier(0);
       rows_rp_nb<G>(rp, vbeg + (bi + D * stride) * RB, vend, lane, rpl[k], rpe[k]);
       const int kl = (k + D - 1) % D;
-      rows_labels_nb<G, kG>(lab[kl], vb[kl], al, vbeg + (bi + (D - 1) * stride) * RB, vend, rpl[kl], rpe[kl], lane, Lg);
+      rows_labels_nb<G, kG>(lab[kl], vb[kl], al.p, vbeg + (bi + (D - 1) * stride) * RB, vend, rpl[kl], rpe[kl], lane, Lg);
       __builtin_amdgcn_sched_barrier(0);
       tally_batch(lab[k], vb[k], vbeg + bi * RB);
       bi += stride;
@@ -1062,7 +1077,7 @@ __device__ __forceinline__ void rows_bin(int64_t bid, int64_t nblk, u64* htab_al
 
 template <int G, bool kG = false>
 __global__ __launch_bounds__(256) void k_lpa_rows(const int64_t* __restrict__ rp,
-                                                  const int32_t* __restrict__ al,
+                                                  const ArcSrc asrc,
                                                   int32_t* __restrict__ Ln, int64_t vbeg,
                                                   int64_t vend, const int32_t* __restrict__ flist,
                                                   const int32_t* __restrict__ fcnt_b,
@@ -1071,8 +1086,8 @@ __global__ __launch_bounds__(256) void k_lpa_rows(const int64_t* __restrict__ rp
                                                   const int32_t* __restrict__ Lg) {
   __shared__ u32 ghist_all[4 * (64 / G) * kRowsGB];
   __shared__ u64 htab_all[4 * kRowsHashSlots];
-  rows_bin<G, kG>(blockIdx.x, gridDim.x, htab_all, ghist_all, rp, al, Ln, vbeg, vend, flist, fcnt_b, fr_all,
-                  sort_after, gsel, Lg);
+  rows_bin<G, kG>(blockIdx.x, gridDim.x, htab_all, ghist_all, rp, arc_labels(asrc), Ln, vbeg, vend, flist, fcnt_b,
+                  fr_all, sort_after, gsel, Lg);
 }
 
 // ---------------------------------------------------------------------------
@@ -1097,7 +1112,7 @@ struct FusedBins {
 
 template <int kWide>
 __global__ __launch_bounds__(256, LPA_FUSED_WAVES) void k_bins_fused(const FusedBins fb, const int64_t* __restrict__ rp,
-                                                    const int32_t* __restrict__ al, int32_t* __restrict__ Ln,
+                                                    const ArcSrc asrc, int32_t* __restrict__ Ln,
                                                     const int32_t* __restrict__ flist,
                                                     const int32_t* __restrict__ fcnt,
                                                     const int32_t* __restrict__ fr_all, int pmax, int sort_after) {
@@ -1111,6 +1126,7 @@ __global__ __launch_bounds__(256, LPA_FUSED_WAVES) void k_bins_fused(const Fused
   const int b = fb.bin[k];
   const int64_t v0 = fb.vb[k], v1 = fb.ve[k];
   const int32_t* fc = fcnt + b;
+  const ArcLabels al = arc_labels(asrc);
   if constexpr (kWide) {
     if (b == BIN_W16) wave_bin<16>(bid, nblk, tab, lst, rp, al, Ln, v0, v1, flist, fc, fr_all, pmax, nullptr, nullptr);
     else if (b == BIN_W8) wave_bin<8>(bid, nblk, tab, lst, rp, al, Ln, v0, v1, flist, fc, fr_all, pmax, nullptr, nullptr);
@@ -1161,24 +1177,6 @@ __device__ __forceinline__ Segment load_unit(const Segment* __restrict__ units, 
   return d;
 }
 
-// unconditional loads (the address is clamped into the unit; lanes past the unit's
-// end are masked at use time), so the compiler can count vmcnt exactly
-__device__ __forceinline__ void unit_load(u32 (&raw)[kChunks], const int32_t* __restrict__ al,
-                                          const Segment& d, int lane) {
-  const int len = d.len & 1023;
-  if (__builtin_amdgcn_readfirstlane(len) == 0) {  // frontier-clean unit: no loads
-#pragma unroll
-    for (int c = 0; c < kChunks; ++c) raw[c] = kNone;
-    return;
-  }
-  const int last = len > 0 ? len - 1 : 0;
-#pragma unroll
-  for (int c = 0; c < kChunks; ++c) {
-    const int off = c * 64 + lane;
-    raw[c] = ld_stream(al + d.begin + (off < last ? off : last));
-  }
-}
-
 // 64 work items' unit descriptors in one load per lane (lane k: item i0 + k * stride;
 // empty past the list or for a block-tier unit), read back by readlane
 struct UnitBatch {
@@ -1219,26 +1217,32 @@ __device__ __forceinline__ Segment unit_at(const UnitBatch& cur, const UnitBatch
 constexpr int kUnitsRing = 4;
 
 // branch-free unit_load (k_lpa_units' ring): an empty unit loads al[begin] (begin 0)
-__device__ __forceinline__ void unit_load_nb(u32 (&raw)[kChunks], const int32_t* __restrict__ al,
+// (bw: the unit's arc giant bit words, applied where the unit is tallied -- arc_bits_load)
+__device__ __forceinline__ void unit_load_nb(u32 (&raw)[kChunks], u32& bw, const ArcLabels& al,
                                              const Segment& d, int lane) {
   const int len = d.len & 1023;
   const int last = len > 0 ? len - 1 : 0;
 #pragma unroll
   for (int c = 0; c < kChunks; ++c) {
     const int off = c * 64 + lane;
-    raw[c] = ld_stream(al + d.begin + (off < last ? off : last));
+    raw[c] = ld_stream(al.p + d.begin + (off < last ? off : last));
   }
+  bw = arc_bits_load<kChunks>(al, d.begin, lane);
 }
 
 // tally one unit whose labels are in `raw` (loaded earlier)
-__device__ __forceinline__ void unit_tally(const u32 (&raw)[kChunks], const Segment& d, int64_t u,
+__device__ __forceinline__ void unit_tally(const u32 (&raw)[kChunks], u32 bw, const ArcLabels& al,
+                                           const Segment& d, int64_t u,
                                            u64* __restrict__ stage, int32_t* __restrict__ ucnt,
                                            u64* tab, uint16_t* lst, int lane, u64 lt, int pmax) {
   const int len = d.len & 1023;
   if (len == 0) return;
   u32 lab[kChunks];
 #pragma unroll
-  for (int c = 0; c < kChunks; ++c) lab[c] = c * 64 + lane < len ? raw[c] : kNone;
+  for (int c = 0; c < kChunks; ++c) lab[c] = raw[c];
+  arc_bits_apply<kChunks>(lab, bw, al, d.begin);
+#pragma unroll
+  for (int c = 0; c < kChunks; ++c) lab[c] = c * 64 + lane < len ? lab[c] : kNone;
   const int nch = (len + 63) >> 6;
   // staging slots of this unit: stage[begin .. begin + words) (words <= len)
   u64* st = stage + d.begin;
@@ -1262,7 +1266,7 @@ __device__ __forceinline__ void unit_tally(const u32 (&raw)[kChunks], const Segm
   }
 }
 
-__global__ __launch_bounds__(256) void k_lpa_units(const int32_t* __restrict__ al,
+__global__ __launch_bounds__(256) void k_lpa_units(const ArcSrc asrc,
                                                    const Segment* __restrict__ units, int64_t nunits,
                                                    u64* __restrict__ stage,
                                                    int32_t* __restrict__ ucnt,
@@ -1288,6 +1292,7 @@ __global__ __launch_bounds__(256) void k_lpa_units(const int32_t* __restrict__ a
   // the wave's table is cleared only by waves with work (a frontier superstep lists
   // few units: most of the grid leaves at once)
   for (int i = lane; i < kCap; i += 64) tab[i] = 0ull;
+  const ArcLabels al = arc_labels(asrc);
   // unit descriptors by 64-unit batches (lane k: work item ib + k * stride), the next
   // batch loaded half a batch ahead; kUnitsRing label sets in an unrolled ring (labels
   // kUnitsRing - 1 units ahead), branch-free loads: no label load waits on a
@@ -1299,16 +1304,16 @@ __global__ __launch_bounds__(256) void k_lpa_units(const int32_t* __restrict__ a
   nxt.len = 0;
   nxt.id = 0;
   int p = 0;
-  u32 rl[D][kChunks];
+  u32 rl[D][kChunks], rb[D];
 #pragma unroll
-  for (int k = 0; k < D - 1; ++k) unit_load_nb(rl[k], al, unit_at(cur, nxt, k), lane);
+  for (int k = 0; k < D - 1; ++k) unit_load_nb(rl[k], rb[k], al, unit_at(cur, nxt, k), lane);
   while (true) {
 #pragma unroll
     for (int k = 0; k < D; ++k) {
-      unit_load_nb(rl[(k + D - 1) % D], al, unit_at(cur, nxt, p + D - 1), lane);
+      unit_load_nb(rl[(k + D - 1) % D], rb[(k + D - 1) % D], al, unit_at(cur, nxt, p + D - 1), lane);
       const Segment d = unit_at(cur, nxt, p);
       const int64_t id = (int64_t)__builtin_amdgcn_readlane(cur.id, p);
-      unit_tally(rl[k], d, id, stage, ucnt, tab, lst, lane, lt, pmax);
+      unit_tally(rl[k], rb[k], al, d, id, stage, ucnt, tab, lst, lane, lt, pmax);
       if (ib + (int64_t)(p + 1) * stride >= ui.n) return;
       ++p;
       if (p == 32) nxt = unit_batch(units, ui, ib + 64 * stride, stride, lane);
@@ -1330,9 +1335,12 @@ __global__ __launch_bounds__(256) void k_lpa_units(const int32_t* __restrict__ a
 // Block 0 also zeroes the undecided-unit list count (*ndec) for k_hub_decide.
 // (k_lpa_units_code2 below: the same from the 2-bit giant codes, when the refresh took
 // them -- gsel[GW_CODE]; this form returns at once then.)
+// (bits: the arc giant bit words of a possibly sparse al[], T = int32_t; the giant codes carry none)
 template <typename T>
-__device__ __forceinline__ void unit_load_nb_t(u32 (&raw)[kChunks], const T* __restrict__ al, const Segment& d,
-                                               int lane) {
+__device__ __forceinline__ void unit_load_nb_t(u32 (&raw)[kChunks], u32& bw, const T* __restrict__ al,
+                                               const ArcLabels& bits, const Segment& d, int lane) {
+  if constexpr (sizeof(T) == 4) bw = arc_bits_load<kChunks>(bits, d.begin, lane);
+  else bw = 0u;
   const int len = d.len & 1023;
   const int last = len > 0 ? len - 1 : 0;
 #pragma unroll
@@ -1343,7 +1351,7 @@ __device__ __forceinline__ void unit_load_nb_t(u32 (&raw)[kChunks], const T* __r
   }
 }
 template <typename T>
-__global__ __launch_bounds__(256) void k_lpa_units_giant(const T* __restrict__ al,
+__global__ __launch_bounds__(256) void k_lpa_units_giant(const T* __restrict__ al, const ArcSrc asrc,
                                                          const Segment* __restrict__ units, int64_t nunits,
                                                          const int32_t* __restrict__ gsel,
                                                          uint32_t* __restrict__ ugc, uint32_t* __restrict__ umx,
@@ -1360,15 +1368,19 @@ __global__ __launch_bounds__(256) void k_lpa_units_giant(const T* __restrict__ a
   const int64_t stride = (int64_t)gridDim.x * 4;
   int64_t u = (int64_t)blockIdx.x * 4 + w;
   if (u >= nunits) return;  // no block-level barriers in this kernel
+  const ArcLabels bsrc = arc_labels(asrc);
   UnitIds ui;
   ui.n = nunits;
   ui.lim = nunits;
   ui.list = nullptr;
-  auto one = [&](const u32 (&raw)[kChunks], const Segment& d, int64_t id) {
+  auto one = [&](const u32 (&raw)[kChunks], u32 bw, const Segment& d, int64_t id) {
     const int len = d.len & 1023;
     u32 lab[kChunks];
 #pragma unroll
-    for (int c = 0; c < kChunks; ++c) lab[c] = c * 64 + lane < len ? raw[c] : kNone;
+    for (int c = 0; c < kChunks; ++c) lab[c] = raw[c];
+    if constexpr (sizeof(T) == 4) arc_bits_apply<kChunks>(lab, bw, bsrc, d.begin);
+#pragma unroll
+    for (int c = 0; c < kChunks; ++c) lab[c] = c * 64 + lane < len ? lab[c] : kNone;
     const u32 cg = wave_sum_u32(giant_count<kChunks>(lab, kChunks, G, hist, kGiantLg));
     __builtin_amdgcn_wave_barrier();  // no reordering across (LDS ops of a wave complete in order)
     const u32 b = hist[lane];
@@ -1387,14 +1399,14 @@ __global__ __launch_bounds__(256) void k_lpa_units_giant(const T* __restrict__ a
   nxt.len = 0;
   nxt.id = 0;
   int p = 0;
-  u32 rl[D][kChunks];
+  u32 rl[D][kChunks], rb[D];
 #pragma unroll
-  for (int k = 0; k < D - 1; ++k) unit_load_nb_t<T>(rl[k], al, unit_at(cur, nxt, k), lane);
+  for (int k = 0; k < D - 1; ++k) unit_load_nb_t<T>(rl[k], rb[k], al, bsrc, unit_at(cur, nxt, k), lane);
   while (true) {
 #pragma unroll
     for (int k = 0; k < D; ++k) {
-      unit_load_nb_t<T>(rl[(k + D - 1) % D], al, unit_at(cur, nxt, p + D - 1), lane);
-      one(rl[k], unit_at(cur, nxt, p), ib + (int64_t)p * stride);
+      unit_load_nb_t<T>(rl[(k + D - 1) % D], rb[(k + D - 1) % D], al, bsrc, unit_at(cur, nxt, p + D - 1), lane);
+      one(rl[k], rb[k], unit_at(cur, nxt, p), ib + (int64_t)p * stride);
       if (ib + (int64_t)(p + 1) * stride >= nunits) return;
       ++p;
       if (p == 32) nxt = unit_batch(units, ui, ib + 64 * stride, stride, lane);
@@ -1456,20 +1468,22 @@ __global__ __launch_bounds__(256) void k_units_pure(const int32_t* __restrict__ 
         if (off && off + n > 64 && wq + 1 < nwords) bits |= abits[wq + 1] << (64 - off);
         u64 clear = ~bits & (n == 64 ? ~0ull : ((1ull << n) - 1ull));
         // the clear bits' al[] entries eight at a time, every load issued before the first
-        // compare (unused slots re-read the chunk's first entry): a chunk of a hub row holds
-        // several joiners, and one dependent load after another cost ~5x
+        // compare (unused slots re-read the round's first clear entry -- not the chunk's
+        // first entry: under a sparse al[] that one is undefined when its bit is set): a
+        // chunk of a hub row holds several joiners, and one dependent load after another
+        // cost ~5x
         while (clear && ok) {
           int pos[8];
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
-            pos[k] = clear ? __ffsll((unsigned long long)clear) - 1 : 0;
+            pos[k] = clear ? __ffsll((unsigned long long)clear) - 1 : pos[0];
             clear &= clear - 1ull;
           }
           int32_t v[8];
 #pragma unroll
           for (int k = 0; k < 8; ++k) v[k] = al[a + pos[k]];
 #pragma unroll
-          for (int k = 0; k < 8; ++k) ok = ok && v[k] == G;  // (a padding slot's arc is the chunk's too)
+          for (int k = 0; k < 8; ++k) ok = ok && v[k] == G;  // (a padding slot repeats slot 0)
         }
       }
     }
@@ -1746,6 +1760,14 @@ __global__ __launch_bounds__(256) void k_abits_pass(const int32_t* __restrict__ 
                                                     unsigned long long* __restrict__ abits) {
   if (gword[GW_TRY] == 0) return;  // uniform: no settle this superstep
   if (gword[GW_ABITS_OK] != 0) return;  // uniform: the kept bits serve (no block writes that word here)
+  // a sparse al[] (gword[GW_AL_SPARSE]) does not hold the labels of its set bits, so the bits are
+  // not re-derived from it: every scatter since the sparse rebuild cleared the bits of the
+  // columns that left Gb, so for G = Gb they are already the lower bound the settle needs
+  // (valid as after a pass); under another G the settle is skipped and the rows are tallied
+  if (gword[GW_AL_SPARSE] != 0) {
+    if (blockIdx.x == 0 && threadIdx.x == 0 && gword[GW_G] == gword[GW_AL_GB]) gword[GW_ABITS_PASS] = 1;
+    return;
+  }
   if (blockIdx.x == 0 && threadIdx.x == 0) gword[GW_ABITS_PASS] = 1;
   const u32 G = (u32)gword[GW_G];
   const int lane = threadIdx.x & 63;
@@ -2589,7 +2611,7 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
       // (giant mode: the undecided rows only; a grid sized to few rows measured slower
       // at C5, superstep 2 48.7 -> 54.3 ms, and the same at C3)
       hipLaunchKernelGGL((k_lpa_block<14, kBlockMaxDeg2 / kSegArcs>), dim3(cap_grid(hl - h2, 1024)),
-                         dim3(kBlockMaxDeg2 / kSegArcs * 64), 0, st, g->rp, g->al, Lown, h2, hl, blist, bcnt,
+                         dim3(kBlockMaxDeg2 / kSegArcs * 64), 0, st, g->rp, arc_src(g), Lown, h2, hl, blist, bcnt,
                          ball, pmax, bsel);
       LPA_HIP(hipGetLastError());
     }
@@ -2599,7 +2621,7 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
   auto launch_block_narrow = [&](hipStream_t st) -> int {
     const int64_t nb = g->n_hub - g->hub_lane_begin;
     hipLaunchKernelGGL((k_lpa_block<13, kBlockMaxDeg / kSegArcs>), dim3(cap_grid(nb, 2048)),
-                       dim3(kBlockMaxDeg / kSegArcs * 64), 0, st, g->rp, g->al, Lown, g->hub_lane_begin, g->n_hub,
+                       dim3(kBlockMaxDeg / kSegArcs * 64), 0, st, g->rp, arc_src(g), Lown, g->hub_lane_begin, g->n_hub,
                        blist, bcnt, ball, pmax, bsel);
     LPA_HIP(hipGetLastError());
     return LPA_OK;
@@ -2633,7 +2655,7 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
   auto launch_units = [&]() -> int {
     if (giant_units && g->n_segs > 0) {
       hipLaunchKernelGGL(k_lpa_units_giant<int32_t>, dim3(cap_grid((g->n_segs + 3) / 4, 2048)), dim3(256), 0, s,
-                         g->al, g->segs, g->n_segs, gsel, g->ugc, g->umx, g->gdec);
+                         g->al, arc_src(g), g->segs, g->n_segs, gsel, g->ugc, g->umx, g->gdec);
       LPA_HIP(hipGetLastError());
       if (code_tally_now(g)) {  // the form on the giant codes (one of the two returns at once)
         hipLaunchKernelGGL(k_lpa_units_code2, dim3(cap_grid((g->n_segs + 3) / 4, 2048)), dim3(256), 0, s,
@@ -2656,7 +2678,7 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
     LPA_TRY(mark(0, s));
     if (n_units > 0 && giant_units) {
       hipLaunchKernelGGL(k_lpa_units, dim3(cap_grid((n_units + 3) / 4, 2048)), dim3(256), 0, s,
-                         g->al, g->segs, n_units, g->stage, g->ucnt, g->ulist2, g->gdec + GD_UNITS,
+                         arc_src(g), g->segs, n_units, g->stage, g->ucnt, g->ulist2, g->gdec + GD_UNITS,
                          g->gdec + GD_ALL, pmax);
       LPA_HIP(hipGetLastError());
     } else if (n_units > 0 && settle4 && g->units_pure) {
@@ -2667,12 +2689,12 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
                          g->abits, g->arcs, g->segs, n_units, g->gword, g->stage, g->ucnt, g->ulist2);
       LPA_HIP(hipGetLastError());
       hipLaunchKernelGGL(k_lpa_units, dim3(cap_grid((n_units + 3) / 4, 2048)), dim3(256), 0, s,
-                         g->al, g->segs, n_units, g->stage, g->ucnt, g->ulist2, g->gword + GW_PURE_CNT,
+                         arc_src(g), g->segs, n_units, g->stage, g->ucnt, g->ulist2, g->gword + GW_PURE_CNT,
                          g->gword + GW_PURE_ALL, pmax);
       LPA_HIP(hipGetLastError());
     } else if (n_units > 0) {
       hipLaunchKernelGGL(k_lpa_units, dim3(cap_grid((n_units + 3) / 4, 2048)), dim3(256), 0, s,
-                         g->al, g->segs, n_units, g->stage, g->ucnt, g->ulist, fcnt + kFcntUnits, fr_all, pmax);
+                         arc_src(g), g->segs, n_units, g->stage, g->ucnt, g->ulist, fcnt + kFcntUnits, fr_all, pmax);
       LPA_HIP(hipGetLastError());
       LPA_TRACE_POINT("seg");
     }
@@ -2682,7 +2704,7 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
   if (!units_last) LPA_TRY(launch_units());
   // gather mode (lpa_build): the votes are Lc[col[i]] -- the kernels read col and Lc
   const bool gnow = gather_now(g);
-  const int32_t* vsrc = gnow ? g->col : g->al;
+  const ArcSrc vsrc = arc_src(g, gnow ? g->col : g->al);
 #define LPA_WAVE_LAUNCH(BIN, NC, ST, FR)                                                          \
   {                                                                                           \
     const int64_t n = bb[BIN + 1] - bb[BIN];                                                  \
@@ -2770,10 +2792,10 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
     LPA_TRY(mark(2 * (b0 + 1), st));
     if (fb.n > 0) {
       if (wide)
-        hipLaunchKernelGGL(k_bins_fused<1>, dim3((unsigned)tot), dim3(256), 0, st, fb, g->rp, g->al, Lown, g->flist,
+        hipLaunchKernelGGL(k_bins_fused<1>, dim3((unsigned)tot), dim3(256), 0, st, fb, g->rp, arc_src(g), Lown, g->flist,
                            fcnt, fr_bins, pmax, sort_after);
       else
-        hipLaunchKernelGGL(k_bins_fused<0>, dim3((unsigned)tot), dim3(256), 0, st, fb, g->rp, g->al, Lown, g->flist,
+        hipLaunchKernelGGL(k_bins_fused<0>, dim3((unsigned)tot), dim3(256), 0, st, fb, g->rp, arc_src(g), Lown, g->flist,
                            fcnt, fr_bins, pmax, sort_after);
       LPA_HIP(hipGetLastError());
     }

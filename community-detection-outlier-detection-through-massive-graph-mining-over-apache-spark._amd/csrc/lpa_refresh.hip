@@ -4,6 +4,7 @@
 // bits, the giant-code refresh, and their host schedule (launch_refresh and its callers'
 // forms).
 #include <algorithm>
+#include <type_traits>
 
 #include "lpa_codes.h"
 #include "lpa_device.h"
@@ -301,9 +302,17 @@ __global__ __launch_bounds__(256) void k_al_scatter(const int32_t* __restrict__ 
   // non-folded rebuild follows this kernel and sets gword[GW_ABITS_OK] itself.
   const bool keep = keep_bits != 0 && !rebuild;
   if (blockIdx.x == 0 && threadIdx.x == 0 && (!rebuild || col_fold) && !keep) gword[GW_ABITS_OK] = 0;
-  const int32_t Gk = gword[GW_G];
+  // A sparse al[] (gword[GW_AL_SPARSE], read before block 0 may clear it below: uniform over the
+  // grid only while no rebuild is folded in, which is when it is used) keeps its invariant in
+  // EVERY superstep: a changed column whose gbits bit is set (it held Gb when the sparse
+  // rebuild ran) and whose new label is not Gb clears the bit of each of its positions and
+  // writes al[] there; any other changed column writes al[] and leaves the bits alone (its
+  // bits are clear already: a joiner ends with a clear bit and al = Gb).  Bits are only ever
+  // cleared, so a repeated clear is harmless.
+  const bool sparse = !rebuild && gword[GW_AL_SPARSE] != 0;
+  const int32_t Gk = sparse ? gword[GW_AL_GB] : gword[GW_G];
   auto left_g = [&](int64_t u, int32_t lab) -> bool {
-    return keep && lab != Gk && ((gbits[u >> 5] >> (u & 31)) & 1u);
+    return (keep || sparse) && lab != Gk && ((gbits[u >> 5] >> (u & 31)) & 1u);
   };
   // The next superstep tallies every row after a rebuild, with the frontier off, or
   // when more than fr_thr arcs changed: then nearly every row has a changed neighbour
@@ -317,7 +326,10 @@ __global__ __launch_bounds__(256) void k_al_scatter(const int32_t* __restrict__ 
   // col_fold (captured converged supersteps): a wanted rebuild is done here, the plain
   // form, instead of by a k_al_rebuild_hot launch that nearly always returns at once
   // (one dependent launch fewer per converged superstep)
-  if (rebuild && col_fold) rebuild_all(col_fold, arcs, Ln, al);
+  if (rebuild && col_fold) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) gword[GW_AL_SPARSE] = 0;  // a dense al[] again
+    rebuild_all(col_fold, arcs, Ln, al);
+  }
   // one-chunk columns from the list: a lane each, longer rows of positions by the wave
   if (!rebuild) {
     const int64_t nl = (int64_t)counters[0];
@@ -405,7 +417,10 @@ __global__ __launch_bounds__(256) void k_al_rebuild(const unsigned long long* __
                                                     const int32_t* __restrict__ Ln,
                                                     int32_t* __restrict__ al, int32_t* __restrict__ gword) {
   if (kIfWanted && !rebuild_wanted(counters, thr)) return;
-  if (blockIdx.x == 0 && threadIdx.x == 0) gword[GW_ABITS_OK] = 0;  // no arc giant bits from this form
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    gword[GW_ABITS_OK] = 0;   // no arc giant bits from this form
+    gword[GW_AL_SPARSE] = 0;  // ... and a dense al[]
+  }
   rebuild_all(col, arcs, Ln, al);
 }
 
@@ -475,6 +490,9 @@ __global__ __launch_bounds__(256) void k_giant_bits(const unsigned long long* __
   // atomic per wave on the one word serialised: ~2,500 of them, ~30 us at C3)
   __shared__ u32 bcnt;
   if (threadIdx.x == 0) bcnt = 0u;
+  // a full rebuild follows (the LDS hot-set, small or code form): al[] is dense again unless
+  // that rebuild takes the bits mode of one GPU and sets the word itself
+  if (blockIdx.x == 0 && threadIdx.x == 0) gword[GW_AL_SPARSE] = 0;
   __syncthreads();
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nzero; i += (int64_t)gridDim.x * blockDim.x)
     abits[i] = 0ull;
@@ -511,10 +529,27 @@ __global__ __launch_bounds__(256) void k_giant_bits(const unsigned long long* __
 // al[i] = lab(col[i]) over every arc by the calling grid (one wave per 512-arc batch,
 // grid-stride); bits: also the arc giant bits (abits: bit i = al[i] == G, one ballot
 // per 64 arcs), which the next superstep's full tally settles rows from (k_settle_*).
+// sparse (one GPU, bits mode, lpa_graph::sparse_al): an arc whose label is G is carried by its
+// bit alone and its al[] entry is not stored -- 98.5 % of the stores at C3 -- which every
+// reader of al[] honours while gword[GW_AL_SPARSE] is set (lpa_device.h arc_label).
+// -DLPA_SPARSE_POISON (a check build, never the default): those entries are stored after
+// all, with a valid label other than G, so a reader that misses the bit changes a label.
+__device__ __forceinline__ int32_t sparse_poison(int32_t G, int64_t nslots) {
+  return (G ^ 1) < nslots ? (G ^ 1) : (G > 0 ? G - 1 : G);
+}
+// the sparse rebuild's bookkeeping (one thread): the flag, Gb and the refresh count
+__device__ __forceinline__ void sparse_mark(int32_t* __restrict__ gword, bool sparse, int32_t G) {
+  gword[GW_AL_SPARSE] = sparse ? 1 : 0;
+  if (sparse) {
+    gword[GW_AL_GB] = G;
+    gword[GW_SPARSE_CNT] += 1;
+  }
+}
 template <typename Lab>
 __device__ __forceinline__ void rebuild_stream(Lab lab, int32_t G, bool bits, const int32_t* __restrict__ col,
                                                int64_t arcs, int32_t* __restrict__ al,
-                                               unsigned long long* __restrict__ abits) {
+                                               unsigned long long* __restrict__ abits, bool sparse = false,
+                                               int32_t poison = 0) {
   // lane-consecutive arcs: one gather instruction covers 64 consecutive arcs of
   // a row, whose sorted columns often share lines (hub rows) -> fewer L2 requests.
   // Full 512-arc batches are software-pipelined: the next batch's column loads are in
@@ -539,7 +574,13 @@ __device__ __forceinline__ void rebuild_stream(Lab lab, int32_t G, bool bits, co
 #pragma unroll
     for (int k = 0; k < 8; ++k) r[k] = lab(c[k]);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) __builtin_nontemporal_store(r[k], al + base + k * 64 + lane);
+    for (int k = 0; k < 8; ++k) {
+#ifdef LPA_SPARSE_POISON
+      __builtin_nontemporal_store(sparse && r[k] == G ? poison : r[k], al + base + k * 64 + lane);
+#else
+      if (!(sparse && r[k] == G)) __builtin_nontemporal_store(r[k], al + base + k * 64 + lane);
+#endif
+    }
     if (bits) {
       unsigned long long mine = 0ull;
 #pragma unroll
@@ -558,7 +599,11 @@ __device__ __forceinline__ void rebuild_stream(Lab lab, int32_t G, bool bits, co
       const int64_t i = base + k * 64 + lane;
       const bool v = i < arcs;
       const int32_t x = v ? lab(col[i]) : 0;
-      if (v) al[i] = x;
+#ifdef LPA_SPARSE_POISON
+      if (v) al[i] = sparse && x == G ? poison : x;
+#else
+      if (v && !(sparse && x == G)) al[i] = x;
+#endif
       const unsigned long long m = __ballot(v && x == G);
       if (bits && lane == 0 && base + k * 64 < arcs) abits[(base >> 6) + k] = m;
     }
@@ -636,10 +681,13 @@ __device__ __forceinline__ void or_arc_bits(unsigned long long* __restrict__ abi
 
 // the plain stream: this wave's whole 512-arc batches of [0, arcs), then the partial
 // last batch (one wave)
-template <typename P1, typename P2>
+// (kSparse: the bits mode of one GPU, whose stores may leave the G lanes out -- `sparse`;
+// the other modes keep their unconditional stores)
+template <bool kSparse = false, typename P1, typename P2>
 __device__ __forceinline__ void rebuild_pipe(P1 p1, P2 p2, int32_t G, bool bits, const int32_t* __restrict__ col,
                                              int64_t arcs, int32_t* __restrict__ al,
-                                             unsigned long long* __restrict__ abits) {
+                                             unsigned long long* __restrict__ abits, bool sparse = false,
+                                             int32_t poison = 0) {
   const int lane = threadIdx.x & 63;
   const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
   const int64_t wv = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -663,7 +711,14 @@ __device__ __forceinline__ void rebuild_pipe(P1 p1, P2 p2, int32_t G, bool bits,
   auto store = [&](int64_t t, const int32_t (&r)[8], int) {
     const int64_t b = base(t);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) __builtin_nontemporal_store(r[k], al + b + k * 64 + lane);
+    for (int k = 0; k < 8; ++k) {
+#ifdef LPA_SPARSE_POISON
+      __builtin_nontemporal_store(kSparse && sparse && r[k] == G ? poison : r[k], al + b + k * 64 + lane);
+#else
+      // (an exec-masked store: the sparse form leaves the G lanes out)
+      if (!(kSparse && sparse && r[k] == G)) __builtin_nontemporal_store(r[k], al + b + k * 64 + lane);
+#endif
+    }
     if (bits) {
       unsigned long long mine = 0ull;
 #pragma unroll
@@ -683,7 +738,11 @@ __device__ __forceinline__ void rebuild_pipe(P1 p1, P2 p2, int32_t G, bool bits,
       const bool v = i < arcs;
       const int32_t c = v ? col[i] : 0;
       const int32_t x = p2(c, p1(c));
-      if (v) al[i] = x;
+#ifdef LPA_SPARSE_POISON
+      if (v) al[i] = sparse && x == G ? poison : x;
+#else
+      if (v && !(sparse && x == G)) al[i] = x;
+#endif
       const unsigned long long m = __ballot(v && x == G);
       if (bits && lane == 0 && nfull + k * 64 < arcs) abits[(nfull >> 6) + k] = m;
     }
@@ -795,7 +854,7 @@ __global__ __launch_bounds__(1024) void k_al_rebuild_hot(const unsigned long lon
                                                          int32_t* __restrict__ gword,
                                                          unsigned long long* __restrict__ abits,
                                                          const u64* __restrict__ pieces, BlkInfo blk,
-                                                         const int32_t* __restrict__ skip) {
+                                                         const int32_t* __restrict__ skip, int sparse_ok) {
   if (kIfWanted && !rebuild_wanted(counters, thr)) return;
   if (skip && *skip) return;  // the giant-code refresh replaces this rebuild (k_code_mode)
   __shared__ u32 hot[kHotLabelsSingle];
@@ -827,6 +886,11 @@ __global__ __launch_bounds__(1024) void k_al_rebuild_hot(const unsigned long lon
   // ballot per 64 arcs), which the next superstep's full tally settles rows from
   // (k_settle_*)
   if (blockIdx.x == 0 && threadIdx.x == 0) gword[GW_ABITS_OK] = (bits || hyb) ? 1 : 0;
+  // one GPU, bits mode: the G arcs go unstored (rebuild_stream's note); every other mode
+  // leaves al[] dense (k_giant_bits cleared the word)
+  const bool sparse = !kRanked && bits && sparse_ok != 0;
+  if (!kRanked && blockIdx.x == 0 && threadIdx.x == 0) sparse_mark(gword, sparse, G);
+  const int32_t poison = sparse_poison(G, nbits);
   if (!bits) {
     __syncthreads();
     for (int i = threadIdx.x; i < nhot; i += 1024)
@@ -864,7 +928,8 @@ __global__ __launch_bounds__(1024) void k_al_rebuild_hot(const unsigned long lon
     // P = 1 only up to kHotMaxSlots = 2^29 slots, so every byte offset fits the voffset)
     const auto ln_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)Ln, 0, (int)(nbits * 4), 0x00020000);
     constexpr int kPast = (int)0x80000000u;  // past every record count: no request
-    auto run = [&](auto p1, auto p2, bool wbits) {
+    auto run = [&](auto p1, auto p2, bool wbits, auto sp) {
+      // (sp: the bits mode -- its stream may be sparse; it never takes the pieces)
       // uniform: labels / hybrid mode of a blocked handle (the bits mode through the
       // pieces measured slower, round 6: C5 superstep 3 13.4 -> 17.4 ms, C4 superstep 2
       // 8.9 -> 12.8 ms -- its lookups hit LDS / L2 anyway, the split arc ranges cost)
@@ -887,7 +952,7 @@ __global__ __launch_bounds__(1024) void k_al_rebuild_hot(const unsigned long lon
         if ((threadIdx.x & 63) == 0 && blockIdx.x < 512) atomicMax(&g_blk_time[3 * blockIdx.x + 2], wall_clock64());
 #endif
       } else {
-        rebuild_pipe(p1, p2, G, wbits, col, arcs, al, abits);
+        rebuild_pipe<decltype(sp)::value>(p1, p2, G, wbits, col, arcs, al, abits, sparse, poison);
       }
     };
     if (bits) {
@@ -908,7 +973,7 @@ __global__ __launch_bounds__(1024) void k_al_rebuild_hot(const unsigned long lon
             const int32_t x = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(ln_rsrc, g ? kPast : (int)((u32)c << 2), 0, 0);
             return g ? G : x;
           },
-          true);
+          true, std::true_type{});
     } else {
       run([&](int c) -> u32 { return hot[(u32)c < nh ? (u32)c : nh - 1u]; },
           [&](int c, u32 w) -> int32_t {
@@ -916,7 +981,7 @@ __global__ __launch_bounds__(1024) void k_al_rebuild_hot(const unsigned long lon
             const int32_t x = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(ln_rsrc, h ? kPast : (int)((u32)c << 2), 0, 0);
             return h ? (int32_t)w : x;
           },
-          hyb);
+          hyb, std::false_type{});
     }
   }
 }
@@ -931,12 +996,14 @@ __global__ __launch_bounds__(256) void k_al_rebuild_small(const unsigned long lo
                                                           const int32_t* __restrict__ Ln, int32_t* __restrict__ al,
                                                           const uint32_t* __restrict__ gbits, int64_t nbits,
                                                           int32_t* __restrict__ gword,
-                                                          unsigned long long* __restrict__ abits) {
+                                                          unsigned long long* __restrict__ abits, int sparse_ok) {
   if (kIfWanted && !rebuild_wanted(counters, thr)) return;
   const int64_t nhb = nbits < kHotBits ? nbits : kHotBits;
   const bool bits = nhb > 0 && 2 * (int64_t)gword[GW_HOT_BITS] >= nhb;  // uniform
   const int32_t G = gword[GW_G];
   if (blockIdx.x == 0 && threadIdx.x == 0) gword[GW_ABITS_OK] = bits ? 1 : 0;
+  const bool sparse = bits && sparse_ok != 0;  // the G arcs go unstored (rebuild_stream's note)
+  if (blockIdx.x == 0 && threadIdx.x == 0) sparse_mark(gword, sparse, G);
   if (!bits) {  // labels mode: the plain 16 B/lane gather stream (C2: 0.21 -> ~0.17 ms)
     rebuild_all(col, arcs, Ln, al);
     return;
@@ -945,7 +1012,7 @@ __global__ __launch_bounds__(256) void k_al_rebuild_small(const unsigned long lo
     if ((gbits[(u32)c >> 5] >> ((u32)c & 31u)) & 1u) return G;
     return Ln[c];
   };
-  rebuild_stream(lab, G, true, col, arcs, al, abits);
+  rebuild_stream(lab, G, true, col, arcs, al, abits, sparse, sparse_poison(G, nbits));
 }
 
 // gword[GW_CODE] = take the giant-code refresh: a rebuild is wanted, G is worth trying, and the
@@ -1108,7 +1175,7 @@ __global__ __launch_bounds__(1024) void k_code_rebuild(const int32_t* __restrict
 // [0, kHotLabels) there), the plain one otherwise
 constexpr int64_t kHotMaxSlots = int64_t(1) << 29;  // k_al_rebuild_hot's 32-bit label offsets (P = 1)
 int launch_rebuild(lpa_graph* g, bool if_wanted, int64_t thr, const int32_t* L,
-                   const unsigned long long* ctr) {
+                   const unsigned long long* ctr, bool allow_sparse = false) {
   hipStream_t s = g->stream;
   const bool code = if_wanted && code_refresh_now(g);
   // the giant label of the refreshed vector: the rebuild's bits below and the next
@@ -1118,6 +1185,10 @@ int launch_rebuild(lpa_graph* g, bool if_wanted, int64_t thr, const int32_t* L,
     LPA_HIP(hipGetLastError());
   }
   const bool ranked = rebuild_ranked(g);
+  // one GPU outside gather mode: a bits-mode rebuild leaves al[] sparse (LPA_SPARSE_AL)
+  // -- only in a superstep's own refresh (allow_sparse): the L0 rebuild, whose al[] superstep
+  // 1's column runs read as it is, and the rebuild after a caller's put stay dense
+  const int sparse_ok = (allow_sparse && g->sparse_al && g->nranks == 1 && !g->gather) ? 1 : 0;
   // hot slots of the bits-mode / code-mode test (k_giant_bits' count in gword[GW_HOT_BITS]): the
   // first kHotBits slots at P = 1, the first kHotBits / P (whole bit words) of every slice
   // of a rank-strided vector -- the same degree-ranked top set
@@ -1131,12 +1202,12 @@ int launch_rebuild(lpa_graph* g, bool if_wanted, int64_t thr, const int32_t* L,
       hipLaunchKernelGGL(k_giant_bits<true>, dim3(gb), dim3(256), 0, s, ctr, thr, L, g->vpad, g->gword,
                          (unsigned long long*)g->gbits, g->abits, (int64_t)0, hmask, hlim);
       hipLaunchKernelGGL(k_al_rebuild_small<true>, dim3(gr), dim3(256), 0, s, ctr, thr, g->col, g->arcs, L, g->al,
-                         g->gbits, g->vpad, g->gword, g->abits);
+                         g->gbits, g->vpad, g->gword, g->abits, sparse_ok);
     } else {
       hipLaunchKernelGGL(k_giant_bits<false>, dim3(gb), dim3(256), 0, s, ctr, thr, L, g->vpad, g->gword,
                          (unsigned long long*)g->gbits, g->abits, (int64_t)0, hmask, hlim);
       hipLaunchKernelGGL(k_al_rebuild_small<false>, dim3(gr), dim3(256), 0, s, ctr, thr, g->col, g->arcs, L, g->al,
-                         g->gbits, g->vpad, g->gword, g->abits);
+                         g->gbits, g->vpad, g->gword, g->abits, sparse_ok);
     }
   } else if (g->rebuild_hot && ((g->nranks == 1 && g->vpad <= kHotMaxSlots) || ranked)) {
     int dev_cus = 256;
@@ -1175,7 +1246,7 @@ int launch_rebuild(lpa_graph* g, bool if_wanted, int64_t thr, const int32_t* L,
 #define LPA_HOT_LAUNCH(W, R, B)                                                                  \
   hipLaunchKernelGGL((k_al_rebuild_hot<W, R, B>), dim3(dev_cus), dim3(1024), 0, s, ctr, thr, g->col, \
                      g->arcs, L, nhot, g->al, slice_lg, hot_lg, hb_lg, g->gbits, nbits, g->gword, g->abits, \
-                     blk ? g->blk_pieces : nullptr, binfo, code ? g->gword + GW_CODE : nullptr)
+                     blk ? g->blk_pieces : nullptr, binfo, code ? g->gword + GW_CODE : nullptr, sparse_ok)
     if (code) {
       hipLaunchKernelGGL(k_code_mode, dim3(1), dim3(64), 0, s, ctr, thr, nhot_bits, g->gword);
       LPA_HIP(hipGetLastError());
@@ -1319,7 +1390,7 @@ int launch_refresh(lpa_graph* g, const int32_t* Lc, const int32_t* Ln, bool diff
                        g->gword);
     LPA_HIP(hipGetLastError());
   } else if (!fold_rebuild && !gnow) {
-    LPA_TRY(launch_rebuild(g, true, thr, Ln, ctr));
+    LPA_TRY(launch_rebuild(g, true, thr, Ln, ctr, true));
   }
   LPA_HIP(hipGetLastError());
   return LPA_OK;

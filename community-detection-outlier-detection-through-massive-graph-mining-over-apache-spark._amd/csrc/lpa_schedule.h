@@ -110,4 +110,16 @@ inline bool early_graph_window(const lpa_graph* g) { return g->since_reset >= 1 
 // ... numbered 0 and 1 in the graph keys
 inline int early_graph_index(const lpa_graph* g) { return (int)(g->since_reset - 1); }
 
+// the vote source of a tally launch: p = g->al (or the column array in gather mode, whose
+// refreshes never leave al[] sparse)
+inline ArcSrc arc_src(const lpa_graph* g, const int32_t* p) {
+  ArcSrc a;
+  a.p = p;
+  a.bits = reinterpret_cast<const uint32_t*>(g->abits);
+  a.gword = g->gword;
+  a.last = (uint32_t)(2 * ((g->arcs + 63) / 64 + 1) - 1);
+  return a;
+}
+inline ArcSrc arc_src(const lpa_graph* g) { return arc_src(g, g->al); }
+
 }  // namespace lpa

@@ -97,6 +97,10 @@ typedef struct lpa_graph_info {
                               GPU, label vector <= 4 MB, no row above 128 arcs; since ABI 6) */
   int64_t host_allgathers; /* allgathers served by the host collective's function
                               (lpa_graph_create_hostcoll; since ABI 7)                 */
+  int64_t sparse_refreshes; /* refreshes since the build or the last reset that left al[]
+                              sparse: a one-GPU bits-mode rebuild carries the arcs on the
+                              giant label in the arc giant bits and stores only the other
+                              arcs' labels (LPA_SPARSE_AL=0: never; since ABI 15)      */
 } lpa_graph_info;
 
 /* Outlier summary. */
@@ -606,8 +610,9 @@ int lpa_degrees(lpa_graph* g, int32_t* deg_out);
  * ABI 11: lpa_shortest_paths.
  * ABI 12: lpa_strongly_connected_components.
  * ABI 13: lpa_parallel_pagerank.
- * ABI 14: lpa_louvain. */
-#define LPA_ABI_VERSION 14
+ * ABI 14: lpa_louvain.
+ * ABI 15: sparse_refreshes. */
+#define LPA_ABI_VERSION 15
 int lpa_abi_version(void);
 int lpa_graph_get_info(const lpa_graph* g, lpa_graph_info* info);
 int lpa_graph_get_info_sized(const lpa_graph* g, lpa_graph_info* info, int64_t info_size);
