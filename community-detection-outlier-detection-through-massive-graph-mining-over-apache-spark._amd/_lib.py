@@ -153,6 +153,14 @@ class LpaLouvainSummary(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LpaCoreSummary(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int64) for k in ("degeneracy", "main_core_size", "levels", "simple_edges",
+                                              "max_degree", "n_core0", "passes")]
+
+    def to_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class LpaOutlierSummary(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in (
         "n_groups", "k", "threshold", "n_flagged", "n_communities", "n_communities_flagged",
@@ -205,6 +213,8 @@ SIGNATURES = {
                                                          ctypes.POINTER(LpaSccSummary)]),
     "lpa_louvain": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int32, _vp,
                                    ctypes.POINTER(LpaLouvainLevel), ctypes.c_int32, ctypes.POINTER(LpaLouvainSummary)]),
+    "lpa_core_numbers": (ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32,
+                                        ctypes.POINTER(LpaCoreSummary)]),
     "lpa_loopback_create": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(_vp)]),
     "lpa_loopback_abort": (None, [_vp]),
     "lpa_loopback_destroy": (None, [_vp]),

@@ -251,6 +251,10 @@ int create_common(int32_t device, hipStream_t stream, const int32_t* src, const 
   if (const char* f = getenv("LPA_SP_PULL")) g->sp_pull = atoi(f) == 1 ? 1 : 0;
   if (const char* f = getenv("LPA_SCC_BLOCK"))
     g->scc_block = atoi(f) < 0 ? 0 : atoi(f) > lpa::kSccTrimCap ? lpa::kSccTrimCap : atoi(f);
+  if (const char* f = getenv("LPA_KC_SHORT")) g->kc_short = atoi(f) < 0 ? 0 : atoi(f);
+  if (const char* f = getenv("LPA_KC_WAVE")) g->kc_wave = atoi(f) < 0 ? 0 : atoi(f);
+  if (const char* f = getenv("LPA_KC_BLOCK"))
+    g->kc_block = atoi(f) < 0 ? 0 : atoi(f) > lpa::kKcPeelCap ? lpa::kKcPeelCap : atoi(f);
   if (const char* f = getenv("LPA_LV_SHORT")) g->lv_short = atoi(f) < 0 ? 0 : atoi(f);
   if (const char* f = getenv("LPA_LV_WAVE")) g->lv_wave = atoi(f) < 0 ? 0 : atoi(f);
   if (const char* f = getenv("LPA_LV_TABLE")) {
@@ -832,6 +836,28 @@ int lpa_louvain(lpa_graph* g, int32_t max_levels, int32_t max_rounds, int32_t* c
   }
   LPA_HIP(hipSetDevice(g->device));
   return louvain(g, max_levels, max_rounds, comm_out, out_is_device, size_out, levels_out, levels_cap, summary);
+}
+
+int lpa_core_numbers(lpa_graph* g, int32_t max_k, int32_t* core_out, int32_t* simple_degree_out,
+                     int32_t out_is_device, lpa_core_summary* summary) {
+  if (!g) {
+    set_error("null handle");
+    return LPA_EINVAL;
+  }
+  if (max_k < 0) {
+    set_error("lpa_core_numbers: max_k must not be negative, got %d", max_k);
+    return LPA_EINVAL;
+  }
+  if (!core_out && g->V > 0) {
+    set_error("lpa_core_numbers: null core output");
+    return LPA_EINVAL;
+  }
+  if (g->m > 0 && !g->e_src) {
+    set_error("lpa_core_numbers of a distributed job runs on rank 0 (the rank that keeps the edge list)");
+    return LPA_EINVAL;
+  }
+  LPA_HIP(hipSetDevice(g->device));
+  return core_numbers(g, max_k, core_out, simple_degree_out, out_is_device, summary);
 }
 
 int lpa_degrees(lpa_graph* g, int32_t* deg_out) {

@@ -104,6 +104,12 @@ constexpr int kSccTrimCap = 4096;     // vertices the in-block trim's LDS queue 
 constexpr int kSccBlockTrim = 512;    // a trim level of at most this many vertices runs inside one block (measured:
                                       //   1000 levels of 512 take 17.6 ms there, 24.9 ms as launches; of 1024, 34.5
                                       //   against 31.9 ms; DESIGN.md "Strongly connected components")
+// k-core decomposition (lpa_kcore.hip): list lengths of the expand kernels' row forms and the in-block peel
+constexpr int kKcShort = 32;          // 8 lanes per row up to this length
+constexpr int kKcWave = 1024;         // a wave per row up to this length; longer: a block of 1024 per row
+constexpr int kKcPeelCap = 4096;      // vertices the in-block peel's LDS queue holds per sub-level
+constexpr int kKcBlockPeel = 512;     // a sub-level of at most this many vertices runs inside one block (the SCC
+                                      //   trim's measured break-even: the same queue, the same loop)
 // Louvain (lpa_louvain.hip): list lengths of the move kernel's row forms and the slots of their LDS
 // tally tables; a row of more than half its form's slots takes a region of the global spill table
 constexpr int kLvShort = 32;          // 8 lanes per row up to this length, no table
@@ -425,6 +431,11 @@ struct lpa_graph {
   int sp_pull = 0;                          // LPA_SP_PULL=1: pull at every level
   // strongly connected components (lpa_scc.hip): the largest trim level that runs inside one block
   int scc_block = lpa::kSccBlockTrim;       // LPA_SCC_BLOCK (0 .. kSccTrimCap; 0: every level is a launch)
+  // k-core decomposition (lpa_kcore.hip): list lengths up to which a queued row takes the short form and
+  // the wave form (longer: the block form), and the largest sub-level that runs inside one block
+  int kc_short = lpa::kKcShort;             // LPA_KC_SHORT (>= 0; 0: no row with a neighbour takes the short form)
+  int kc_wave = lpa::kKcWave;               // LPA_KC_WAVE  (>= 0; 0, or <= LPA_KC_SHORT: no row takes the wave form)
+  int kc_block = lpa::kKcBlockPeel;         // LPA_KC_BLOCK (0 .. kKcPeelCap; 0: every sub-level is a launch)
   // Louvain (lpa_louvain.hip): list lengths up to which a row takes the short form and the wave form
   // (longer: the block form), and the slots of the block form's LDS table (the wave form's: the
   // smaller of this and kLvWaveSlots)
@@ -657,5 +668,9 @@ int strongly_connected_components(lpa_graph* g, int32_t max_iter, int32_t* comp_
 // Louvain community detection on the symmetrised multigraph (lpa_louvain.hip)
 int louvain(lpa_graph* g, int32_t max_levels, int32_t max_rounds, int32_t* comm_out, int32_t out_is_device,
             int64_t* size_out, lpa_louvain_level* levels_out, int32_t levels_cap, lpa_louvain_summary* summary);
+
+// k-core decomposition of the canonical simple undirected graph (lpa_kcore.hip)
+int core_numbers(lpa_graph* g, int32_t max_k, int32_t* core_out, int32_t* simple_degree_out, int32_t out_is_device,
+                 lpa_core_summary* summary);
 
 }  // namespace lpa

@@ -643,6 +643,58 @@ class Graph:
             return comm
         return comm, size, [rows[i].to_dict() for i in range(min(int(summ.levels), cap))], summ.to_dict()
 
+    # -- k-core decomposition -----------------------------------------------------------
+    def core_numbers(self, max_k=None, out=None, stats: bool = False):
+        """Core numbers of the canonical simple undirected graph of the input multigraph
+        (lpa_core_numbers: self-loops dropped, direction ignored, duplicates collapsed, as
+        ``triangle_count``): ``core[v]`` is the largest k such that v lies in a subgraph where
+        every vertex has at least k neighbours; 0 for a vertex without a neighbour.  ``max_k``
+        (an int >= 0, ``None``: no cap) gives ``min(core, max_k)`` and stops the peeling before
+        level ``max_k``; ``max_k=0`` only builds the graph.  Host int32 array by default, or
+        written into the int32 device tensor ``out`` (this handle's device, ``num_vertices``
+        entries).  ``stats=True`` returns ``(core, simple_degree, summary)``:
+        ``simple_degree[v]`` (int32, in the memory ``core`` is in) is the number of distinct
+        neighbours of v; ``summary`` is a dict of degeneracy, main_core_size (both of the capped
+        values), levels, simple_edges, max_degree, n_core0 and passes (the peel's host round
+        trips: the schedule, not a property of the graph).  The result is identical across
+        runs, handles, input edge orders and directions, and kernel schedules.  The labels and
+        the LPA state are not touched."""
+        if max_k is None:
+            max_k = 2 ** 31 - 1
+        if not isinstance(max_k, (int, np.integer)) or isinstance(max_k, (bool, np.bool_)):
+            raise TypeError(f"max_k must be an int or None, got {type(max_k).__name__}")
+        if max_k < 0:
+            raise ValueError(f"max_k must not be negative, got {max_k}")
+        max_k = min(int(max_k), 2 ** 31 - 1)
+        V = self.num_vertices
+        deg = None
+        if out is not None and _is_device_tensor(out):
+            import torch
+
+            if out.dtype != torch.int32:
+                raise ValueError(f"out must be int32, got {out.dtype}")
+            if out.device.index != self.device:
+                raise ValueError(f"out must be on cuda:{self.device}, got {out.device}")
+            if out.numel() != V or not out.is_contiguous():
+                raise ValueError(f"out must hold {V} contiguous entries")
+            core, ptr, on_dev = out, out.data_ptr(), 1
+            if stats:
+                deg = torch.empty(V, dtype=torch.int32, device=out.device)
+            torch.cuda.current_stream(out.device).synchronize()   # the library works on its own stream
+            deg_ptr = deg.data_ptr() if stats else None
+        elif out is not None:
+            raise ValueError("out must be an int32 device tensor")
+        else:
+            core = np.empty(V, dtype=np.int32)
+            ptr, on_dev = core.ctypes.data, 0
+            if stats:
+                deg = np.empty(V, dtype=np.int32)
+            deg_ptr = deg.ctypes.data if stats else None
+        summ = _lib.LpaCoreSummary()
+        _lib.check(self._lib.lpa_core_numbers(self._handle(), max_k, ptr, deg_ptr, on_dev,
+                                              ctypes.byref(summ) if stats else None))
+        return (core, deg, summ.to_dict()) if stats else core
+
 
 class Loopback:
     """In-process collective group of ``nranks`` handles on one device (the

@@ -35,6 +35,7 @@ from .graph import Graph
 ID, SRC, DST, LABEL = "id", "src", "dst", "label"
 COMPONENT = "component"
 COUNT = "count"
+CORE = "core"
 PAGERANK = "pagerank"
 PAGERANKS = "pageranks"
 WEIGHT = "weight"
@@ -99,6 +100,14 @@ def _check_louvain(maxLevels, maxRounds):
             raise TypeError(f"{name} must be an int, got {type(x).__name__}")
         if x <= 0:
             raise ValueError(f"{name} must be greater than 0, but got {x}")
+
+
+def _check_core_k(k, name="k"):
+    """The argument check of GraphFrame.kCore (and of a core-number cap), before any device work."""
+    if not isinstance(k, (int, np.integer)) or isinstance(k, (bool, np.bool_)):
+        raise TypeError(f"{name} must be an int, got {type(k).__name__}")
+    if k < 0:
+        raise ValueError(f"{name} must not be negative, but got {k}")
 
 
 def _check_cc_algorithm(algorithm):
@@ -289,6 +298,44 @@ class GraphFrame:
         wedges = summ["wedges"]
         out.attrs["transitivity"] = 3.0 * summ["n_triangles"] / wedges if wedges > 0 else 0.0
         return out
+
+    def coreNumber(self) -> pd.DataFrame:
+        """Core number per vertex (k-core decomposition) -- this package's own addition, not a
+        GraphFrames call (like ``clusteringCoefficient`` and ``louvain``).  On the canonical
+        simple undirected graph (self-loops dropped, direction ignored, duplicates collapsed, as
+        ``triangleCount``), ``core`` (int64) is the largest k such that the vertex lies in a
+        subgraph where every vertex has at least k neighbours; 0 without a neighbour.  Returns
+        the vertex rows sorted by id, all columns kept, + ``core``.  ``.attrs["degeneracy"]`` is
+        the largest core number, ``.attrs["core_sizes"]`` the list ``np.bincount(core)``: the
+        vertices of each core number."""
+        ig = self._indexed()
+        core = self._gpu_graph().core_numbers().astype(np.int64)
+        out = _attach(self._v, ig, {CORE: core})
+        sizes = np.bincount(core)
+        out.attrs["degeneracy"] = max(int(sizes.size) - 1, 0)
+        out.attrs["core_sizes"] = [int(x) for x in sizes]
+        return out
+
+    def kCore(self, k: int) -> "GraphFrame":
+        """The k-core as a graph -- this package's own addition (see ``coreNumber``): the
+        sub-multigraph induced by the vertices of core number >= ``k``.  Returns a
+        **GraphFrame**, as ``pageRank`` does: ``.vertices`` is the surviving vertex rows, sorted
+        by id, all columns kept, + ``core`` (int64) capped at ``k`` (the peeling stops at level
+        ``k``); ``.edges`` the input edges whose endpoints both survive, in input order, with
+        all their columns -- duplicates and self-loops among survivors included.  ``k = 0``
+        keeps every vertex; a ``k`` above the degeneracy gives two empty tables.  The result
+        feeds ``labelPropagation``, ``louvain`` and ``outlierScores`` as any GraphFrame: cutting
+        to a k-core first is the usual cure for thousands of tiny fringe communities."""
+        _check_core_k(k)
+        ig = self._indexed()
+        core = self._gpu_graph().core_numbers(max_k=int(k)).astype(np.int64)
+        vdf = _attach(self._v, ig, {CORE: core})
+        vdf = vdf[vdf[CORE].to_numpy() >= k].reset_index(drop=True)
+        inside = core >= k
+        keep = ig.kept.copy()
+        keep[ig.kept] = inside[ig.src] & inside[ig.dst]
+        edf = self._e[keep].reset_index(drop=True)
+        return GraphFrame(vdf, edf, device=self._device)
 
     def _source_dense(self, sourceId):
         """Dense id of ``sourceId`` (None: none); a ValueError when it is no vertex id."""
@@ -488,6 +535,25 @@ def triangle_count(vertices: pd.DataFrame, edges: pd.DataFrame, device: int = 0)
     gf = GraphFrame(vertices, edges, device=device)
     try:
         return gf.triangleCount()
+    finally:
+        gf.close()
+
+
+def core_number(vertices: pd.DataFrame, edges: pd.DataFrame, device: int = 0) -> pd.DataFrame:
+    """Function form of ``GraphFrame(vertices, edges).coreNumber()``."""
+    gf = GraphFrame(vertices, edges, device=device)
+    try:
+        return gf.coreNumber()
+    finally:
+        gf.close()
+
+
+def k_core(vertices: pd.DataFrame, edges: pd.DataFrame, k: int, device: int = 0) -> "GraphFrame":
+    """Function form of ``GraphFrame(vertices, edges).kCore(k)``: the k-core as a GraphFrame."""
+    _check_core_k(k)
+    gf = GraphFrame(vertices, edges, device=device)
+    try:
+        return gf.kCore(k)
     finally:
         gf.close()
 

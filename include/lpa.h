@@ -593,6 +593,46 @@ int lpa_louvain(lpa_graph* g, int32_t max_levels, int32_t max_rounds, int32_t* c
                 lpa_louvain_level* levels_out /* nullable, host */, int32_t levels_cap,
                 lpa_louvain_summary* summary /* nullable */);
 
+/*
+ * k-core decomposition (core numbers) of the canonical simple undirected graph of the input
+ * multigraph, exactly lpa_triangle_count's: self-loops dropped, direction ignored, duplicates
+ * collapsed, an edge with an end outside [0, V) is no edge.  This is the package's own call
+ * (GraphFrames has none).  core_out[v], by dense id (V entries, required), is the largest k such
+ * that v belongs to a subgraph in which every vertex has at least k neighbours; an isolated
+ * vertex, or one with only self-loops, gets 0.  The result is unique: a pure function of
+ * (V, edge set, max_k), identical across runs, edge orders, edge directions, handles, devices
+ * and kernel schedules.
+ * max_k >= 0 caps it (INT32_MAX: no cap): the result is min(core[v], max_k); the peeling stops
+ * before level max_k and every vertex still alive gets max_k.  max_k = 0 does only the build and
+ * writes zeros.  With a cap, degeneracy and main_core_size describe the CAPPED values: the
+ * largest value written and the vertices that hold it.
+ * simple_degree_out (nullable, V entries, int32): d(v), the distinct neighbours of v other than
+ * v.  Both arrays are host memory unless out_is_device; summary is nullable.  V == 0: success,
+ * nothing written, the summary all zeros.  LPA_EINVAL for a null handle, for max_k < 0 and for
+ * a null core_out with V > 0.  The call blocks until the work is done.
+ * Level-by-level peeling with an atomic live count per vertex: a vertex leaves at level k when
+ * its count falls from k + 1 to k (DESIGN.md "k-core decomposition"); the removal queue holds
+ * every vertex once, and a call whose queue tails do not sum to the vertices peeled returns
+ * LPA_EOVERFLOW.  All working memory is stream-ordered temporaries, the labels and every other
+ * piece of lpa_step's state are neither read nor written, nothing is kept on the handle.  On a
+ * distributed job (nranks > 1) only rank 0 keeps the edge list this needs; the other ranks
+ * return LPA_EINVAL.  Since ABI 16.
+ */
+typedef struct lpa_core_summary {
+  int64_t degeneracy;      /* largest value of core_out (0 if V == 0)                         */
+  int64_t main_core_size;  /* vertices with core_out == degeneracy                            */
+  int64_t levels;          /* distinct values of the uncapped core among the peeled vertices,
+                              + 1 if the cap left a vertex alive                               */
+  int64_t simple_edges;    /* as lpa_triangle_summary                                         */
+  int64_t max_degree;      /* largest simple degree                                           */
+  int64_t n_core0;         /* vertices of simple degree 0                                     */
+  int64_t passes;          /* host round trips of the peel: the schedule, NOT a function of
+                              the graph (it depends on LPA_KC_BLOCK)                          */
+} lpa_core_summary;        /* 56 bytes */
+int lpa_core_numbers(lpa_graph* g, int32_t max_k /* INT32_MAX: no cap */, int32_t* core_out,
+                     int32_t* simple_degree_out /* nullable */, int32_t out_is_device,
+                     lpa_core_summary* summary /* nullable */);
+
 /* Symmetrised degree of every vertex (dense ids), host output. */
 int lpa_degrees(lpa_graph* g, int32_t* deg_out);
 
@@ -611,8 +651,9 @@ int lpa_degrees(lpa_graph* g, int32_t* deg_out);
  * ABI 12: lpa_strongly_connected_components.
  * ABI 13: lpa_parallel_pagerank.
  * ABI 14: lpa_louvain.
- * ABI 15: sparse_refreshes. */
-#define LPA_ABI_VERSION 15
+ * ABI 15: sparse_refreshes.
+ * ABI 16: lpa_core_numbers. */
+#define LPA_ABI_VERSION 16
 int lpa_abi_version(void);
 int lpa_graph_get_info(const lpa_graph* g, lpa_graph_info* info);
 int lpa_graph_get_info_sized(const lpa_graph* g, lpa_graph_info* info, int64_t info_size);
