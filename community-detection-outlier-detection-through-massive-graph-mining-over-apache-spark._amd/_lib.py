@@ -71,6 +71,7 @@ class LpaGraphInfo(ctypes.Structure):
         ("gather_mode", ctypes.c_int64),
         ("host_allgathers", ctypes.c_int64),
         ("sparse_refreshes", ctypes.c_int64),
+        ("fill_refreshes", ctypes.c_int64),
     ]
 
     def to_dict(self):

@@ -466,8 +466,10 @@ int init_labels(lpa_graph* g) {
     LPA_HIP(hipMemsetAsync(g->gword + GW_ABITS_OK, 0, sizeof(int32_t), g->stream));  // abits stale
     LPA_HIP(hipMemsetAsync(g->gword + GW_ABITS_PASS, 0, sizeof(int32_t), g->stream));  // no abits pass ran
     LPA_HIP(hipMemsetAsync(g->gword + GW_CODE, 0, sizeof(int32_t), g->stream));  // no code refresh pending
-    // al[] is dense again (al0 / the L0 rebuild below); GW_AL_SPARSE, GW_AL_GB, GW_SPARSE_CNT
-    LPA_HIP(hipMemsetAsync(g->gword + GW_AL_SPARSE, 0, 3 * sizeof(int32_t), g->stream));
+    // al[] is dense again (al0 / the L0 rebuild below); GW_AL_SPARSE, GW_AL_GB, GW_SPARSE_CNT,
+    // GW_FILL, GW_FILL_CNT
+    static_assert(GW_FILL_CNT == GW_AL_SPARSE + 4, "one memset over the sparse-al words");
+    LPA_HIP(hipMemsetAsync(g->gword + GW_AL_SPARSE, 0, 5 * sizeof(int32_t), g->stream));
   }
   g->cur = 0;
   g->since_reset = 0;
@@ -650,6 +652,7 @@ int finish_build(lpa_graph* g, int32_t* deg_own, int64_t m) {
   LPA_TRY(dev_alloc(g, (void**)&g->gbits, sizeof(uint32_t) * ((g->vpad + 63) / 64 * 2)));
   LPA_TRY(dev_alloc(g, (void**)&g->gword, sizeof(int32_t) * kGwordLen));
   LPA_HIP(hipMemsetAsync(g->gword, 0, sizeof(int32_t) * kGwordLen, s));
+  LPA_TRY(dev_alloc(g, (void**)&g->fill_part, sizeof(u64) * 2 * kFillBlocks));
   LPA_TRY(dev_alloc(g, (void**)&g->abits, sizeof(unsigned long long) * ((g->arcs + 63) / 64 + 1)));
   LPA_TRY(dev_alloc(g, (void**)&g->lab[0], sizeof(int32_t) * g->vpad));
   LPA_TRY(dev_alloc(g, (void**)&g->lab[1], sizeof(int32_t) * g->vpad));

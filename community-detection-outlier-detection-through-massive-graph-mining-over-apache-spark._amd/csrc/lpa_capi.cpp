@@ -238,6 +238,7 @@ int create_common(int32_t device, hipStream_t stream, const int32_t* src, const 
   if (const char* f = getenv("LPA_UNITS_PURE")) g->units_pure = atoi(f) ? 1 : 0;
   if (const char* f = getenv("LPA_KEEP_BITS")) g->keep_bits = atoi(f) ? 1 : 0;
   if (const char* f = getenv("LPA_SPARSE_AL")) g->sparse_al = atoi(f) ? 1 : 0;
+  if (const char* f = getenv("LPA_FILL_SCATTER")) g->fill_scatter = atoi(f) < 0 ? 0 : atoi(f) > 2 ? 2 : atoi(f);
   if (const char* f = getenv("LPA_TC_SHORT")) g->tc_short = atoi(f) < 0 ? 0 : atoi(f);
   if (const char* f = getenv("LPA_TC_WAVE")) g->tc_wave = atoi(f) < 0 ? 0 : atoi(f) > kTcWaveMax ? kTcWaveMax : atoi(f);
   if (const char* f = getenv("LPA_TC_LDS")) g->tc_lds = atoi(f) < 0 ? 0 : atoi(f) > kTcLdsMax ? kTcLdsMax : atoi(f);
@@ -917,6 +918,9 @@ int fill_info(const lpa_graph* g, lpa_graph_info* info) {
     LPA_HIP(hipMemcpyAsync(&w, g->gword + GW_SPARSE_CNT, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
     LPA_HIP(hipStreamSynchronize(g->stream));
     info->sparse_refreshes = w;
+    LPA_HIP(hipMemcpyAsync(&w, g->gword + GW_FILL_CNT, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    LPA_HIP(hipStreamSynchronize(g->stream));
+    info->fill_refreshes = w;
   }
   return LPA_OK;
 }

@@ -67,6 +67,15 @@ constexpr double kRebuildFrac = 0.25;
 // the al[] scatter marks dirty rows while <= this fraction of the arcs changed; above
 // it the next superstep tallies every row
 constexpr double kFrontierFrac = 0.005;
+// fill-scatter form of the sparse bits-mode rebuild (lpa_refresh.hip k_fill_decide): taken
+// while the arcs of the columns off the giant label are at most this fraction of the arcs
+// (half the break-even share measured at C3) and no such column is longer
+// than max(kFillCap, arcs >> kFillCapShift) positions: one wave writes a whole column, 256
+// positions per round, so the longest one bounds the scatter's tail (C3: 16 K positions, 64
+// rounds, ~0.1 ms against the 0.65 ms stream)
+constexpr double kFillFrac = 0.0154;
+constexpr int kFillCap = 4096;
+constexpr int kFillCapShift = 15;
 // superstep 1's column-run tiles (lpa_iter.hip k_first_runs): arcs per wave tile, 16 per
 // lane; the row-start bitmap holds whole tiles plus the next tile's first word
 constexpr int kRunTile = 1024;
@@ -210,8 +219,15 @@ enum GwordSlot {
                       //   code forms, k_al_rebuild, the folded rebuild of k_al_scatter) and by a reset.
   GW_AL_GB = 13,      // Gb: the giant label of the vector the sparse rebuild read
   GW_SPARSE_CNT = 14, // refreshes that left al[] sparse since the build or the last reset
+  GW_FILL = 15,       // this refresh takes the fill-scatter form of the sparse bits-mode rebuild
+                      //   (k_fill_decide; zeroed by k_giant_pick, so it never outlives its refresh,
+                      //   and cleared wherever GW_AL_SPARSE is): the stream rebuilds stand down
+  GW_FILL_CNT = 16,   // refreshes that took that form since the build or the last reset
+  GW_FILL_TICKET = 17, // k_fill_decide's last-block ticket (zeroed by k_giant_pick)
 };
-constexpr int kGwordLen = 16;
+constexpr int kGwordLen = 24;
+// blocks of k_fill_decide at most: each leaves one partial (sum, longest) in lpa_graph::fill_part
+constexpr int kFillBlocks = 512;
 // Slots of lpa_graph::gdec (kGdecLen words): superstep 2's hub decision in block mode
 // (k_hub_decide, `ndec` there) and the lists of what it could not settle.
 enum GdecSlot {
@@ -271,6 +287,8 @@ struct lpa_graph {
   int units_pure = 1;     // LPA_UNITS_PURE=0: superstep 4 re-tallies every hub unit
   int keep_bits = 1;      // LPA_KEEP_BITS=0: superstep 3's scatter drops the arc giant bits
   int sparse_al = 1;      // LPA_SPARSE_AL=0: a bits-mode rebuild also stores the giant label (dense al[])
+  int fill_scatter = 1;   // LPA_FILL_SCATTER: the sparse bits-mode rebuild by fill and scatter (0: never,
+                          // 1: the device decision, 2: whenever that rebuild runs -- tests)
   int conv_streams = 2;   // LPA_CONV_STREAMS: streams of a converged superstep's tally (1-3)
   int64_t vpad = 0;       // nranks * slice
   int64_t own_begin = 0;  // rank * slice
@@ -366,6 +384,7 @@ struct lpa_graph {
   uint32_t* gbits = nullptr;    // [vpad / 32] rebuild: bit u = (L[u] == G), the giant label
   int32_t* gword = nullptr;     // [kGwordLen] G of the last refreshed vector and the decisions of
                                 //     supersteps 2-4 that hang on it (GwordSlot)
+  lpa::u64* fill_part = nullptr; // [2 kFillBlocks] k_fill_decide's per-block (sum, longest)
   // giant codes (round 5, lpa_codes.h "Giant codes"): the refresh after superstep 1 (or
   // 2), when one label G carries the hubs but not half the hot slots (R-MAT), writes a
   // 2-bit code per arc instead of al[] (code 0 = G, else 1 + a label hash mod 3; 16 arcs

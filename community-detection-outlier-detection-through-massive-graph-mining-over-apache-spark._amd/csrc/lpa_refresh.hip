@@ -327,7 +327,10 @@ __global__ __launch_bounds__(256) void k_al_scatter(const int32_t* __restrict__ 
   // form, instead of by a k_al_rebuild_hot launch that nearly always returns at once
   // (one dependent launch fewer per converged superstep)
   if (rebuild && col_fold) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) gword[GW_AL_SPARSE] = 0;  // a dense al[] again
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      gword[GW_AL_SPARSE] = 0;  // a dense al[] again
+      gword[GW_FILL] = 0;
+    }
     rebuild_all(col_fold, arcs, Ln, al);
   }
   // one-chunk columns from the list: a lane each, longer rows of positions by the wave
@@ -420,6 +423,7 @@ __global__ __launch_bounds__(256) void k_al_rebuild(const unsigned long long* __
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     gword[GW_ABITS_OK] = 0;   // no arc giant bits from this form
     gword[GW_AL_SPARSE] = 0;  // ... and a dense al[]
+    gword[GW_FILL] = 0;
   }
   rebuild_all(col, arcs, Ln, al);
 }
@@ -469,6 +473,8 @@ __global__ __launch_bounds__(1024) void k_giant_pick(const int32_t* __restrict__
     gword[GW_CODE] = 0;  // no giant-code refresh unless k_code_mode takes it below
     gword[GW_ABITS_PASS] = 0;  // no k_abits_pass since this refresh
     gword[GW_PURE_CNT] = 0;  // superstep 4's impure-unit list (k_units_pure)
+    gword[GW_FILL] = 0;      // no fill-scatter form unless k_fill_decide takes it below ...
+    gword[GW_FILL_TICKET] = 0;  // ... in its last block
     gword[GW_TRY] = n > 0 && 5 * (int64_t)(m >> 32) >= n ? 1 : 0;
   }
 }
@@ -492,7 +498,10 @@ __global__ __launch_bounds__(256) void k_giant_bits(const unsigned long long* __
   if (threadIdx.x == 0) bcnt = 0u;
   // a full rebuild follows (the LDS hot-set, small or code form): al[] is dense again unless
   // that rebuild takes the bits mode of one GPU and sets the word itself
-  if (blockIdx.x == 0 && threadIdx.x == 0) gword[GW_AL_SPARSE] = 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    gword[GW_AL_SPARSE] = 0;
+    gword[GW_FILL] = 0;
+  }
   __syncthreads();
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nzero; i += (int64_t)gridDim.x * blockDim.x)
     abits[i] = 0ull;
@@ -513,12 +522,16 @@ __global__ __launch_bounds__(256) void k_giant_bits(const unsigned long long* __
       if (lane == k) mine = m;
     }
     if (lane < 8 && g0 + lane * 64 < n) bits[(g0 >> 6) + lane] = mine;
-    // the hot slots' set bits (the rebuild's bits-mode test without an LDS fill); hlim
-    // and the slice are multiples of 64, so a bit word is hot or cold as a whole
+    // the hot slots' set bits (the rebuild's bits-mode test without an LDS fill); a ranked
+    // hlim and the slice are multiples of 64, so a bit word is hot or cold as a whole there;
+    // kHotBits (P = 1) ends mid-word, and that word counts its hot half only -- the count is
+    // then exactly the one k_al_rebuild_hot takes of its LDS words, so k_fill_decide, k_code_mode
+    // and both rebuild kernels agree on the bits mode
     const int64_t wi = g0 + lane * 64;
-    const bool hot = lane < 8 && wi < n && (int64_t)((uint64_t)wi & hmask) < hlim;
+    const int64_t hrem = hlim - (int64_t)((uint64_t)wi & hmask);
+    const bool hot = lane < 8 && wi < n && hrem > 0;
     if (__ballot(hot)) {
-      const u32 c = wave_sum_u32(hot ? (u32)__popcll(mine) : 0u);
+      const u32 c = wave_sum_u32(hot ? (u32)__popcll(hrem >= 64 ? mine : mine & ((1ull << hrem) - 1ull)) : 0u);
       if (lane == 0 && c) atomicAdd(&bcnt, c);
     }
   }
@@ -857,6 +870,7 @@ __global__ __launch_bounds__(1024) void k_al_rebuild_hot(const unsigned long lon
                                                          const int32_t* __restrict__ skip, int sparse_ok) {
   if (kIfWanted && !rebuild_wanted(counters, thr)) return;
   if (skip && *skip) return;  // the giant-code refresh replaces this rebuild (k_code_mode)
+  if (!kRanked && gword[GW_FILL] != 0) return;  // ... or the fill-scatter form (k_fill_decide)
   __shared__ u32 hot[kHotLabelsSingle];
   u32* s_cnt = &hot[kHotLabelsSingle - 1];   // beyond the bit words; labels mode refills it
   // ---- the giant-label bits of the hot slots, and how many are set ----
@@ -998,6 +1012,7 @@ __global__ __launch_bounds__(256) void k_al_rebuild_small(const unsigned long lo
                                                           int32_t* __restrict__ gword,
                                                           unsigned long long* __restrict__ abits, int sparse_ok) {
   if (kIfWanted && !rebuild_wanted(counters, thr)) return;
+  if (gword[GW_FILL] != 0) return;  // the fill-scatter form replaces this rebuild (k_fill_decide)
   const int64_t nhb = nbits < kHotBits ? nbits : kHotBits;
   const bool bits = nhb > 0 && 2 * (int64_t)gword[GW_HOT_BITS] >= nhb;  // uniform
   const int32_t G = gword[GW_G];
@@ -1013,6 +1028,265 @@ __global__ __launch_bounds__(256) void k_al_rebuild_small(const unsigned long lo
     return Ln[c];
   };
   rebuild_stream(lab, G, true, col, arcs, al, abits, sparse, sparse_poison(G, nbits));
+}
+
+// ---------------------------------------------------------------------------
+// The fill-scatter form of the sparse bits-mode rebuild (one GPU; LPA_FILL_SCATTER).
+// A sparse al[] needs, of a bits-mode rebuild, the arc giant bits and the al[] entries of
+// the arcs whose column is off G -- at C3 after superstep 2, 1.5 % of the arcs, all in short
+// columns of low-degree vertices -- while the stream form reads every arc's column and probes
+// a giant bit for it.  This form sets every arc bit and then visits only the columns off G
+// through the CSC position index: al[p] = L[u] and bit p cleared for each position p of such
+// a column u.  The result is the stream form's, bit for bit in abits and entry for entry in
+// al[] wherever a bit is clear.
+//
+// k_fill_decide (after k_giant_bits, whose gbits and hot-bit count it reads): returns at once
+// unless the rebuild is wanted and in bits mode (the test of both rebuild kernels; the code
+// refresh needs the opposite, k_code_mode).  Then it
+//   - sets the arc bits [0, arcs) (the last word's tail stays clear, as the stream leaves
+//     it) -- already here, before the decision: a bits-mode stream that runs after all
+//     rewrites every word, and the scatter then needs no launch between it and the fill;
+//   - sums the positions of the columns off G below the isolated slots, and their longest
+//     (cptr read for those slots only; a lane per slot, all-G bit words skipped), one partial
+//     per block in part[] (4,096 blocks adding into gword cost ~150 us of same-address atomics);
+//   - in its last block (ticket) sums the partials and takes the form when those arcs are <= frac_arcs and no
+//     column is longer than cap (mode 2, tests: always), with the sparse rebuild's
+//     bookkeeping: gword[GW_FILL], sparse_mark, gword[GW_ABITS_OK], gword[GW_FILL_CNT].
+// -DLPA_SPARSE_POISON: every al[] entry is poisoned first (the stream, if it runs after all,
+// rewrites every entry in that build).
+template <bool kIfWanted>
+__global__ __launch_bounds__(1024) void k_fill_decide(const unsigned long long* __restrict__ counters, int64_t thr,
+                                                     const unsigned long long* __restrict__ gbits64, int64_t n_iso,
+                                                     const int64_t* __restrict__ cptr, int64_t arcs, int64_t nhb,
+                                                     int64_t nslots, int32_t* __restrict__ gword,
+                                                     unsigned long long* __restrict__ abits,
+                                                     int32_t* __restrict__ al, int mode, int64_t frac_arcs,
+                                                     int64_t cap, unsigned long long* __restrict__ part) {
+  if (kIfWanted && !rebuild_wanted(counters, thr)) return;
+  if (!(nhb > 0 && 2 * (int64_t)gword[GW_HOT_BITS] >= nhb)) return;  // not the bits mode (uniform)
+  const int32_t G = gword[GW_G];
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t nth = (int64_t)gridDim.x * blockDim.x;
+  const int64_t nfw = arcs >> 6;
+  {  // 16-B streaming stores (device allocations are 256-B aligned), the odd word and the tail apart
+    v4i* __restrict__ a4 = reinterpret_cast<v4i*>(abits);
+    v4i ones;
+    ones.x = ones.y = ones.z = ones.w = -1;
+    for (int64_t i = tid; i < (nfw >> 1); i += nth) __builtin_nontemporal_store(ones, a4 + i);
+  }
+  if (tid == 0 && (nfw & 1)) abits[nfw - 1] = ~0ull;
+  if (tid == 0 && (arcs & 63)) abits[nfw] = (1ull << (arcs & 63)) - 1ull;
+#ifdef LPA_SPARSE_POISON
+  {
+    const int32_t poison = sparse_poison(G, nslots);
+    for (int64_t i = tid; i < arcs; i += nth) al[i] = poison;
+  }
+#else
+  (void)al;
+  (void)nslots;
+#endif
+  // ---- the arcs of the columns off G: a wave takes kDecideWords bit words at a time (one
+  // load), then four words' slots per round, their cptr loads in flight together ----
+  constexpr int kDecideWords = 16;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t nw = nth >> 6, ngrp = (n_iso + 63) >> 6;
+  unsigned long long sum = 0ull;
+  u32 mx = 0u;
+#ifdef LPA_FILL_ONLY_TIMING  // variant build that times the fill alone: no
+  if (false)                 // count, so the form is always taken
+#endif
+  for (int64_t g0 = (tid >> 6) * kDecideWords; g0 < ngrp; g0 += nw * kDecideWords) {
+    const unsigned long long off = lane < kDecideWords && g0 + lane < ngrp ? ~gbits64[g0 + lane] : 0ull;
+    if (__ballot(off != 0ull) == 0ull) continue;
+    for (int j0 = 0; j0 < kDecideWords; j0 += 4) {
+      unsigned long long w[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) w[j] = __shfl(off, j0 + j, 64);
+      if ((w[0] | w[1] | w[2] | w[3]) == 0ull) continue;  // uniform
+      int64_t a[4], e[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int64_t u = (g0 + j0 + j) * 64 + lane;
+        const bool on = ((w[j] >> lane) & 1ull) && u < n_iso;
+        a[j] = on ? cptr[u] : 0;
+        e[j] = on ? cptr[u + 1] : 0;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        sum += (unsigned long long)(e[j] - a[j]);
+        mx = max(mx, (u32)min(e[j] - a[j], (int64_t)0x7FFFFFFF));
+      }
+    }
+  }
+  // ---- per block one partial (no same-address atomics beyond the ticket: ~12 ns each) ----
+  __shared__ unsigned long long s_sum[16];
+  __shared__ u32 s_max[16];
+  __shared__ int s_last;
+  auto reduce = [&]() {  // -> thread 0: the block's sum and max
+    for (int o = 32; o > 0; o >>= 1) {
+      sum += __shfl_xor(sum, o, 64);
+      mx = max(mx, (u32)__shfl_xor((int)mx, o, 64));
+    }
+    if (lane == 0) {
+      s_sum[wv] = sum;
+      s_max[wv] = mx;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int k = 1; k < (int)(blockDim.x >> 6); ++k) {
+        sum += s_sum[k];
+        mx = max(mx, s_max[k]);
+      }
+  };
+  reduce();
+  if (threadIdx.x == 0) {
+    part[2 * blockIdx.x] = sum;
+    part[2 * blockIdx.x + 1] = mx;
+    __threadfence();
+    s_last = atomicAdd(&gword[GW_FILL_TICKET], 1) == (int32_t)gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!s_last) return;  // uniform over the block
+  __threadfence();
+  sum = 0ull;
+  mx = 0u;
+  for (unsigned k = threadIdx.x; k < gridDim.x; k += blockDim.x) {
+    sum += __hip_atomic_load(&part[2 * k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    mx = max(mx, (u32)__hip_atomic_load(&part[2 * k + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  }
+  __syncthreads();  // (s_sum / s_max reused)
+  reduce();
+  if (threadIdx.x != 0) return;
+  if (mode == 2 || ((int64_t)sum <= frac_arcs && (int64_t)mx <= cap)) {
+    gword[GW_FILL] = 1;
+    sparse_mark(gword, true, G);
+    gword[GW_ABITS_OK] = 1;
+    gword[GW_FILL_CNT] += 1;
+  }
+}
+
+// Clear the arc bits `m` of word `wd` for the wave's active lanes (act), one atomic per run of
+// neighbouring lanes on the same word: the positions of consecutive slots ascend (the
+// locality order of the build; columns ascend inside a row), so the lanes of one step mostly
+// share a few words, and same-word atomics of one wave would otherwise queue at the word's
+// channel.  A suffix OR over each run (a lane that matches a farther lane across another
+// word only repeats a clear: harmless); the run's first lane issues the atomic.  Runs end at
+// the 16-lane DPP rows: row shifts are VALU moves, while the wave-wide shuffles of a 64-lane
+// merge went through the LDS pipe (18 ds_bpermute per step: the scatter was bound by them).
+template <int kCtrl>
+__device__ __forceinline__ u32 dpp_or_old(u32 old, u32 v) {  // a lane without a source keeps `old`
+  return (u32)__builtin_amdgcn_update_dpp((int)old, (int)v, kCtrl, 0xF, 0xF, false);
+}
+__device__ __forceinline__ void clear_bits_merged(unsigned long long* __restrict__ abits, bool act, u32 wd,
+                                                  unsigned long long m) {
+  const u32 key = act ? wd : 0xFFFFFFFFu;  // (no word has this index: arcs < 2^32)
+  u32 lo = act ? (u32)m : 0u, hi = act ? (u32)(m >> 32) : 0u;
+#define LPA_MERGE_STEP(O)                                             \
+  {                                                                   \
+    const u32 ko = dpp_or_old<0x100 + O>(0xFFFFFFFEu, key); /* row_shl: lane + O */ \
+    const u32 l2 = dpp_or_old<0x100 + O>(0u, lo), h2 = dpp_or_old<0x100 + O>(0u, hi); \
+    if (ko == key) {                                                  \
+      lo |= l2;                                                       \
+      hi |= h2;                                                       \
+    }                                                                 \
+  }
+  LPA_MERGE_STEP(1)
+  LPA_MERGE_STEP(2)
+  LPA_MERGE_STEP(4)
+  LPA_MERGE_STEP(8)
+#undef LPA_MERGE_STEP
+  const u32 kp = dpp_or_old<0x111>(0xFFFFFFFEu, key);  // row_shr 1: lane - 1, a row's first lane none
+  if (act && kp != key) atomicAnd(&abits[wd], ~(((unsigned long long)hi << 32) | lo));
+}
+
+// The scatter of the fill-scatter form: a wave takes 64 consecutive slots at a time (one gbits
+// word; all-G words skipped), a lane per column off G for its cptr and label.  The columns'
+// positions are cut into pieces of kFillPiece dealt over the lanes, so a round writes 64
+// pieces whatever the columns' lengths (mean 2.4 at C3, a tail up to ~100: a lane per
+// column left most lanes idle behind the longest) with kFillPiece position loads in flight
+// per lane; most columns are one piece, so neighbouring lanes still hold the same step's
+// positions of neighbouring columns, which are neighbours in al[] and abits.  A long column
+// is many pieces of one wave (k_fill_decide refuses the form above its cap, lpa_internal.h).
+// kMerge: clear_bits_merged, else one atomic per lane.
+constexpr int kFillPiece = 4;
+constexpr int kFillGroups = 4;
+#ifdef LPA_FILL_PLAIN_ATOMICS  // A/B variant build: the per-lane atomics
+constexpr bool kFillMerge = false;
+#else
+constexpr bool kFillMerge = true;
+#endif
+template <bool kIfWanted, bool kMerge>
+__global__ __launch_bounds__(256) void k_fill_scatter(const unsigned long long* __restrict__ counters, int64_t thr,
+                                                      const unsigned long long* __restrict__ gbits64, int64_t n_iso,
+                                                      const int64_t* __restrict__ cptr,
+                                                      const uint32_t* __restrict__ cpos,
+                                                      const int32_t* __restrict__ L, int32_t* __restrict__ al,
+                                                      unsigned long long* __restrict__ abits,
+                                                      const int32_t* __restrict__ gword) {
+  if (kIfWanted && !rebuild_wanted(counters, thr)) return;
+  if (gword[GW_FILL] == 0) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6, ngrp = (n_iso + 63) >> 6;
+  auto put = [&](bool act, u32 p, int32_t lab) {
+    if (act) al[p] = lab;
+    if (kMerge) clear_bits_merged(abits, act, p >> 6, 1ull << (p & 63u));
+    else if (act) atomicAnd(&abits[p >> 6], ~(1ull << (p & 63u)));
+  };
+  // a wave takes kFillGroups bit words at a time (one load), then group after group
+  for (int64_t g0 = (tid >> 6) * kFillGroups; g0 < ngrp; g0 += nw * kFillGroups) {
+    const unsigned long long offs = lane < kFillGroups && g0 + lane < ngrp ? ~gbits64[g0 + lane] : 0ull;
+    if (__ballot(offs != 0ull) == 0ull) continue;
+    // every group's cptr and label loads first, in flight together
+    int64_t bs[kFillGroups], es[kFillGroups];
+    int32_t ls[kFillGroups];
+#pragma unroll
+    for (int gj = 0; gj < kFillGroups; ++gj) {
+      const unsigned long long off = __shfl(offs, gj, 64);
+      const int64_t u = (g0 + gj) * 64 + lane;
+      const bool on = ((off >> lane) & 1ull) && u < n_iso;
+      bs[gj] = on ? cptr[u] : 0;
+      es[gj] = on ? cptr[u + 1] : 0;
+      ls[gj] = on ? L[u] : 0;
+    }
+#pragma unroll
+    for (int gj = 0; gj < kFillGroups; ++gj) {
+      const int64_t b = bs[gj];
+      const int n = (int)(es[gj] - b);
+      const int32_t lab = ls[gj];
+      if (__ballot(n != 0) == 0ull) continue;
+      // pieces of kFillPiece positions, dealt over the lanes (scatter_runs' search)
+      const int k = (n + kFillPiece - 1) / kFillPiece;
+      int incl = k;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += v;
+      }
+      const int S = __shfl(incl, 63, 64);
+      for (int r0 = 0; r0 < S; r0 += 64) {
+        const int t = r0 + lane;
+        int o = 0;  // the owner: first lane whose inclusive piece count exceeds t
+#pragma unroll
+        for (int st = 32; st >= 1; st >>= 1) {
+          const int ic = __shfl(incl, o + st - 1, 64);
+          if (ic <= t) o += st;
+        }
+        o = o < 64 ? o : 63;
+        const int excl = __shfl(incl, o, 64) - __shfl(k, o, 64);
+        const int64_t bo = __shfl(b, o, 64);
+        const int no = __shfl(n, o, 64);
+        const int32_t lv = __shfl(lab, o, 64);
+        const int p0 = (t - excl) * kFillPiece;
+        const int cnt = t < S ? min(kFillPiece, no - p0) : 0;
+        u32 p[kFillPiece];
+#pragma unroll
+        for (int j = 0; j < kFillPiece; ++j) p[j] = j < cnt ? cpos[bo + p0 + j] : 0u;
+#pragma unroll
+        for (int j = 0; j < kFillPiece; ++j) put(j < cnt, p[j], lv);
+      }
+    }
+  }
 }
 
 // gword[GW_CODE] = take the giant-code refresh: a rebuild is wanted, G is worth trying, and the
@@ -1195,20 +1469,51 @@ int launch_rebuild(lpa_graph* g, bool if_wanted, int64_t thr, const int32_t* L,
   const uint64_t hmask = ranked ? (uint64_t)(g->slice - 1) : ~0ull;
   const int64_t hlim = ranked ? std::min<int64_t>(g->slice, kHotBits / g->nranks / 64 * 64) : kHotBits;
   const int64_t nhot_bits = ranked ? g->nranks * hlim : std::min<int64_t>(g->vpad, kHotBits);
+  // the fill-scatter form of the sparse bits-mode rebuild (LPA_FILL_SCATTER; needs the CSC
+  // position index): its decision and its scatter, launched between k_giant_bits and the
+  // stream rebuild, which stands down when the form is taken
+  auto launch_fill = [&]() -> int {
+    if (!sparse_ok || g->fill_scatter == 0 || g->no_scatter || !g->cptr || !g->cpos || !g->fill_part)
+      return LPA_OK;
+    const int64_t n_iso = g->bin_begin[BIN_ISO];
+    const unsigned long long* gb64 = (const unsigned long long*)g->gbits;
+    const unsigned gd = cap_grid(std::max<int64_t>((n_iso + 1023) / 1024, (g->arcs / 64 + 8191) / 8192), kFillBlocks);
+    const unsigned gs = cap_grid((n_iso + 64 * 4 * kFillGroups - 1) / (64 * 4 * kFillGroups), 8192);
+    const int64_t frac_arcs = (int64_t)(kFillFrac * (double)g->arcs);
+    const int64_t cap = std::max<int64_t>(kFillCap, g->arcs >> kFillCapShift);
+    if (if_wanted) {
+      hipLaunchKernelGGL(k_fill_decide<true>, dim3(gd), dim3(1024), 0, s, ctr, thr, gb64, n_iso, g->cptr, g->arcs,
+                         nhot_bits, g->vpad, g->gword, g->abits, g->al, g->fill_scatter, frac_arcs,
+                         cap, g->fill_part);
+      hipLaunchKernelGGL((k_fill_scatter<true, kFillMerge>), dim3(gs), dim3(256), 0, s, ctr, thr, gb64, n_iso,
+                         g->cptr, g->cpos, L, g->al, g->abits, g->gword);
+    } else {
+      hipLaunchKernelGGL(k_fill_decide<false>, dim3(gd), dim3(1024), 0, s, ctr, thr, gb64, n_iso, g->cptr, g->arcs,
+                         nhot_bits, g->vpad, g->gword, g->abits, g->al, g->fill_scatter, frac_arcs,
+                         cap, g->fill_part);
+      hipLaunchKernelGGL((k_fill_scatter<false, kFillMerge>), dim3(gs), dim3(256), 0, s, ctr, thr, gb64, n_iso,
+                         g->cptr, g->cpos, L, g->al, g->abits, g->gword);
+    }
+    LPA_HIP(hipGetLastError());
+    return LPA_OK;
+  };
   if (g->rebuild_hot && g->nranks == 1 && g->vpad < kHotMinSlots) {
     const int64_t ngrp = (g->vpad + 511) / 512;
     const unsigned gb = cap_grid((ngrp + 3) / 4, 4096), gr = cap_grid((g->arcs + 2047) / 2048, 8192);
-    if (if_wanted) {
+    if (if_wanted)
       hipLaunchKernelGGL(k_giant_bits<true>, dim3(gb), dim3(256), 0, s, ctr, thr, L, g->vpad, g->gword,
                          (unsigned long long*)g->gbits, g->abits, (int64_t)0, hmask, hlim);
-      hipLaunchKernelGGL(k_al_rebuild_small<true>, dim3(gr), dim3(256), 0, s, ctr, thr, g->col, g->arcs, L, g->al,
-                         g->gbits, g->vpad, g->gword, g->abits, sparse_ok);
-    } else {
+    else
       hipLaunchKernelGGL(k_giant_bits<false>, dim3(gb), dim3(256), 0, s, ctr, thr, L, g->vpad, g->gword,
                          (unsigned long long*)g->gbits, g->abits, (int64_t)0, hmask, hlim);
+    LPA_HIP(hipGetLastError());
+    LPA_TRY(launch_fill());
+    if (if_wanted)
+      hipLaunchKernelGGL(k_al_rebuild_small<true>, dim3(gr), dim3(256), 0, s, ctr, thr, g->col, g->arcs, L, g->al,
+                         g->gbits, g->vpad, g->gword, g->abits, sparse_ok);
+    else
       hipLaunchKernelGGL(k_al_rebuild_small<false>, dim3(gr), dim3(256), 0, s, ctr, thr, g->col, g->arcs, L, g->al,
                          g->gbits, g->vpad, g->gword, g->abits, sparse_ok);
-    }
   } else if (g->rebuild_hot && ((g->nranks == 1 && g->vpad <= kHotMaxSlots) || ranked)) {
     int dev_cus = 256;
     (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, g->device);
@@ -1237,6 +1542,7 @@ int launch_rebuild(lpa_graph* g, bool if_wanted, int64_t thr, const int32_t* L,
       hipLaunchKernelGGL(k_giant_bits<false>, dim3(cap_grid((ngrp + 3) / 4, 4096)), dim3(256), 0, s, ctr, thr, L,
                          g->vpad, g->gword, (unsigned long long*)g->gbits, g->abits, nzero, hmask, hlim);
     LPA_HIP(hipGetLastError());
+    LPA_TRY(launch_fill());
     // ranked without a usable bit share: nbits 0 keeps every block in labels mode
     const int64_t nbits = (ranked && hb_lg == 0) ? 0 : g->vpad;
     BlkInfo binfo;

@@ -101,6 +101,9 @@ typedef struct lpa_graph_info {
                               sparse: a one-GPU bits-mode rebuild carries the arcs on the
                               giant label in the arc giant bits and stores only the other
                               arcs' labels (LPA_SPARSE_AL=0: never; since ABI 15)      */
+  int64_t fill_refreshes;  /* ... those of them that took the fill-scatter form: every arc
+                              bit set, then only the columns off the giant label visited
+                              through the CSC index (LPA_FILL_SCATTER=0: never; since ABI 17) */
 } lpa_graph_info;
 
 /* Outlier summary. */
@@ -652,8 +655,9 @@ int lpa_degrees(lpa_graph* g, int32_t* deg_out);
  * ABI 13: lpa_parallel_pagerank.
  * ABI 14: lpa_louvain.
  * ABI 15: sparse_refreshes.
- * ABI 16: lpa_core_numbers. */
-#define LPA_ABI_VERSION 16
+ * ABI 16: lpa_core_numbers.
+ * ABI 17: fill_refreshes. */
+#define LPA_ABI_VERSION 17
 int lpa_abi_version(void);
 int lpa_graph_get_info(const lpa_graph* g, lpa_graph_info* info);
 int lpa_graph_get_info_sized(const lpa_graph* g, lpa_graph_info* info, int64_t info_size);
