@@ -668,6 +668,50 @@ struct PrCsr {
 // and the counters, for V > 0; reads V, m, e_src / e_dst and the stream, synchronises it once
 int pr_build(lpa_graph* g, PrCsr* b);
 
+// The shared edge-list builds (lpa_adj.hip; its header describes the stages).  Every array is a
+// stream-ordered temporary of the caller's Tmp (lpa_algo.h) on the handle's stream.
+struct Tmp;
+// The distinct non-loop arcs of the directed graph, in two steps.  arcs_count: keys, sort,
+// flags, scan; synchronises once and leaves E (loop, nullable: [V] zeroed by the caller, set to
+// 1 at every vertex with a self-loop).  arcs_lists: the out-lists and in-lists from that.
+struct ArcLists {
+  int64_t E = 0;               // distinct arcs
+  int64_t *oo = nullptr, *io = nullptr;      // [V + 1] offsets of the out-lists / the in-lists
+  int32_t *ocol = nullptr, *icol = nullptr;  // [E] their entries, a list ascending
+  u64* keys = nullptr;         // [2 m] between the steps: the sorted keys and the sort's other buffer
+  uint8_t* flag = nullptr;     // [m]
+  u32* pos = nullptr;          // [m + 1]
+};
+int arcs_count(lpa_graph* g, Tmp& tmp, uint8_t* loop, ArcLists* a);
+int arcs_lists(lpa_graph* g, Tmp& tmp, ArcLists* a);
+// The rows that take the wave form (short_max < L <= wave_max; L = off[v + 1] - off[v]) in
+// (*lists)[0, n_rows[0]) and the block form (longer) in (*lists)[V, V + n_rows[1]), ascending.
+// n_rows is host memory, valid after the caller's next synchronisation of the stream
+int form_lists(Tmp& tmp, const int64_t* off, int64_t V, int64_t short_max, int64_t wave_max, int32_t** lists,
+               u32* n_rows);
+// its last kernel alone: the rows flagged in fw / fb at their scanned positions pw / pb
+int fill_form_lists(const uint8_t* fw, const uint8_t* fb, const u32* pw, const u32* pb, int64_t V, int32_t* lists,
+                    hipStream_t s);
+// The canonical simple undirected graph's edges: keys [2 m] sorted (min << 32 | max), first[i]
+// = key i is a simple edge and the first of its value, pos = its scan, E = pos[m] read on the
+// host (one synchronisation).  m == 0: E = 0 and no array
+struct SimpleEdges {
+  u64* keys = nullptr;
+  int32_t* first = nullptr;
+  int64_t* pos = nullptr;
+  int64_t E = 0;
+};
+int simple_edges(lpa_graph* g, Tmp& tmp, SimpleEdges* e);
+// out[v], v in [0, V]: the first of the n keys, ascending in their high (or low) half, whose half is >= v
+int key_bounds(const u64* keys, int64_t n, int64_t V, bool high_half, int64_t* out, hipStream_t s);
+// col[i] = the low half of key i
+int key_col(const u64* keys, int64_t n, int32_t* col, hipStream_t s);
+// Members per component of comp[] (comp[c] == c at every value c) into *size: size_out when that
+// is device memory, else a temporary.  summary: h[0] components, h[1] singletons, h[2] the largest
+// as (size << 32 | 0xFFFFFFFF - id), copied to the host words h (valid after the next synchronisation)
+int comp_sizes(Tmp& tmp, const int32_t* comp, int64_t V, int64_t* size_out, int32_t out_is_device, bool summary,
+               unsigned long long** size, unsigned long long* h);
+
 // static PageRank of the directed multigraph (lpa_pr.hip)
 int pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, int32_t source, double* rank_out,
              int64_t* out_degree_out, int64_t* in_degree_out, int32_t out_is_device, lpa_pagerank_summary* summary);

@@ -1,10 +1,10 @@
 // k-core decomposition of the handle's input multigraph (GraphFrame.coreNumber / kCore):
 // core[v] = the largest k such that v lies in a subgraph of the canonical simple undirected
-// graph (no self-loops, no direction, duplicates collapsed: lpa_tc.hip's) in which every vertex
+// graph (no self-loops, no direction, duplicates collapsed: lpa_adj.hip's) in which every vertex
 // has at least k neighbours; with a cap, min(core[v], max_k).  Integers throughout.
 //
 //   build    keys (min << 32 | max) of every edge, radix-sorted; the first key of each run with
-//            min != max is a simple edge (E of them, as lpa_tc.hip).  Both directions of every
+//            min != max is a simple edge (E of them: lpa_adj.hip, simple_edges).  Both directions of every
 //            simple edge as arc keys (from << 32 | to), sorted by the high half: the CSR
 //            off[] (the first arc of every vertex, by binary search) / col[] (2 E entries).
 //            deg[v] = off[v + 1] - off[v], the live count; the simple degree stays readable
@@ -47,37 +47,12 @@
 // one host read of the tails.  A path of n vertices is n / 2 sub-levels of two vertices: a
 // handful of host round trips instead of n / 2.
 #include "lpa_device.h"
+#include "lpa_algo.h"
 
 namespace lpa {
 
 namespace {
 
-inline unsigned grid_for(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > 65536) b = 65536;
-  return (unsigned)b;
-}
-inline unsigned grid_bh(int64_t n) {
-  const unsigned g = grid_for(n);
-  return g < 2048u ? g : 2048u;
-}
-inline unsigned grid_rows(int64_t nrows, int per_block, int64_t cap) {
-  int64_t b = (nrows + per_block - 1) / per_block;
-  if (b > cap) b = cap;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
-#define GRID_STRIDE(i, n) \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-// the whole block runs every trip (ballots, shuffles and barriers inside)
-#define BLOCK_STRIDE(b, n) \
-  for (int64_t b = (int64_t)blockIdx.x * blockDim.x; b < (n); b += (int64_t)gridDim.x * blockDim.x)
-
-#define KC_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-constexpr int kShortLanes = 8;       // lanes per row of the short form
-constexpr int kBlockThreads = 1024;  // threads per row of the block form, and of the in-block peel
 constexpr int kKcAgg = 2;            // shared fetch-adds tried per trip of the short form
 // The in-block peel walks a wave-form or block-form row with the whole block, one row after
 // another: a row's latency each, where a launch spreads them over the chip.  Such a row counts as
@@ -90,24 +65,7 @@ constexpr int kKcLongRow = 64;
 // largest simple degree and the vertices of simple degree 0
 enum { Q_TAIL = 0, Q_HEAD = 3, K_MIN = 6, N_ALIVE = 7, N_LIST = 8, MAX_DEG = 9, N_CORE0 = 10, C_LEN = 12 };
 
-// ---- build (the simple edges as lpa_tc.hip builds them) ----
-// an id outside [0, V) makes the edge a loop: dropped
-__global__ __launch_bounds__(256) void k_kc_keys(const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
-                                                 int64_t m, u32 V, u64* __restrict__ keys) {
-  GRID_STRIDE(i, m) {
-    const u32 a = (u32)__builtin_nontemporal_load(src + i), b = (u32)__builtin_nontemporal_load(dst + i);
-    const u32 lo = a < b ? a : b, hi = a < b ? b : a;
-    keys[i] = hi < V ? ((u64)lo << 32) | hi : 0ull;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_kc_mark(const u64* __restrict__ keys, int64_t m, int32_t* __restrict__ first) {
-  GRID_STRIDE(i, m) {
-    const u64 k = keys[i];
-    first[i] = ((u32)(k >> 32) != (u32)k && (i == 0 || keys[i - 1] != k)) ? 1 : 0;
-  }
-}
-
+// ---- build (the simple edges: lpa_adj.hip) ----
 // the simple edge at position p: its two arcs at 2 p and 2 p + 1
 __global__ __launch_bounds__(256) void k_kc_arcs(const u64* __restrict__ keys, const int32_t* __restrict__ first,
                                                  const int64_t* __restrict__ pos, int64_t m, u64* __restrict__ arcs) {
@@ -118,24 +76,6 @@ __global__ __launch_bounds__(256) void k_kc_arcs(const u64* __restrict__ keys, c
       arcs[2 * pos[i] + 1] = (k << 32) | (k >> 32);
     }
   }
-}
-
-// arcs ascending in the high half.  off[v], v in [0, V]: the first arc whose high half is >= v
-__global__ __launch_bounds__(256) void k_kc_bounds(const u64* __restrict__ arcs, int64_t n, int64_t V,
-                                                   int64_t* __restrict__ off) {
-  GRID_STRIDE(v, V + 1) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if ((int64_t)(u32)(arcs[mid] >> 32) < v) lo = mid + 1;
-      else hi = mid;
-    }
-    off[v] = lo;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_kc_col(const u64* __restrict__ arcs, int64_t n, int32_t* __restrict__ col) {
-  GRID_STRIDE(i, n) col[i] = (int32_t)(u32)arcs[i];
 }
 
 // the live counts; cnt[MAX_DEG], cnt[N_CORE0]; the alive pass's slots at their start values
@@ -208,7 +148,7 @@ struct Peel {
   // a dead u's neighbour w loses a neighbour; true for the one thread that removes w
   __device__ __forceinline__ bool take(int32_t w) const {
     if (dead[w]) return false;
-    return __hip_atomic_fetch_add(deg + w, -1, KC_RLX) == k + 1;
+    return __hip_atomic_fetch_add(deg + w, -1, LPA_RLX_AGENT) == k + 1;
   }
   // the same for a whole wave (every lane calls it; act: this lane has a w): the lanes that
   // hold the first active lane's w take their number from deg[w] in one add, and the add that
@@ -225,12 +165,12 @@ struct Peel {
       const bool same = act && w == wl;
       const int n = __popcll(__ballot(same));
       if (lane == leader) {
-        const int32_t old = __hip_atomic_fetch_add(deg + wl, -n, KC_RLX);
+        const int32_t old = __hip_atomic_fetch_add(deg + wl, -n, LPA_RLX_AGENT);
         mine = old > k && old - n <= k;
       }
       if (same) act = false;
     }
-    if (act) mine = __hip_atomic_fetch_add(deg + w, -1, KC_RLX) == k + 1;
+    if (act) mine = __hip_atomic_fetch_add(deg + w, -1, LPA_RLX_AGENT) == k + 1;
     return mine;
   }
 };
@@ -377,7 +317,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_kc_peel_block(Peel p, u32 h0,
     const u32 h[3] = {h0, h1, h2};
     u32 base = 0;
     for (int f = 0; f < 3; ++f) {
-      const u32 t = __hip_atomic_load(p.cnt + Q_TAIL + f, KC_RLX);
+      const u32 t = __hip_atomic_load(p.cnt + Q_TAIL + f, LPA_RLX_AGENT);
       for (u32 i = h[f] + tid; i < t; i += kBlockThreads)
         if (base + (i - h[f]) < (u32)kKcPeelCap) q[0][base + (i - h[f])] = p.queue[(int64_t)f * p.V + i];
       base += t - h[f];
@@ -437,30 +377,12 @@ __global__ __launch_bounds__(kBlockThreads) void k_kc_peel_block(Peel p, u32 h0,
     // outgrown, or too much for one block: hd stays at this sub-level's end
     if (nq[cur ^ 1] > (u32)kKcPeelCap || nq[cur ^ 1] + (u32)(kKcLongRow - 1) * nlong > limit) break;
     if (tid == 0)
-      for (int f = 0; f < 3; ++f) hd[f] = __hip_atomic_load(p.cnt + Q_TAIL + f, KC_RLX);
+      for (int f = 0; f < 3; ++f) hd[f] = __hip_atomic_load(p.cnt + Q_TAIL + f, LPA_RLX_AGENT);
     cur ^= 1;
   }
   if (tid == 0)
     for (int f = 0; f < 3; ++f) p.cnt[Q_HEAD + f] = hd[f];
 }
-
-struct Tmp {   // stream-ordered temporaries of one call, and its pinned host words
-  hipStream_t s;
-  void* ptrs[24];
-  int n = 0;
-  u32* pinned = nullptr;
-  explicit Tmp(hipStream_t st) : s(st) {}
-  template <typename T>
-  int get(T** p, int64_t count) {
-    LPA_TRY(tmp_alloc((void**)p, sizeof(T) * (size_t)(count > 0 ? count : 1), s));
-    ptrs[n++] = *p;
-    return LPA_OK;
-  }
-  ~Tmp() {
-    for (int i = 0; i < n; ++i) tmp_free(ptrs[i], s);
-    if (pinned) (void)hipHostFree(pinned);
-  }
-};
 
 // the queued rows [head[f], head[f] + n[f]) of every form f
 void launch_rows(const Peel& p, const u32* head, const u32* n, hipStream_t s) {
@@ -487,45 +409,23 @@ int core_numbers(lpa_graph* g, int32_t max_k, int32_t* core_out, int32_t* simple
   if (V == 0) return LPA_OK;
   Tmp tmp(s);
   // ---- build ----
-  int64_t E = 0;
-  u64 *keys = nullptr, *arcs = nullptr;   // keys [2 m]: the edge keys and the sorts' other buffer
+  SimpleEdges se;   // keys [2 m]: the edge keys and the sorts' other buffer
+  LPA_TRY(simple_edges(g, tmp, &se));
+  const int64_t E = se.E;
   int64_t* off = nullptr;
   int32_t* col = nullptr;
   LPA_TRY(tmp.get(&off, V + 1));
-  const int bits = bits_for((uint64_t)(V - 1));
-  int both[8], hi[4], ns = 0;
-  for (int b = 0; b < bits; b += 8, ++ns) hi[ns] = 32 + b;
-  for (int i = 0; i < ns; ++i) {
-    both[i] = 8 * i;
-    both[ns + i] = 32 + 8 * i;
-  }
-  if (m > 0) {
-    int32_t* first = nullptr;
-    int64_t* pos = nullptr;
-    LPA_TRY(tmp.get(&keys, 2 * m));
-    LPA_TRY(tmp.get(&first, m));
-    LPA_TRY(tmp.get(&pos, m + 1));
-    hipLaunchKernelGGL(k_kc_keys, dim3(grid_for(m)), dim3(256), 0, s, g->e_src, g->e_dst, m, (u32)V, keys);
-    LPA_HIP(hipGetLastError());
-    LPA_TRY(radix_sort_u64(keys, keys + m, m, both, 2 * ns, s));
-    hipLaunchKernelGGL(k_kc_mark, dim3(grid_for(m)), dim3(256), 0, s, keys, m, first);
-    LPA_HIP(hipGetLastError());
-    LPA_TRY(exclusive_scan_i32_i64(first, pos, m, s));
-    LPA_HIP(hipMemcpyAsync(&E, pos + m, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    LPA_HIP(hipStreamSynchronize(s));
-    if (E > 0) {
-      LPA_TRY(tmp.get(&arcs, 2 * E));
-      hipLaunchKernelGGL(k_kc_arcs, dim3(grid_for(m)), dim3(256), 0, s, keys, first, pos, m, arcs);
-      LPA_HIP(hipGetLastError());
-      // the edge keys are spent: keys[0, 2 E) is the sort's other buffer (E <= m)
-      LPA_TRY(radix_sort_u64(arcs, keys, 2 * E, hi, ns, s));
-    }
-  }
   LPA_TRY(tmp.get(&col, 2 * E));
   if (E > 0) {
-    hipLaunchKernelGGL(k_kc_bounds, dim3(grid_for(V + 1)), dim3(256), 0, s, arcs, 2 * E, V, off);
-    hipLaunchKernelGGL(k_kc_col, dim3(grid_for(2 * E)), dim3(256), 0, s, arcs, 2 * E, col);
+    const HalfShifts sh(bits_for((uint64_t)(V - 1)));
+    u64* arcs = nullptr;
+    LPA_TRY(tmp.get(&arcs, 2 * E));
+    hipLaunchKernelGGL(k_kc_arcs, dim3(grid_for(m)), dim3(256), 0, s, se.keys, se.first, se.pos, m, arcs);
     LPA_HIP(hipGetLastError());
+    // the edge keys are spent: keys[0, 2 E) is the sort's other buffer (E <= m)
+    LPA_TRY(radix_sort_u64(arcs, se.keys, 2 * E, sh.hi(), sh.ns, s));
+    LPA_TRY(key_bounds(arcs, 2 * E, V, true, off, s));
+    LPA_TRY(key_col(arcs, 2 * E, col, s));
   } else {
     LPA_HIP(hipMemsetAsync(off, 0, sizeof(int64_t) * (size_t)(V + 1), s));
   }
@@ -537,15 +437,16 @@ int core_numbers(lpa_graph* g, int32_t max_k, int32_t* core_out, int32_t* simple
   LPA_TRY(tmp.get(&dead, V));
   LPA_TRY(tmp.get(&cnt, C_LEN));
   if (!out_is_device) LPA_TRY(tmp.get(&core, V));
-  LPA_HIP(hipHostMalloc((void**)&tmp.pinned, sizeof(u32) * C_LEN, hipHostMallocDefault));
+  u32* pinned = nullptr;
+  LPA_TRY(tmp.pin(&pinned, C_LEN));
   LPA_HIP(hipMemsetAsync(dead, 0, (size_t)V, s));
   LPA_HIP(hipMemsetAsync(cnt, 0, sizeof(u32) * C_LEN, s));
   LPA_HIP(hipMemsetAsync(cnt + K_MIN, 0xFF, sizeof(u32), s));
   hipLaunchKernelGGL(k_kc_init, dim3(grid_bh(V)), dim3(256), 0, s, off, V, deg, cnt);
   LPA_HIP(hipGetLastError());
-  const volatile u32* hc = tmp.pinned;
+  const volatile u32* hc = pinned;
   const auto read_counts = [&]() -> int {
-    LPA_HIP(hipMemcpyAsync(tmp.pinned, cnt, sizeof(u32) * C_LEN, hipMemcpyDeviceToHost, s));
+    LPA_HIP(hipMemcpyAsync(pinned, cnt, sizeof(u32) * C_LEN, hipMemcpyDeviceToHost, s));
     LPA_HIP(hipStreamSynchronize(s));
     return LPA_OK;
   };

@@ -28,16 +28,13 @@
 #include <vector>
 
 #include "lpa_device.h"
+#include "lpa_algo.h"
 
 namespace lpa {
 
 namespace {
 
-typedef unsigned long long ull;
-
-constexpr int kShortLanes = 8;       // lanes per row of the short form
 constexpr int kShortStage = 32;      // entries of a short row staged in LDS (longer: re-read from memory)
-constexpr int kBlockThreads = 1024;  // threads per row of the block form
 constexpr u64 kNoKey = ~0ull;        // a dropped edge / an absent diagonal
 constexpr int32_t kNoCand = 0x7FFFFFFF;
 constexpr int64_t kNoScore = INT64_MIN;   // no real score: |score| <= A^2 < 2^63
@@ -45,23 +42,6 @@ constexpr int64_t kMaxArcs = 3037000499ll;
 
 // the call's counters (ull): proposals, proposals to a smaller id, I, sum of D^2, kept edges
 enum { C_PROP = 0, C_DOWN = 1, C_INTRA = 2, C_SQ = 3, C_KEPT = 4, C_LEN = 8 };
-
-inline unsigned grid_for(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > 65536) b = 65536;
-  return (unsigned)b;
-}
-inline unsigned grid_rows(int64_t nrows, int per_block, int64_t cap) {
-  int64_t b = (nrows + per_block - 1) / per_block;
-  if (b > cap) b = cap;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
-#define GRID_STRIDE(i, n) \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-#define LV_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
 // slots of a spilled row's table: 2 len rounded up to a power of two (< 4 len)
 __host__ __device__ inline u64 spill_slots(int64_t len) {
@@ -215,15 +195,6 @@ __global__ __launch_bounds__(256) void k_lv_forms(const int64_t* __restrict__ of
   }
 }
 
-__global__ __launch_bounds__(256) void k_lv_form_lists(const uint8_t* __restrict__ fw, const uint8_t* __restrict__ fb,
-                                                       const u32* __restrict__ pw, const u32* __restrict__ pb,
-                                                       int64_t n, int32_t* __restrict__ lists) {
-  GRID_STRIDE(u, n) {
-    if (fw[u]) lists[pw[u]] = (int32_t)u;
-    if (fb[u]) lists[n + pb[u]] = (int32_t)u;
-  }
-}
-
 // ---------------------------------------------------------------------------
 // the move kernels
 // ---------------------------------------------------------------------------
@@ -341,8 +312,8 @@ struct Tab {
   u64 mask;
   __device__ __forceinline__ void clear(u64 i) const {
     if constexpr (kGlobal) {
-      __hip_atomic_store(keys + i, -1, LV_RLX);
-      __hip_atomic_store(vals + i, 0ull, LV_RLX);
+      __hip_atomic_store(keys + i, -1, LPA_RLX_AGENT);
+      __hip_atomic_store(vals + i, 0ull, LPA_RLX_AGENT);
     } else {
       keys[i] = -1;
       vals[i] = 0ull;
@@ -354,12 +325,12 @@ struct Tab {
       int32_t old;
       if constexpr (kGlobal) {
         old = -1;
-        if (__hip_atomic_compare_exchange_strong(keys + h, &old, x, __ATOMIC_RELAXED, LV_RLX)) old = -1;
+        if (__hip_atomic_compare_exchange_strong(keys + h, &old, x, __ATOMIC_RELAXED, LPA_RLX_AGENT)) old = -1;
       } else {
         old = atomicCAS(keys + h, -1, x);
       }
       if (old == -1 || old == x) {
-        if constexpr (kGlobal) __hip_atomic_fetch_add(vals + h, wt, LV_RLX);
+        if constexpr (kGlobal) __hip_atomic_fetch_add(vals + h, wt, LPA_RLX_AGENT);
         else atomicAdd(vals + h, wt);
         return;
       }
@@ -367,11 +338,11 @@ struct Tab {
     }
   }
   __device__ __forceinline__ int32_t key(u64 i) const {
-    if constexpr (kGlobal) return __hip_atomic_load(keys + i, LV_RLX);
+    if constexpr (kGlobal) return __hip_atomic_load(keys + i, LPA_RLX_AGENT);
     else return keys[i];
   }
   __device__ __forceinline__ ull val(u64 i) const {
-    if constexpr (kGlobal) return __hip_atomic_load(vals + i, LV_RLX);
+    if constexpr (kGlobal) return __hip_atomic_load(vals + i, LPA_RLX_AGENT);
     else return vals[i];
   }
 };
@@ -602,32 +573,6 @@ __global__ __launch_bounds__(256) void k_lv_summary(const int32_t* __restrict__ 
 // ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
-struct Tmp {   // stream-ordered temporaries of one call, and its pinned host words
-  hipStream_t s;
-  std::vector<void*> ptrs;
-  ull* pinned = nullptr;
-  explicit Tmp(hipStream_t st) : s(st) {}
-  template <typename T>
-  int get(T** p, int64_t count) {
-    LPA_TRY(tmp_alloc((void**)p, sizeof(T) * (size_t)(count > 0 ? count : 1), s));
-    ptrs.push_back(*p);
-    return LPA_OK;
-  }
-  void drop(void* p) {
-    for (size_t i = 0; i < ptrs.size(); ++i)
-      if (ptrs[i] == p) {
-        tmp_free(p, s);
-        ptrs[i] = ptrs.back();
-        ptrs.pop_back();
-        return;
-      }
-  }
-  ~Tmp() {
-    for (void* p : ptrs) tmp_free(p, s);
-    if (pinned) (void)hipHostFree(pinned);
-  }
-};
-
 struct Level {   // one level's weighted CSR, its row lists and its spill table
   int64_t n = 0, nnz = 0;
   int64_t *off = nullptr, *w = nullptr, *s = nullptr, *k = nullptr;
@@ -667,14 +612,8 @@ int build_level(Tmp& tmp, const u64* keys, const int64_t* wt, int64_t M, int64_t
   LPA_TRY(tmp.get(&ww, 2 * M1));
   hipLaunchKernelGGL(k_lv_compact, dim3(grid_for(M)), dim3(256), 0, s, keys, wt, flag, pos, M, kk, ww);
   LPA_HIP(hipGetLastError());
-  const int bits = bits_for((uint64_t)n);
-  int both[8], ns = 0;
-  for (int b = 0; b < bits; b += 8) ++ns;
-  for (int i = 0; i < ns; ++i) {
-    both[i] = 8 * i;
-    both[ns + i] = 32 + 8 * i;
-  }
-  LPA_TRY(radix_sort_u64_kv(kk, ww, kk + M1, ww + M1, M1, both, 2 * ns, s));
+  const HalfShifts sh(bits_for((uint64_t)n));
+  LPA_TRY(radix_sort_u64_kv(kk, ww, kk + M1, ww + M1, M1, sh.both(), 2 * sh.ns, s));
   hipLaunchKernelGGL(k_lv_heads, dim3(grid_for(M1)), dim3(256), 0, s, kk, M1, flag);
   LPA_HIP(hipGetLastError());
   LPA_TRY(exclusive_scan_u8_u32(flag, pos, M1, s));
@@ -713,8 +652,7 @@ int build_level(Tmp& tmp, const u64* keys, const int64_t* wt, int64_t M, int64_t
   LPA_TRY(exclusive_scan_u8_u32(fw, pw, n, s));
   LPA_TRY(exclusive_scan_u8_u32(fb, pb, n, s));
   LPA_TRY(exclusive_scan_i64(need, L->spoff, n, s));
-  hipLaunchKernelGGL(k_lv_form_lists, dim3(grid_for(n)), dim3(256), 0, s, fw, fb, pw, pb, n, L->lists);
-  LPA_HIP(hipGetLastError());
+  LPA_TRY(fill_form_lists(fw, fb, pw, pb, n, L->lists, s));
   int64_t total = 0;
   LPA_HIP(hipMemcpyAsync(&L->n_wave, pw + n, sizeof(u32), hipMemcpyDeviceToHost, s));
   LPA_HIP(hipMemcpyAsync(&L->n_block, pb + n, sizeof(u32), hipMemcpyDeviceToHost, s));
@@ -758,10 +696,11 @@ int louvain(lpa_graph* g, int32_t max_levels, int32_t max_rounds, int32_t* comm_
   LPA_TRY(tmp.get(&acc, C_LEN));
   LPA_TRY(tmp.get(&member, V));
   if (!out_is_device) LPA_TRY(tmp.get(&comm, V));
-  LPA_HIP(hipHostMalloc((void**)&tmp.pinned, sizeof(ull) * C_LEN, hipHostMallocDefault));
-  const volatile ull* hc = tmp.pinned;
+  ull* pinned = nullptr;
+  LPA_TRY(tmp.pin(&pinned, C_LEN));
+  const volatile ull* hc = pinned;
   const auto read_acc = [&]() -> int {
-    LPA_HIP(hipMemcpyAsync(tmp.pinned, acc, sizeof(ull) * C_LEN, hipMemcpyDeviceToHost, s));
+    LPA_HIP(hipMemcpyAsync(pinned, acc, sizeof(ull) * C_LEN, hipMemcpyDeviceToHost, s));
     LPA_HIP(hipStreamSynchronize(s));
     return LPA_OK;
   };

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "lpa_device.h"
+#include "lpa_algo.h"
 
 namespace lpa {
 
@@ -30,25 +31,11 @@ void destroy(lpa_graph* g);
 
 namespace {
 
-inline unsigned grid_for(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > 65536) b = 65536;
-  return (unsigned)b;
-}
-
-// block-aggregated histograms: few blocks, each over a long stretch of the input
-inline unsigned grid_bh(int64_t n) {
-  const unsigned g = grid_for(n);
-  return g < 2048u ? g : 2048u;
-}
 inline unsigned grid_cnt(int64_t n) {
   const unsigned g = grid_for(n);
   return g < 4096u ? g : 4096u;
 }
 
-#define GRID_STRIDE(i, n) \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 // uniform variant: every lane of a wave runs every trip (wave-level ballots inside);
 // `act` says whether this lane holds an element
 #define GRID_STRIDE_UNIFORM_BEGIN(i, act, n)                                         \

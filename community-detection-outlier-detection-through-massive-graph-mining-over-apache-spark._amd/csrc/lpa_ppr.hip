@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "lpa_device.h"
+#include "lpa_algo.h"
 
 #pragma clang fp contract(off)
 
@@ -51,31 +52,8 @@ namespace lpa {
 
 namespace {
 
-inline unsigned grid_for(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > 65536) b = 65536;
-  return (unsigned)b;
-}
-// block-reduced passes: a grid that depends on n alone (the reductions' shape)
-inline unsigned grid_bh(int64_t n) {
-  const unsigned g = grid_for(n);
-  return g < 2048u ? g : 2048u;
-}
-inline unsigned grid_rows(int64_t nrows, int per_block, int64_t cap) {
-  int64_t b = (nrows + per_block - 1) / per_block;
-  if (b > cap) b = cap;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
-#define GRID_STRIDE(i, n) \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-typedef unsigned long long ull;
 typedef double d2 __attribute__((ext_vector_type(2)));   // a lane's two columns: one 16-byte access
 
-constexpr int kShortLanes = 8;      // lanes per row of the short form
-constexpr int kBlockThreads = 1024; // threads per row of the block form
 constexpr int kTile = 64;           // vertices per tile of the transposing finish
 
 struct Pass {   // what a row needs beside its sums
@@ -269,22 +247,6 @@ __global__ __launch_bounds__(256) void k_ppr_scale(const double* __restrict__ r,
   for (int off = 32; off > 0; off >>= 1) pos += (u32)__shfl_xor((int)pos, off, 64);
   if ((threadIdx.x & 63) == 0 && pos) atomicAdd(nz, (ull)pos);
 }
-
-struct Tmp {   // stream-ordered temporaries of one call
-  hipStream_t s;
-  void* ptrs[16];
-  int n = 0;
-  explicit Tmp(hipStream_t st) : s(st) {}
-  template <typename T>
-  int get(T** p, int64_t count) {
-    LPA_TRY(tmp_alloc((void**)p, sizeof(T) * (size_t)(count > 0 ? count : 1), s));
-    ptrs[n++] = *p;
-    return LPA_OK;
-  }
-  ~Tmp() {
-    for (int i = 0; i < n; ++i) tmp_free(ptrs[i], s);
-  }
-};
 
 // the passes over a built CSR; S_all (device) receives batches * B sums, pass by pass
 template <int B>

@@ -46,6 +46,7 @@
 #include <string.h>
 
 #include "lpa_device.h"
+#include "lpa_algo.h"
 
 #pragma clang fp contract(off)
 
@@ -53,46 +54,11 @@ namespace lpa {
 
 namespace {
 
-inline unsigned grid_for(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > 65536) b = 65536;
-  return (unsigned)b;
-}
-// block-reduced passes: a grid that depends on n alone (the reductions' shape)
-inline unsigned grid_bh(int64_t n) {
-  const unsigned g = grid_for(n);
-  return g < 2048u ? g : 2048u;
-}
-
-#define GRID_STRIDE(i, n) \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-typedef unsigned long long ull;
-
-constexpr int kShortLanes = 8;      // lanes per row of the short form
-constexpr int kBlockThreads = 1024; // threads per row of the block form
-
 __global__ __launch_bounds__(256) void k_pr_keys(const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
                                                  int64_t m, u32 V, u64* __restrict__ keys) {
   GRID_STRIDE(i, m) {
     const u32 a = (u32)__builtin_nontemporal_load(src + i), b = (u32)__builtin_nontemporal_load(dst + i);
     keys[i] = a < V && b < V ? ((u64)b << 32) | a : ((u64)V << 32) | V;
-  }
-}
-
-// keys ascending in the half at `shift` (0: sources, 32: destinations).  out[v], v in
-// [0, V]: the first position whose half is >= v
-__global__ __launch_bounds__(256) void k_pr_bounds(const u64* __restrict__ keys, int64_t m, int64_t V, int shift,
-                                                   int64_t* __restrict__ out) {
-  GRID_STRIDE(v, V + 1) {
-    int64_t lo = 0, hi = m;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if ((int64_t)(u32)(keys[mid] >> shift) < v) lo = mid + 1;
-      else hi = mid;
-    }
-    out[v] = lo;
   }
 }
 
@@ -118,10 +84,6 @@ __global__ __launch_bounds__(256) void k_pr_remap(u64* __restrict__ keys, int64_
     const u32 a = (u32)k;
     if (a < V) keys[i] = (k & 0xFFFFFFFF00000000ull) | (u32)slot[a];
   }
-}
-
-__global__ __launch_bounds__(256) void k_pr_col(const u64* __restrict__ keys, int64_t E, int32_t* __restrict__ col) {
-  GRID_STRIDE(i, E) col[i] = (int32_t)(u32)keys[i];
 }
 
 // w of every vertex and its form flags (fw: a wave row, fb: a block row); cnt[0] the
@@ -158,16 +120,6 @@ __global__ __launch_bounds__(256) void k_pr_start(int64_t V, int32_t source, con
     const double rv = source < 0 || v == (int64_t)source ? 1.0 : 0.0;
     r[v] = rv;
     c[slot[v]] = rv * w[v];
-  }
-}
-
-// the flagged rows at their scanned positions: the wave rows in lists, the block rows in lists + V
-__global__ __launch_bounds__(256) void k_pr_lists(const uint8_t* __restrict__ fw, const uint8_t* __restrict__ fb,
-                                                  const u32* __restrict__ pw, const u32* __restrict__ pb, int64_t V,
-                                                  int32_t* __restrict__ lists) {
-  GRID_STRIDE(v, V) {
-    if (fw[v]) lists[pw[v]] = (int32_t)v;
-    if (fb[v]) lists[V + pb[v]] = (int32_t)v;
   }
 }
 
@@ -355,28 +307,6 @@ __global__ __launch_bounds__(256) void k_pr_degrees(const int64_t* __restrict__ 
   }
 }
 
-struct Tmp {   // stream-ordered temporaries of one call
-  hipStream_t s;
-  void* ptrs[24];
-  int n = 0;
-  explicit Tmp(hipStream_t st) : s(st) {}
-  template <typename T>
-  int get(T** p, int64_t count) {
-    LPA_TRY(tmp_alloc((void**)p, sizeof(T) * (size_t)(count > 0 ? count : 1), s));
-    ptrs[n++] = *p;
-    return LPA_OK;
-  }
-  ~Tmp() {
-    for (int i = 0; i < n; ++i) tmp_free(ptrs[i], s);
-  }
-};
-
-inline unsigned grid_rows(int64_t nrows, int per_block, int64_t cap) {
-  int64_t b = (nrows + per_block - 1) / per_block;
-  if (b > cap) b = cap;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
 }  // namespace
 
 PrCsr::~PrCsr() {
@@ -416,19 +346,13 @@ int pr_build(lpa_graph* g, PrCsr* b) {
   int32_t* slot = b->slot;
   // the halves hold values up to V (a dropped edge); the sort is stable, so the passes
   // over the high half keep the source order inside every row
-  const int bits = bits_for((uint64_t)V);
-  int lo[4], hi[4], ns = 0;
-  for (int bit = 0; bit < bits; bit += 8, ++ns) {
-    lo[ns] = bit;
-    hi[ns] = 32 + bit;
-  }
+  const HalfShifts sh(bits_for((uint64_t)V));
   if (m > 0) {
     LPA_TRY(tmp.get(&keys, 2 * m));
     hipLaunchKernelGGL(k_pr_keys, dim3(grid_for(m)), dim3(256), 0, s, g->e_src, g->e_dst, m, (u32)V, keys);
     LPA_HIP(hipGetLastError());
-    LPA_TRY(radix_sort_u64(keys, keys + m, m, lo, ns, s));
-    hipLaunchKernelGGL(k_pr_bounds, dim3(grid_for(V + 1)), dim3(256), 0, s, keys, m, V, 0, op);
-    LPA_HIP(hipGetLastError());
+    LPA_TRY(radix_sort_u64(keys, keys + m, m, sh.lo(), sh.ns, s));
+    LPA_TRY(key_bounds(keys, m, V, false, op, s));
   } else {
     LPA_HIP(hipMemsetAsync(op, 0, sizeof(int64_t) * (size_t)(V + 1), s));
   }
@@ -441,9 +365,8 @@ int pr_build(lpa_graph* g, PrCsr* b) {
   if (m > 0) {
     hipLaunchKernelGGL(k_pr_remap, dim3(grid_for(m)), dim3(256), 0, s, keys, m, (u32)V, slot);
     LPA_HIP(hipGetLastError());
-    LPA_TRY(radix_sort_u64(keys, keys + m, m, hi, ns, s));
-    hipLaunchKernelGGL(k_pr_bounds, dim3(grid_for(V + 1)), dim3(256), 0, s, keys, m, V, 32, rp);
-    LPA_HIP(hipGetLastError());
+    LPA_TRY(radix_sort_u64(keys, keys + m, m, sh.hi(), sh.ns, s));
+    LPA_TRY(key_bounds(keys, m, V, true, rp, s));
   } else {
     LPA_HIP(hipMemsetAsync(rp, 0, sizeof(int64_t) * (size_t)(V + 1), s));
   }
@@ -452,8 +375,7 @@ int pr_build(lpa_graph* g, PrCsr* b) {
   LPA_HIP(hipGetLastError());
   LPA_TRY(exclusive_scan_u8_u32(fw, pw, V, s));
   LPA_TRY(exclusive_scan_u8_u32(fb, pb, V, s));
-  hipLaunchKernelGGL(k_pr_lists, dim3(grid_for(V)), dim3(256), 0, s, fw, fb, pw, pb, V, b->lists);
-  LPA_HIP(hipGetLastError());
+  LPA_TRY(fill_form_lists(fw, fb, pw, pb, V, b->lists, s));
   u32 hc[2] = {0, 0};   // the longest in-list and the sinks
   LPA_HIP(hipMemcpyAsync(&b->E, rp + V, sizeof(int64_t), hipMemcpyDeviceToHost, s));
   LPA_HIP(hipMemcpyAsync(&b->n_wave, pw + V, sizeof(u32), hipMemcpyDeviceToHost, s));
@@ -463,10 +385,7 @@ int pr_build(lpa_graph* g, PrCsr* b) {
   b->max_in = hc[0];
   b->sinks = hc[1];
   LPA_TRY(keep(&b->col, b->E));
-  if (b->E > 0) {
-    hipLaunchKernelGGL(k_pr_col, dim3(grid_for(b->E)), dim3(256), 0, s, keys, b->E, b->col);
-    LPA_HIP(hipGetLastError());
-  }
+  if (b->E > 0) LPA_TRY(key_col(keys, b->E, b->col, s));
   return LPA_OK;
 }
 

@@ -6,11 +6,9 @@
 // fact about its vertex (loop[v]: it is never trimmed).  Integers throughout.
 //
 // GraphX's rounds are Orzan's colouring algorithm, and so are these:
-//   build    keys (src << 32 | dst) of every in-range non-loop edge, radix sort, unique:
-//            E distinct arcs; out-lists oo / ocol; the halves swapped and sorted again by
-//            the new high half: in-lists io / icol (as lpa_sp.hip).  loop[v] = 1 by plain
-//            byte stores from the raw edge list.  outc[v] / inc[v] = the list lengths: the
-//            live out- and in-counts
+//   build    the E distinct non-loop arcs (lpa_adj.hip: arcs_count, arcs_lists): out-lists
+//            oo / ocol, in-lists io / icol.  loop[v] = 1 by plain byte stores from the raw
+//            edge list.  outc[v] / inc[v] = the list lengths: the live out- and in-counts
 //   round    while a vertex is alive and rounds < max_iter: ++rounds, then
 //   write    (from round 2 on) every marked v: comp[v] = colour[v], dead, appended to the
 //            removal queue.  Round 1 instead: every v without a loop and with an empty
@@ -36,7 +34,7 @@
 //   mark     roots = alive v with colour[v] == v; a backward breadth-first search over the
 //            in-lists, restricted to alive unmarked vertices of the frontier vertex's colour
 //            (bit ST_MARK of the state byte, claimed by the same atomic OR)
-//   finish   sizes and the summary from comp[], exact integers, as lpa_cc.hip
+//   finish   sizes and the summary from comp[], exact integers (lpa_adj.hip: comp_sizes)
 //
 // Row forms, by list length L (kSccShort / kSccWave; out + in for the trim, out for the
 // colour push, in for the colour pull and the mark):
@@ -63,36 +61,12 @@
 // colour[] are only touched by agent-scope atomics where they are shared.  Lists written by
 // one kernel are read by the next.
 #include "lpa_device.h"
+#include "lpa_algo.h"
 
 namespace lpa {
 
 namespace {
 
-inline unsigned grid_for(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > 65536) b = 65536;
-  return (unsigned)b;
-}
-inline unsigned grid_bh(int64_t n) {
-  const unsigned g = grid_for(n);
-  return g < 2048u ? g : 2048u;
-}
-inline unsigned grid_rows(int64_t nrows, int per_block, int64_t cap) {
-  int64_t b = (nrows + per_block - 1) / per_block;
-  if (b > cap) b = cap;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
-#define GRID_STRIDE(i, n) \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-#define SCC_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-typedef unsigned long long ull;
-
-constexpr int kShortLanes = 8;      // lanes per row of the short forms
-constexpr int kBlockThreads = 1024; // threads per row of the block forms
 constexpr u32 ST_DEAD = 1, ST_MARK = 2;   // bits of a state byte (0: alive and unmarked)
 
 // slots of the call's counters (u32): the removal queue's tails and, after an in-block trim,
@@ -115,7 +89,7 @@ __device__ __forceinline__ int64_t in_len(const Adj& a, int64_t v) { return a.io
 __device__ __forceinline__ bool claim(uint8_t* bytes, int32_t v, u32 bit) {
   u32* w = reinterpret_cast<u32*>(bytes) + ((u32)v >> 2);
   const u32 m = bit << (8 * ((u32)v & 3u));
-  return (__hip_atomic_fetch_or(w, m, SCC_RLX) & m) == 0;
+  return (__hip_atomic_fetch_or(w, m, LPA_RLX_AGENT) & m) == 0;
 }
 
 // v at the end of the list of form f (lists + f V, length cnt[f]); the address of each add
@@ -125,78 +99,6 @@ __device__ __forceinline__ void append(int32_t* __restrict__ lists, int64_t V, u
 #pragma unroll
   for (int k = 0; k < 3; ++k)
     if (f == k) lists[(int64_t)k * V + atomicAdd(cnt + k, 1u)] = v;
-}
-
-// ---- build (the arcs as lpa_sp.hip builds them) ----
-__global__ __launch_bounds__(256) void k_scc_keys(const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
-                                                  int64_t m, u32 V, u64* __restrict__ keys,
-                                                  uint8_t* __restrict__ loop) {
-  GRID_STRIDE(i, m) {
-    const u32 a = (u32)__builtin_nontemporal_load(src + i), b = (u32)__builtin_nontemporal_load(dst + i);
-    keys[i] = a < V && b < V && a != b ? ((u64)a << 32) | b : ((u64)V << 32) | V;
-    if (a == b && a < V) loop[a] = 1;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_scc_uniq(const u64* __restrict__ keys, int64_t m, u32 V,
-                                                  uint8_t* __restrict__ flag) {
-  GRID_STRIDE(i, m) {
-    const u64 k = keys[i];
-    flag[i] = (u32)(k >> 32) < V && (i == 0 || keys[i - 1] != k) ? 1 : 0;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_scc_compact(const u64* __restrict__ keys, const uint8_t* __restrict__ flag,
-                                                     const u32* __restrict__ pos, int64_t m, u64* __restrict__ out) {
-  GRID_STRIDE(i, m) {
-    if (flag[i]) out[pos[i]] = keys[i];
-  }
-}
-
-__global__ __launch_bounds__(256) void k_scc_split(const u64* __restrict__ okeys, int64_t E,
-                                                   int32_t* __restrict__ ocol, u64* __restrict__ tkeys) {
-  GRID_STRIDE(i, E) {
-    const u64 k = okeys[i];
-    ocol[i] = (int32_t)(u32)k;
-    tkeys[i] = (k << 32) | (k >> 32);
-  }
-}
-
-__global__ __launch_bounds__(256) void k_scc_col(const u64* __restrict__ keys, int64_t E, int32_t* __restrict__ col) {
-  GRID_STRIDE(i, E) col[i] = (int32_t)(u32)keys[i];
-}
-
-// keys ascending in the high half.  out[v], v in [0, V]: the first position whose high half is >= v
-__global__ __launch_bounds__(256) void k_scc_bounds(const u64* __restrict__ keys, int64_t n, int64_t V,
-                                                    int64_t* __restrict__ out) {
-  GRID_STRIDE(v, V + 1) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if ((int64_t)(u32)(keys[mid] >> 32) < v) lo = mid + 1;
-      else hi = mid;
-    }
-    out[v] = lo;
-  }
-}
-
-// the pull's static forms, by in-list length (fw: a wave row, fb: a block row)
-__global__ __launch_bounds__(256) void k_scc_forms(const int64_t* __restrict__ io, int64_t V, uint8_t* __restrict__ fw,
-                                                   uint8_t* __restrict__ fb) {
-  GRID_STRIDE(v, V) {
-    const int f = form_of(io[v + 1] - io[v]);
-    fw[v] = f == 1 ? 1 : 0;
-    fb[v] = f == 2 ? 1 : 0;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_scc_form_lists(const uint8_t* __restrict__ fw, const uint8_t* __restrict__ fb,
-                                                        const u32* __restrict__ pw, const u32* __restrict__ pb,
-                                                        int64_t V, int32_t* __restrict__ lists) {
-  GRID_STRIDE(v, V) {
-    if (fw[v]) lists[pw[v]] = (int32_t)v;
-    if (fb[v]) lists[V + pb[v]] = (int32_t)v;
-  }
 }
 
 // ---- listed rows, by form: op.begin(u) once per lane, then op.visit(ctx, j, w) for every
@@ -256,7 +158,7 @@ struct TrimOp {
   // that emptied a count of w and this thread is the one that removes w
   __device__ __forceinline__ bool take(int j, int32_t w) const {
     if (st[w] & ST_DEAD) return false;
-    if (__hip_atomic_fetch_add((j == 0 ? inc : outc) + w, -1, SCC_RLX) != 1 || loop[w]) return false;
+    if (__hip_atomic_fetch_add((j == 0 ? inc : outc) + w, -1, LPA_RLX_AGENT) != 1 || loop[w]) return false;
     return claim(st, w, ST_DEAD);
   }
   __device__ __forceinline__ void visit(int, int j, int32_t w) const {
@@ -321,7 +223,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_scc_trim_block(TrimOp op, u32
     const u32 h[3] = {h0, h1, h2};
     u32 base = 0;
     for (int f = 0; f < 3; ++f) {
-      const u32 t = __hip_atomic_load(op.cnt + Q_TAIL + f, SCC_RLX);
+      const u32 t = __hip_atomic_load(op.cnt + Q_TAIL + f, LPA_RLX_AGENT);
       for (u32 i = h[f] + tid; i < t; i += kBlockThreads)
         if (base + (i - h[f]) < (u32)kSccTrimCap) q[0][base + (i - h[f])] = op.queue[(int64_t)f * op.V + i];
       base += t - h[f];
@@ -351,7 +253,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_scc_trim_block(TrimOp op, u32
     __syncthreads();   // every append of the level has returned
     if (nq[cur ^ 1] > (u32)kSccTrimCap) break;   // outgrown: hd stays at this level's start
     if (tid == 0)
-      for (int f = 0; f < 3; ++f) hd[f] = __hip_atomic_load(op.cnt + Q_TAIL + f, SCC_RLX);
+      for (int f = 0; f < 3; ++f) hd[f] = __hip_atomic_load(op.cnt + Q_TAIL + f, LPA_RLX_AGENT);
     cur ^= 1;
   }
   if (tid == 0)
@@ -468,7 +370,7 @@ struct PushOp {
   u32* cnt;             // their lengths
   __device__ __forceinline__ int32_t begin(int32_t u) const {
     flag_cur[u] = 0;
-    return __hip_atomic_load(colour + u, SCC_RLX);
+    return __hip_atomic_load(colour + u, LPA_RLX_AGENT);
   }
   __device__ __forceinline__ void list(int, const int64_t*& off, const int32_t*& col) const {
     off = a.oo;
@@ -476,7 +378,7 @@ struct PushOp {
   }
   __device__ __forceinline__ void visit(int32_t c, int, int32_t w) const {
     if (st[w] != 0) return;
-    if (__hip_atomic_fetch_min(colour + w, c, SCC_RLX) <= c) return;
+    if (__hip_atomic_fetch_min(colour + w, c, LPA_RLX_AGENT) <= c) return;
     const int64_t Lo = out_len(a, w);
     if (Lo > 0 && claim(flag_next, w, 1u)) append(next, V, cnt, form_of(Lo), w);
   }
@@ -515,75 +417,6 @@ struct MarkOp {
   }
 };
 
-// ---- sizes and the summary (as lpa_cc.hip: comp[c] == c at every value c of comp) ----
-__global__ __launch_bounds__(256) void k_scc_sizes(const int32_t* __restrict__ comp, int64_t V,
-                                                   ull* __restrict__ size) {
-  __shared__ u32 bk[dev::kBhSlots];
-  __shared__ ull bv[dev::kBhSlots];
-  __shared__ int bsat;
-  dev::BlockHist<ull> bh{bk, bv, &bsat};
-  bh.init();
-  const int lane = threadIdx.x & 63;
-  for (int64_t b = (int64_t)blockIdx.x * blockDim.x; b < V; b += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t v = b + threadIdx.x;
-    const bool act = v < V;
-    bh.add1(size, act, act ? (u32)comp[v] : 0u, lane);
-  }
-  bh.flush(size);
-}
-
-// acc[0] components, [1] singletons, [2] max of (size << 32 | 0xFFFFFFFF - id)
-__global__ __launch_bounds__(256) void k_scc_summary(const int32_t* __restrict__ comp, const ull* __restrict__ size,
-                                                     int64_t V, ull* __restrict__ acc) {
-  __shared__ ull ws[3][4];
-  ull n = 0, n1 = 0, best = 0;
-  GRID_STRIDE(v, V) {
-    if (comp[v] == (int32_t)v) {
-      const ull sz = size[v];
-      n += 1;
-      n1 += sz == 1ull ? 1ull : 0ull;
-      best = dev::umax64(best, (sz << 32) | (ull)(0xFFFFFFFFu - (u32)v));
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    n += __shfl_xor(n, off, 64);
-    n1 += __shfl_xor(n1, off, 64);
-    best = dev::umax64(best, __shfl_xor(best, off, 64));
-  }
-  if ((threadIdx.x & 63) == 0) {
-    ws[0][threadIdx.x >> 6] = n;
-    ws[1][threadIdx.x >> 6] = n1;
-    ws[2][threadIdx.x >> 6] = best;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    n = ws[0][0] + ws[0][1] + ws[0][2] + ws[0][3];
-    n1 = ws[1][0] + ws[1][1] + ws[1][2] + ws[1][3];
-    best = dev::umax64(dev::umax64(ws[2][0], ws[2][1]), dev::umax64(ws[2][2], ws[2][3]));
-    if (n) atomicAdd(&acc[0], n);
-    if (n1) atomicAdd(&acc[1], n1);
-    if (best) atomicMax(&acc[2], best);
-  }
-}
-
-struct Tmp {   // stream-ordered temporaries of one call, and its pinned host words
-  hipStream_t s;
-  void* ptrs[40];
-  int n = 0;
-  u32* pinned = nullptr;
-  explicit Tmp(hipStream_t st) : s(st) {}
-  template <typename T>
-  int get(T** p, int64_t count) {
-    LPA_TRY(tmp_alloc((void**)p, sizeof(T) * (size_t)(count > 0 ? count : 1), s));
-    ptrs[n++] = *p;
-    return LPA_OK;
-  }
-  ~Tmp() {
-    for (int i = 0; i < n; ++i) tmp_free(ptrs[i], s);
-    if (pinned) (void)hipHostFree(pinned);
-  }
-};
-
 // the listed rows [head[f], head[f] + n[f]) of every form f
 template <class Op>
 void launch_rows(const Op& op, const int32_t* lists, int64_t V, const u32* head, const u32* n, hipStream_t s) {
@@ -605,78 +438,22 @@ void launch_rows(const Op& op, const int32_t* lists, int64_t V, const u32* head,
 int strongly_connected_components(lpa_graph* g, int32_t max_iter, int32_t* comp_out, int32_t out_is_device,
                                   int64_t* size_out, lpa_scc_summary* summary) {
   hipStream_t s = g->stream;
-  const int64_t V = g->V, m = g->m;
+  const int64_t V = g->V;
   if (summary) *summary = lpa_scc_summary{0, 0, 0, -1, 0, 0, 0};
   if (V == 0) return LPA_OK;
   Tmp tmp(s);
   // ---- build ----
-  u64* keys = nullptr;   // [2 m]: the keys and the sort's other buffer
-  uint8_t *flag = nullptr, *loop = nullptr;
-  u32* pos = nullptr;
-  int64_t *oo = nullptr, *io = nullptr;
-  int32_t *ocol = nullptr, *icol = nullptr;
-  LPA_TRY(tmp.get(&oo, V + 1));
-  LPA_TRY(tmp.get(&io, V + 1));
+  uint8_t* loop = nullptr;
   LPA_TRY(tmp.get(&loop, V));
   LPA_HIP(hipMemsetAsync(loop, 0, (size_t)V, s));
-  int64_t E = 0;
-  const int bits = bits_for((uint64_t)V);   // the halves hold values up to V (a dropped edge)
-  int both[8], hi[4], ns = 0;
-  for (int b = 0; b < bits; b += 8, ++ns) hi[ns] = 32 + b;
-  for (int i = 0; i < ns; ++i) {
-    both[i] = 8 * i;
-    both[ns + i] = 32 + 8 * i;
-  }
-  if (m > 0) {
-    LPA_TRY(tmp.get(&keys, 2 * m));
-    LPA_TRY(tmp.get(&flag, m));
-    LPA_TRY(tmp.get(&pos, m + 1));
-    hipLaunchKernelGGL(k_scc_keys, dim3(grid_for(m)), dim3(256), 0, s, g->e_src, g->e_dst, m, (u32)V, keys, loop);
-    LPA_HIP(hipGetLastError());
-    LPA_TRY(radix_sort_u64(keys, keys + m, m, both, 2 * ns, s));
-    hipLaunchKernelGGL(k_scc_uniq, dim3(grid_for(m)), dim3(256), 0, s, keys, m, (u32)V, flag);
-    LPA_HIP(hipGetLastError());
-    LPA_TRY(exclusive_scan_u8_u32(flag, pos, m, s));
-    u32 hE = 0;
-    LPA_HIP(hipMemcpyAsync(&hE, pos + m, sizeof(u32), hipMemcpyDeviceToHost, s));
-    LPA_HIP(hipStreamSynchronize(s));
-    E = (int64_t)hE;
-  }
-  LPA_TRY(tmp.get(&ocol, E));
-  LPA_TRY(tmp.get(&icol, E));
-  if (E > 0) {
-    u64* okeys = keys + m;   // the arcs in (src, dst) order; then the second sort's other buffer
-    hipLaunchKernelGGL(k_scc_compact, dim3(grid_for(m)), dim3(256), 0, s, keys, flag, pos, m, okeys);
-    hipLaunchKernelGGL(k_scc_split, dim3(grid_for(E)), dim3(256), 0, s, okeys, E, ocol, keys);
-    hipLaunchKernelGGL(k_scc_bounds, dim3(grid_for(V + 1)), dim3(256), 0, s, okeys, E, V, oo);
-    LPA_HIP(hipGetLastError());
-    LPA_TRY(radix_sort_u64(keys, okeys, E, hi, ns, s));
-    hipLaunchKernelGGL(k_scc_bounds, dim3(grid_for(V + 1)), dim3(256), 0, s, keys, E, V, io);
-    hipLaunchKernelGGL(k_scc_col, dim3(grid_for(E)), dim3(256), 0, s, keys, E, icol);
-    LPA_HIP(hipGetLastError());
-  } else {
-    LPA_HIP(hipMemsetAsync(oo, 0, sizeof(int64_t) * (size_t)(V + 1), s));
-    LPA_HIP(hipMemsetAsync(io, 0, sizeof(int64_t) * (size_t)(V + 1), s));
-  }
-  const Adj adj{oo, ocol, io, icol};
+  ArcLists arcs;
+  LPA_TRY(arcs_count(g, tmp, loop, &arcs));
+  LPA_TRY(arcs_lists(g, tmp, &arcs));
+  const Adj adj{arcs.oo, arcs.ocol, arcs.io, arcs.icol};
   // the pull's static lists, by in-list length
-  uint8_t *fw = nullptr, *fb = nullptr;
-  u32 *pw = nullptr, *pb = nullptr;
   int32_t* plists = nullptr;
-  LPA_TRY(tmp.get(&fw, V));
-  LPA_TRY(tmp.get(&fb, V));
-  LPA_TRY(tmp.get(&pw, V + 1));
-  LPA_TRY(tmp.get(&pb, V + 1));
-  LPA_TRY(tmp.get(&plists, 2 * V));
-  hipLaunchKernelGGL(k_scc_forms, dim3(grid_for(V)), dim3(256), 0, s, io, V, fw, fb);
-  LPA_HIP(hipGetLastError());
-  LPA_TRY(exclusive_scan_u8_u32(fw, pw, V, s));
-  LPA_TRY(exclusive_scan_u8_u32(fb, pb, V, s));
-  hipLaunchKernelGGL(k_scc_form_lists, dim3(grid_for(V)), dim3(256), 0, s, fw, fb, pw, pb, V, plists);
-  LPA_HIP(hipGetLastError());
-  u32 hp[2] = {0, 0};   // the pull's wave rows and block rows
-  LPA_HIP(hipMemcpyAsync(&hp[0], pw + V, sizeof(u32), hipMemcpyDeviceToHost, s));
-  LPA_HIP(hipMemcpyAsync(&hp[1], pb + V, sizeof(u32), hipMemcpyDeviceToHost, s));
+  u32 hp[2] = {0, 0};   // the pull's wave rows and block rows (read after the first read_counts below)
+  LPA_TRY(form_lists(tmp, arcs.io, V, kSccShort, kSccWave, &plists, hp));
   // ---- state ----
   const int64_t vbytes = (V + 3) & ~(int64_t)3;   // byte arrays claimed through their words
   int32_t *outc = nullptr, *inc = nullptr, *colour = nullptr, *queue = nullptr, *flists = nullptr, *comp = comp_out;
@@ -691,13 +468,14 @@ int strongly_connected_components(lpa_graph* g, int32_t max_iter, int32_t* comp_
   LPA_TRY(tmp.get(&fl, 2 * vbytes));  // the colour frontier's flags, per level parity
   LPA_TRY(tmp.get(&cnt, C_LEN));
   if (!out_is_device) LPA_TRY(tmp.get(&comp, V));
-  LPA_HIP(hipHostMalloc((void**)&tmp.pinned, sizeof(u32) * C_LEN, hipHostMallocDefault));
+  u32* pinned = nullptr;
+  LPA_TRY(tmp.pin(&pinned, C_LEN));
   LPA_HIP(hipMemsetAsync(st, 0, (size_t)vbytes, s));
   LPA_HIP(hipMemsetAsync(fl, 0, (size_t)(2 * vbytes), s));
   LPA_HIP(hipMemsetAsync(cnt, 0, sizeof(u32) * C_LEN, s));
-  const volatile u32* hc = tmp.pinned;
+  const volatile u32* hc = pinned;
   const auto read_counts = [&]() -> int {
-    LPA_HIP(hipMemcpyAsync(tmp.pinned, cnt, sizeof(u32) * C_LEN, hipMemcpyDeviceToHost, s));
+    LPA_HIP(hipMemcpyAsync(pinned, cnt, sizeof(u32) * C_LEN, hipMemcpyDeviceToHost, s));
     LPA_HIP(hipStreamSynchronize(s));
     return LPA_OK;
   };
@@ -777,21 +555,8 @@ int strongly_connected_components(lpa_graph* g, int32_t max_iter, int32_t* comp_
   }
   // ---- sizes and the summary ----
   ull h[3] = {0, 0, 0};
-  ull *size = nullptr, *acc = nullptr;
-  if (size_out || summary) {
-    size = reinterpret_cast<ull*>(size_out);
-    if (!size_out || !out_is_device) LPA_TRY(tmp.get(&size, V));
-    LPA_HIP(hipMemsetAsync(size, 0, sizeof(ull) * (size_t)V, s));
-    hipLaunchKernelGGL(k_scc_sizes, dim3(grid_bh(V)), dim3(256), 0, s, comp, V, size);
-    LPA_HIP(hipGetLastError());
-    if (summary) {
-      LPA_TRY(tmp.get(&acc, 3));
-      LPA_HIP(hipMemsetAsync(acc, 0, sizeof(h), s));
-      hipLaunchKernelGGL(k_scc_summary, dim3(grid_bh(V)), dim3(256), 0, s, comp, size, V, acc);
-      LPA_HIP(hipGetLastError());
-      LPA_HIP(hipMemcpyAsync(h, acc, sizeof(h), hipMemcpyDeviceToHost, s));
-    }
-  }
+  ull* size = nullptr;
+  if (size_out || summary) LPA_TRY(comp_sizes(tmp, comp, V, size_out, out_is_device, summary != nullptr, &size, h));
   if (!out_is_device) {
     LPA_HIP(hipMemcpyAsync(comp_out, comp, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost, s));
     if (size_out) LPA_HIP(hipMemcpyAsync(size_out, size, sizeof(int64_t) * (size_t)V, hipMemcpyDeviceToHost, s));

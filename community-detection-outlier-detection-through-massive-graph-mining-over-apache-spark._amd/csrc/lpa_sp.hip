@@ -8,15 +8,9 @@
 // bit b = landmark b of the batch, a wave64 ballot's width.  A level ORs words along arcs;
 // the distance is the level at which a bit first appeared.
 //
-//   keys     (src << 32 | dst) of every in-range non-loop edge (anything else gets
-//            (V << 32 | V) and sorts behind every vertex)
-//   sort     radix sort over both halves; a key that differs from its predecessor is kept
-//            (flag byte, scan, compaction): E distinct arcs in (src, dst) order
-//   out      oo[u] = the first arc with source >= u (a binary search per vertex),
-//            ocol[i] = the low half: the out-lists, for the pull
-//   in       the halves swapped and sorted again by the new high half alone (the sort is
-//            stable: sources stay ascending inside a row); io[v], icol[i] alike: the
-//            in-lists, for the push.  Offsets int64, ids int32
+//   build    the E distinct non-loop arcs (lpa_adj.hip: arcs_count, arcs_lists): the
+//            out-lists oo / ocol, for the pull, and the in-lists io / icol, for the push.
+//            Offsets int64, ids int32
 //   batch    seen = front = next = 0, the batch's distance rows -1; next[landmark b] |= bit b
 //   level    settle, read four counts on the host, stop at an empty frontier, else expand
 //   settle   new = next & ~seen; seen |= new; front = new; next = 0; every set bit b of
@@ -55,30 +49,12 @@
 // of (V, arc set, landmarks) alone.  Only push_levels / pull_levels tell the schedule; their
 // sum is, over the batches, the batch's largest distance + 1.
 #include "lpa_device.h"
+#include "lpa_algo.h"
 
 namespace lpa {
 
 namespace {
 
-inline unsigned grid_for(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > 65536) b = 65536;
-  return (unsigned)b;
-}
-inline unsigned grid_rows(int64_t nrows, int per_block, int64_t cap) {
-  int64_t b = (nrows + per_block - 1) / per_block;
-  if (b > cap) b = cap;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
-#define GRID_STRIDE(i, n) \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
-typedef unsigned long long ull;
-
-constexpr int kShortLanes = 8;      // lanes per row of the short forms
-constexpr int kBlockThreads = 1024; // threads per row of the block forms
 constexpr int kSpBeta = 24;         // back to the push when the frontier falls below V / kSpBeta
 
 // slots of the per-level counters
@@ -97,79 +73,6 @@ __device__ __forceinline__ ull sp_wave_add(ull x) {
 }
 __device__ __forceinline__ void sp_or(ull* p, ull w) {
   __hip_atomic_fetch_or(p, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ---- build ----
-__global__ __launch_bounds__(256) void k_sp_keys(const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
-                                                 int64_t m, u32 V, u64* __restrict__ keys) {
-  GRID_STRIDE(i, m) {
-    const u32 a = (u32)__builtin_nontemporal_load(src + i), b = (u32)__builtin_nontemporal_load(dst + i);
-    keys[i] = a < V && b < V && a != b ? ((u64)a << 32) | b : ((u64)V << 32) | V;
-  }
-}
-
-// keys ascending: flag[i] = key i is an arc and the first of its value
-__global__ __launch_bounds__(256) void k_sp_uniq(const u64* __restrict__ keys, int64_t m, u32 V,
-                                                 uint8_t* __restrict__ flag) {
-  GRID_STRIDE(i, m) {
-    const u64 k = keys[i];
-    flag[i] = (u32)(k >> 32) < V && (i == 0 || keys[i - 1] != k) ? 1 : 0;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_sp_compact(const u64* __restrict__ keys, const uint8_t* __restrict__ flag,
-                                                    const u32* __restrict__ pos, int64_t m, u64* __restrict__ out) {
-  GRID_STRIDE(i, m) {
-    if (flag[i]) out[pos[i]] = keys[i];
-  }
-}
-
-// the arcs in (src, dst) order: the out-list columns, and the keys with their halves swapped
-__global__ __launch_bounds__(256) void k_sp_split(const u64* __restrict__ okeys, int64_t E, int32_t* __restrict__ ocol,
-                                                  u64* __restrict__ tkeys) {
-  GRID_STRIDE(i, E) {
-    const u64 k = okeys[i];
-    ocol[i] = (int32_t)(u32)k;
-    tkeys[i] = (k << 32) | (k >> 32);
-  }
-}
-
-__global__ __launch_bounds__(256) void k_sp_col(const u64* __restrict__ keys, int64_t E, int32_t* __restrict__ col) {
-  GRID_STRIDE(i, E) col[i] = (int32_t)(u32)keys[i];
-}
-
-// keys ascending in the high half.  out[v], v in [0, V]: the first position whose high half is >= v
-__global__ __launch_bounds__(256) void k_sp_bounds(const u64* __restrict__ keys, int64_t n, int64_t V,
-                                                   int64_t* __restrict__ out) {
-  GRID_STRIDE(v, V + 1) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if ((int64_t)(u32)(keys[mid] >> 32) < v) lo = mid + 1;
-      else hi = mid;
-    }
-    out[v] = lo;
-  }
-}
-
-// the pull's static forms, by out-degree (fw: a wave row, fb: a block row)
-__global__ __launch_bounds__(256) void k_sp_forms(const int64_t* __restrict__ oo, int64_t V, uint8_t* __restrict__ fw,
-                                                  uint8_t* __restrict__ fb) {
-  GRID_STRIDE(v, V) {
-    const int64_t L = oo[v + 1] - oo[v];
-    fw[v] = L > kSpShort && L <= kSpWave ? 1 : 0;
-    fb[v] = L > kSpWave ? 1 : 0;
-  }
-}
-
-// the flagged rows at their scanned positions: the wave rows in lists, the block rows in lists + V
-__global__ __launch_bounds__(256) void k_sp_form_lists(const uint8_t* __restrict__ fw, const uint8_t* __restrict__ fb,
-                                                       const u32* __restrict__ pw, const u32* __restrict__ pb,
-                                                       int64_t V, int32_t* __restrict__ lists) {
-  GRID_STRIDE(v, V) {
-    if (fw[v]) lists[pw[v]] = (int32_t)v;
-    if (fb[v]) lists[V + pb[v]] = (int32_t)v;
-  }
 }
 
 // ---- a batch ----
@@ -398,24 +301,6 @@ __global__ __launch_bounds__(kBlockThreads) void k_sp_pull_block(const int32_t* 
   }
 }
 
-struct Tmp {   // stream-ordered temporaries of one call, and its pinned host words
-  hipStream_t s;
-  void* ptrs[32];
-  int n = 0;
-  ull* pinned = nullptr;
-  explicit Tmp(hipStream_t st) : s(st) {}
-  template <typename T>
-  int get(T** p, int64_t count) {
-    LPA_TRY(tmp_alloc((void**)p, sizeof(T) * (size_t)(count > 0 ? count : 1), s));
-    ptrs[n++] = *p;
-    return LPA_OK;
-  }
-  ~Tmp() {
-    for (int i = 0; i < n; ++i) tmp_free(ptrs[i], s);
-    if (pinned) (void)hipHostFree(pinned);
-  }
-};
-
 }  // namespace
 
 // Reads V, m, e_src / e_dst, the stream and sp_alpha / sp_pull of the handle, nothing of the
@@ -423,78 +308,23 @@ struct Tmp {   // stream-ordered temporaries of one call, and its pinned host wo
 int shortest_paths(lpa_graph* g, const int32_t* landmarks, int32_t n_landmarks, int32_t* dist_out,
                    int32_t out_is_device, lpa_sp_summary* summary) {
   hipStream_t s = g->stream;
-  const int64_t V = g->V, m = g->m;
+  const int64_t V = g->V;
   const int64_t batches = ((int64_t)n_landmarks + 63) / 64;
   if (summary) *summary = lpa_sp_summary{0, 0, -1, batches, 0, 0};
   if (V == 0 || (n_landmarks == 0 && !summary)) return LPA_OK;
   Tmp tmp(s);
   // ---- build ----
-  u64* keys = nullptr;   // [2 m]: the keys and the sort's other buffer
-  uint8_t* flag = nullptr;
-  u32* pos = nullptr;
-  int64_t *oo = nullptr, *io = nullptr;
-  int32_t *ocol = nullptr, *icol = nullptr;
-  LPA_TRY(tmp.get(&oo, V + 1));
-  LPA_TRY(tmp.get(&io, V + 1));
-  int64_t E = 0;
-  const int bits = bits_for((uint64_t)V);   // the halves hold values up to V (a dropped edge)
-  int both[8], hi[4], ns = 0;
-  for (int b = 0; b < bits; b += 8, ++ns) hi[ns] = 32 + b;
-  for (int i = 0; i < ns; ++i) {
-    both[i] = 8 * i;
-    both[ns + i] = 32 + 8 * i;
-  }
-  if (m > 0) {
-    LPA_TRY(tmp.get(&keys, 2 * m));
-    LPA_TRY(tmp.get(&flag, m));
-    LPA_TRY(tmp.get(&pos, m + 1));
-    hipLaunchKernelGGL(k_sp_keys, dim3(grid_for(m)), dim3(256), 0, s, g->e_src, g->e_dst, m, (u32)V, keys);
-    LPA_HIP(hipGetLastError());
-    LPA_TRY(radix_sort_u64(keys, keys + m, m, both, 2 * ns, s));
-    hipLaunchKernelGGL(k_sp_uniq, dim3(grid_for(m)), dim3(256), 0, s, keys, m, (u32)V, flag);
-    LPA_HIP(hipGetLastError());
-    LPA_TRY(exclusive_scan_u8_u32(flag, pos, m, s));
-    u32 hE = 0;
-    LPA_HIP(hipMemcpyAsync(&hE, pos + m, sizeof(u32), hipMemcpyDeviceToHost, s));
-    LPA_HIP(hipStreamSynchronize(s));
-    E = (int64_t)hE;
-  }
-  if (summary) summary->arcs = E;
+  ArcLists arcs;
+  LPA_TRY(arcs_count(g, tmp, nullptr, &arcs));
+  if (summary) summary->arcs = arcs.E;
   if (n_landmarks == 0) return LPA_OK;
-  LPA_TRY(tmp.get(&ocol, E));
-  LPA_TRY(tmp.get(&icol, E));
-  if (E > 0) {
-    u64* okeys = keys + m;   // the arcs in (src, dst) order; then the second sort's other buffer
-    hipLaunchKernelGGL(k_sp_compact, dim3(grid_for(m)), dim3(256), 0, s, keys, flag, pos, m, okeys);
-    hipLaunchKernelGGL(k_sp_split, dim3(grid_for(E)), dim3(256), 0, s, okeys, E, ocol, keys);
-    hipLaunchKernelGGL(k_sp_bounds, dim3(grid_for(V + 1)), dim3(256), 0, s, okeys, E, V, oo);
-    LPA_HIP(hipGetLastError());
-    LPA_TRY(radix_sort_u64(keys, okeys, E, hi, ns, s));
-    hipLaunchKernelGGL(k_sp_bounds, dim3(grid_for(V + 1)), dim3(256), 0, s, keys, E, V, io);
-    hipLaunchKernelGGL(k_sp_col, dim3(grid_for(E)), dim3(256), 0, s, keys, E, icol);
-    LPA_HIP(hipGetLastError());
-  } else {
-    LPA_HIP(hipMemsetAsync(oo, 0, sizeof(int64_t) * (size_t)(V + 1), s));
-    LPA_HIP(hipMemsetAsync(io, 0, sizeof(int64_t) * (size_t)(V + 1), s));
-  }
-  // the pull's static lists
-  uint8_t *fw = nullptr, *fb = nullptr;
-  u32 *pw = nullptr, *pb = nullptr;
+  LPA_TRY(arcs_lists(g, tmp, &arcs));
+  const int64_t *oo = arcs.oo, *io = arcs.io;
+  const int32_t *ocol = arcs.ocol, *icol = arcs.icol;
+  // the pull's static lists, by out-degree
   int32_t* plists = nullptr;
-  LPA_TRY(tmp.get(&fw, V));
-  LPA_TRY(tmp.get(&fb, V));
-  LPA_TRY(tmp.get(&pw, V + 1));
-  LPA_TRY(tmp.get(&pb, V + 1));
-  LPA_TRY(tmp.get(&plists, 2 * V));
-  hipLaunchKernelGGL(k_sp_forms, dim3(grid_for(V)), dim3(256), 0, s, oo, V, fw, fb);
-  LPA_HIP(hipGetLastError());
-  LPA_TRY(exclusive_scan_u8_u32(fw, pw, V, s));
-  LPA_TRY(exclusive_scan_u8_u32(fb, pb, V, s));
-  hipLaunchKernelGGL(k_sp_form_lists, dim3(grid_for(V)), dim3(256), 0, s, fw, fb, pw, pb, V, plists);
-  LPA_HIP(hipGetLastError());
-  u32 hp[2] = {0, 0};   // the pull's wave rows and block rows
-  LPA_HIP(hipMemcpyAsync(&hp[0], pw + V, sizeof(u32), hipMemcpyDeviceToHost, s));
-  LPA_HIP(hipMemcpyAsync(&hp[1], pb + V, sizeof(u32), hipMemcpyDeviceToHost, s));
+  u32 hp[2] = {0, 0};   // the pull's wave rows and block rows (read after the synchronisation below)
+  LPA_TRY(form_lists(tmp, oo, V, kSpShort, kSpWave, &plists, hp));
   // ---- state ----
   ull *seen = nullptr, *front = nullptr, *next = nullptr, *cnt = nullptr;
   int32_t *flists = nullptr, *lm = nullptr, *dbuf = nullptr;
@@ -505,10 +335,11 @@ int shortest_paths(lpa_graph* g, const int32_t* landmarks, int32_t n_landmarks, 
   LPA_TRY(tmp.get(&flists, 3 * V));
   LPA_TRY(tmp.get(&lm, n_landmarks));
   if (!out_is_device) LPA_TRY(tmp.get(&dbuf, (n_landmarks < 64 ? (int64_t)n_landmarks : 64) * V));
-  LPA_HIP(hipHostMalloc((void**)&tmp.pinned, sizeof(ull) * C_READ, hipHostMallocDefault));
+  ull* pinned = nullptr;
+  LPA_TRY(tmp.pin(&pinned, C_READ));
   LPA_HIP(hipMemcpyAsync(lm, landmarks, sizeof(int32_t) * (size_t)n_landmarks, hipMemcpyHostToDevice, s));
   LPA_HIP(hipStreamSynchronize(s));
-  const volatile ull* hc = tmp.pinned;
+  const volatile ull* hc = pinned;
   const int64_t tiles = (V + 63) >> 6;
   const unsigned g_tiles = grid_rows(tiles, 4, 8192);
   const unsigned g_short = grid_rows(V, 256 / kShortLanes, 65536);
@@ -528,7 +359,7 @@ int shortest_paths(lpa_graph* g, const int32_t* landmarks, int32_t n_landmarks, 
       hipLaunchKernelGGL(k_sp_settle, dim3(g_tiles), dim3(256), 0, s, seen, front, next, oo, io, V, active, level, dist,
                          cnt);
       LPA_HIP(hipGetLastError());
-      LPA_HIP(hipMemcpyAsync(tmp.pinned, cnt, sizeof(ull) * C_READ, hipMemcpyDeviceToHost, s));
+      LPA_HIP(hipMemcpyAsync(pinned, cnt, sizeof(ull) * C_READ, hipMemcpyDeviceToHost, s));
       LPA_HIP(hipStreamSynchronize(s));
       const int64_t nf = (int64_t)hc[C_FRONT], in_arcs = (int64_t)hc[C_IN_ARCS], out_arcs = (int64_t)hc[C_OUT_ARCS];
       const int64_t rows[3] = {(int64_t)hc[C_SHORT], (int64_t)hc[C_WAVE], (int64_t)hc[C_BLOCK]};

@@ -3,7 +3,8 @@
 // direction, duplicates collapsed) that contain v.
 //
 //   keys     (min << 32 | max) of every edge, radix-sorted; the first key of each run with
-//            min != max is a simple edge: marked, scanned, compacted           (E of them)
+//            min != max is a simple edge: marked, scanned (lpa_adj.hip: simple_edges),
+//            compacted                                                         (E of them)
 //   degrees  d[v] of the simple graph: the min side by runs of the sorted keys (one atomic
 //            per run and wave), the max side one atomic per edge
 //   orient   every simple edge {a, b} points from the endpoint of lower rank (d, id) to
@@ -37,47 +38,11 @@
 // same bits); the apex's share is summed in registers and across the team, one atomic
 // per row.  Every offset and count is 64-bit; a vertex id is 32-bit.
 #include "lpa_device.h"
+#include "lpa_algo.h"
 
 namespace lpa {
 
 namespace {
-
-inline unsigned grid_for(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > 65536) b = 65536;
-  return (unsigned)b;
-}
-// block-aggregated passes: few blocks, each over a long stretch of the input
-inline unsigned grid_bh(int64_t n) {
-  const unsigned g = grid_for(n);
-  return g < 2048u ? g : 2048u;
-}
-
-#define GRID_STRIDE(i, n) \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-// the whole block runs every trip (ballots, shuffles and barriers inside)
-#define BLOCK_STRIDE(b, n) \
-  for (int64_t b = (int64_t)blockIdx.x * blockDim.x; b < (n); b += (int64_t)gridDim.x * blockDim.x)
-
-typedef unsigned long long ull;
-
-// an id outside [0, V) (the build trusts its input as well) makes the edge a loop: dropped
-__global__ __launch_bounds__(256) void k_tc_keys(const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
-                                                 int64_t m, u32 V, u64* __restrict__ keys) {
-  GRID_STRIDE(i, m) {
-    const u32 a = (u32)__builtin_nontemporal_load(src + i), b = (u32)__builtin_nontemporal_load(dst + i);
-    const u32 lo = a < b ? a : b, hi = a < b ? b : a;
-    keys[i] = hi < V ? ((u64)lo << 32) | hi : 0ull;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_tc_mark(const u64* __restrict__ keys, int64_t m, int32_t* __restrict__ first) {
-  GRID_STRIDE(i, m) {
-    const u64 k = keys[i];
-    first[i] = ((u32)(k >> 32) != (u32)k && (i == 0 || keys[i - 1] != k)) ? 1 : 0;
-  }
-}
 
 __global__ __launch_bounds__(256) void k_tc_compact(const u64* __restrict__ keys, const int32_t* __restrict__ first,
                                                     const int64_t* __restrict__ pos, int64_t m, u64* __restrict__ out) {
@@ -119,10 +84,6 @@ __global__ __launch_bounds__(256) void k_tc_orient(u64* __restrict__ ek, int64_t
     ek[i] = ((u64)from << 32) | to;
     atomicAdd(&od[from], 1);
   }
-}
-
-__global__ __launch_bounds__(256) void k_tc_col(const u64* __restrict__ ok, int64_t E, int32_t* __restrict__ col) {
-  GRID_STRIDE(i, E) col[i] = (int32_t)(u32)ok[i];
 }
 
 // Row lists of the four count forms (list k at lists + k * V, in no particular order:
@@ -366,35 +327,6 @@ __global__ __launch_bounds__(256) void k_tc_argmax(const ull* __restrict__ count
   }
 }
 
-struct Tmp {   // stream-ordered temporaries of one call
-  hipStream_t s;
-  void* ptrs[16];
-  int n = 0;
-  explicit Tmp(hipStream_t st) : s(st) {}
-  template <typename T>
-  int get(T** p, int64_t count) {
-    LPA_TRY(tmp_alloc((void**)p, sizeof(T) * (size_t)(count > 0 ? count : 1), s));
-    ptrs[n++] = *p;
-    return LPA_OK;
-  }
-  ~Tmp() {
-    for (int i = 0; i < n; ++i) tmp_free(ptrs[i], s);
-  }
-};
-
-int sort_pairs(u64* keys, u64* tmp, int64_t n, int bits, hipStream_t s) {
-  int shifts[8], ns = 0;
-  for (int b = 0; b < bits; b += 8) shifts[ns++] = b;
-  for (int b = 0; b < bits; b += 8) shifts[ns++] = 32 + b;
-  return radix_sort_u64(keys, tmp, n, shifts, ns, s);
-}
-
-inline unsigned grid_rows(int64_t nrows, int per_block) {
-  int64_t b = (nrows + per_block - 1) / per_block;
-  if (b > 16384) b = 16384;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
 template <int T, bool kLds>
 int launch_team(const int32_t* rows, int64_t nrows, const int64_t* rp, const int32_t* col, ull* count, int32_t cap,
                 hipStream_t s) {
@@ -404,8 +336,8 @@ int launch_team(const int32_t* rows, int64_t nrows, const int64_t* rp, const int
     set_error("triangle_count: %zu bytes of LDS per block", bytes);
     return LPA_EINVAL;
   }
-  hipLaunchKernelGGL((k_tc_team<T, kLds>), dim3(grid_rows(nrows, 256 / T)), dim3(256), bytes, s, rows, nrows, rp, col,
-                     count, cap);
+  hipLaunchKernelGGL((k_tc_team<T, kLds>), dim3(grid_rows(nrows, 256 / T, 16384)), dim3(256), bytes, s, rows, nrows, rp,
+                     col, count, cap);
   LPA_HIP(hipGetLastError());
   return LPA_OK;
 }
@@ -427,30 +359,15 @@ int triangle_count(lpa_graph* g, int64_t* count_out, int64_t* simple_degree_out,
   LPA_TRY(tmp.get(&d, V));
   LPA_HIP(hipMemsetAsync(count, 0, sizeof(ull) * (size_t)V, s));
   LPA_HIP(hipMemsetAsync(d, 0, sizeof(int32_t) * (size_t)V, s));
-  const int bits = bits_for((uint64_t)(V - 1));
-  int64_t E = 0;
-  u64* keys = nullptr;   // [2 m]: the sorted edge keys, then [m, m + E) the simple edges
-  if (m > 0) {
-    int32_t* first = nullptr;
-    int64_t* pos = nullptr;
-    LPA_TRY(tmp.get(&keys, 2 * m));
-    LPA_TRY(tmp.get(&first, m));
-    LPA_TRY(tmp.get(&pos, m + 1));
-    hipLaunchKernelGGL(k_tc_keys, dim3(grid_for(m)), dim3(256), 0, s, g->e_src, g->e_dst, m, (u32)V, keys);
-    LPA_HIP(hipGetLastError());
-    LPA_TRY(sort_pairs(keys, keys + m, m, bits, s));
-    hipLaunchKernelGGL(k_tc_mark, dim3(grid_for(m)), dim3(256), 0, s, keys, m, first);
-    LPA_HIP(hipGetLastError());
-    LPA_TRY(exclusive_scan_i32_i64(first, pos, m, s));
-    LPA_HIP(hipMemcpyAsync(&E, pos + m, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    LPA_HIP(hipStreamSynchronize(s));
-    if (E > 0) {
-      hipLaunchKernelGGL(k_tc_compact, dim3(grid_for(m)), dim3(256), 0, s, keys, first, pos, m, keys + m);
-      LPA_HIP(hipGetLastError());
-    }
-  }
+  SimpleEdges se;
+  LPA_TRY(simple_edges(g, tmp, &se));
+  const int64_t E = se.E;
+  u64* keys = se.keys;   // [2 m]: the sorted edge keys, then [m, m + E) the simple edges
   if (E > 0) {
+    const HalfShifts sh(bits_for((uint64_t)(V - 1)));
     u64* ek = keys + m;
+    hipLaunchKernelGGL(k_tc_compact, dim3(grid_for(m)), dim3(256), 0, s, keys, se.first, se.pos, m, ek);
+    LPA_HIP(hipGetLastError());
     int32_t *od = nullptr, *col = nullptr, *lists = nullptr;
     int64_t* rp = nullptr;
     u32* cnt = nullptr;
@@ -464,9 +381,8 @@ int triangle_count(lpa_graph* g, int64_t* count_out, int64_t* simple_degree_out,
     hipLaunchKernelGGL(k_tc_degrees, dim3(grid_for(E)), dim3(256), 0, s, ek, E, d);
     hipLaunchKernelGGL(k_tc_orient, dim3(grid_for(E)), dim3(256), 0, s, ek, E, d, od);
     LPA_HIP(hipGetLastError());
-    LPA_TRY(sort_pairs(ek, keys, E, bits, s));
-    hipLaunchKernelGGL(k_tc_col, dim3(grid_for(E)), dim3(256), 0, s, ek, E, col);
-    LPA_HIP(hipGetLastError());
+    LPA_TRY(radix_sort_u64(ek, keys, E, sh.both(), 2 * sh.ns, s));
+    LPA_TRY(key_col(ek, E, col, s));
     LPA_TRY(exclusive_scan_i32_i64(od, rp, V, s));
     hipLaunchKernelGGL(k_tc_classify, dim3(grid_bh(V)), dim3(256), 0, s, od, V, g->tc_short, g->tc_wave, g->tc_lds,
                        lists, cnt);
@@ -476,8 +392,8 @@ int triangle_count(lpa_graph* g, int64_t* count_out, int64_t* simple_degree_out,
     LPA_HIP(hipStreamSynchronize(s));
     const int32_t lmax = (int32_t)h[4];
     if (h[0]) {
-      hipLaunchKernelGGL(k_tc_group<8>, dim3(grid_rows(h[0], 32)), dim3(256), 0, s, lists, (int64_t)h[0], rp, col,
-                         count);
+      hipLaunchKernelGGL(k_tc_group<8>, dim3(grid_rows(h[0], 32, 16384)), dim3(256), 0, s, lists, (int64_t)h[0], rp,
+                         col, count);
       LPA_HIP(hipGetLastError());
     }
     LPA_TRY((launch_team<64, true>(lists + V, h[1], rp, col, count, lmax < g->tc_wave ? lmax : g->tc_wave, s)));
