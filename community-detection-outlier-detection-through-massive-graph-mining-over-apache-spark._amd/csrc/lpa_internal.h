@@ -539,6 +539,9 @@ int scratch_alloc(lpa_graph* g, void** p, size_t bytes);
 void scratch_free(lpa_graph* g, void* p);
 
 // primitives (lpa_prims.hip)
+// elements a block of the sort and the scans owns (256 threads x 16): the sizes at which their code changes
+// path; tools/microbench/prims_check.hip places its cases around multiples of it
+constexpr int kPrimTile = 4096;
 // LSD radix sort of u64 keys in place (tmp: same length); sorts digits at the
 // given bit shifts (8-bit digits), in order.  Result ends in `keys`.
 int radix_sort_u64(u64* keys, u64* tmp, int64_t n, const int* shifts, int nshifts,
@@ -549,7 +552,9 @@ int radix_sort_u64_kv(u64* keys, u64* vals, u64* tkeys, u64* tvals, int64_t n, c
 // exclusive scan of int32 input into int64 output (n + 1 entries: out[n] = total)
 int exclusive_scan_i32_i64(const int32_t* in, int64_t* out, int64_t n, hipStream_t s);
 int exclusive_scan_i64(const int64_t* in, int64_t* out, int64_t n, hipStream_t s);
-// exclusive scan of 0/1 bytes into uint32 positions (n + 1 entries; the total < 2^32)
+// exclusive scan of bytes into uint32 positions (n + 1 entries).  The callers pass 0/1 marks; a byte
+// of any value counts as that value (both forms, the 16-B one and the generic one that misaligned
+// pointers take), as long as the total stays below 2^32
 int exclusive_scan_u8_u32(const uint8_t* in, uint32_t* out, int64_t n, hipStream_t s);
 int bits_for(uint64_t maxval);  // bits needed to represent maxval (0 -> 0)
 

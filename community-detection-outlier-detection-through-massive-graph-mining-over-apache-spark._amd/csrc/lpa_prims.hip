@@ -15,6 +15,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kItems = 16;
 constexpr int kTile = kThreads * kItems;  // keys per block per radix pass
+static_assert(kTile == kPrimTile, "lpa_internal.h names the tile for tools/microbench/prims_check.hip");
 
 // ---------------------------------------------------------------------------
 // block-level helpers (256 threads = 4 waves)

@@ -1,9 +1,15 @@
 """The shared edge-list builds (csrc/lpa_adj.hip) under every call that rests on them, at the
-vertex counts where bits_for(V) and bits_for(V - 1) part ways (V = 2^8 and 2^16 and their
+vertex counts where bits_for(V) and bits_for(V - 1) part ways (V = 2^8, 2^16 and 2^24 and their
 neighbours: one radix pass a half more for the directed-arc keys, which hold values up to V,
-than for the simple-edge keys, which hold ids).  One generated multigraph per V and one handle:
+than for the simple-edge keys, which hold ids).  One generated multigraph per case and one handle:
 every call against the numpy reference its own test file uses, the edge counts of the summaries
-against numpy counts of the same list, and a second call on the handle against the first."""
+against numpy counts of the same list, and a second call on the handle against the first.
+
+The multigraph of SIZES has 4024 edges: less than one tile of the sort and the scans (4096
+elements to a block, csrc/lpa_prims.hip), so one block, one scan level and one histogram column.
+EDGE_CASES run the same calls with the edge list at a tile's edge (4096 and 4097 edges) and over
+several tiles (12289 = 3 * 4096 + 1); tests/test_gpu_prims.py checks the primitives themselves
+there."""
 import numpy as np
 import pytest
 
@@ -16,33 +22,42 @@ import tc_ref
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [255, 256, 257, 65535, 65536, 65537]
+SIZES = [255, 256, 257, 65535, 65536, 65537, 2**24 - 1, 2**24, 2**24 + 1]
+BASE_EDGES = 4024
+EDGE_CASES = [(65536, 4096), (65536, 4097), (257, 12289)]   # (V, edges)
+CASES = [(v, BASE_EDGES) for v in SIZES] + EDGE_CASES
 PR_ITERS = 10
 
 
-def generate(V, seed=9):
-    """(s, d, isolated): about 4000 edges among at most 300 vertices spread over [0, V), with
-    edges at vertex 0 and at V - 1, both directions of some pairs, duplicates, self-loops (one
-    on V - 1) and a vertex without any edge."""
+def generate(V, seed=9, m=BASE_EDGES):
+    """(s, d, isolated): m edges, every appended extra counted (m >= 2024; 4024 is under one tile
+    of the build's sort), among at most 300 vertices spread over [0, V), with edges at vertex 0
+    and at V - 1, both directions of some pairs, duplicates, self-loops (one on V - 1) and a
+    vertex without any edge."""
     rng = np.random.default_rng(seed + V)
     isolated = V // 2
     others = np.setdiff1d(np.arange(1, V - 1), [isolated])
     pool = np.concatenate([[0, V - 1], rng.choice(others, size=min(V // 2, 300) - 2, replace=False)])
-    a = rng.choice(pool, size=3000)
-    b = rng.choice(pool, size=3000)
+    n = m - 1024   # the extras below: 500 reversed, 500 duplicates, 21 loops, 3 more
+    assert n >= 1000
+    a = rng.choice(pool, size=n)
+    b = rng.choice(pool, size=n)
     loops = np.concatenate([[V - 1], rng.choice(pool, size=20)])
     s = np.concatenate([a, b[:500], a[500:1000], loops, [0, V - 1, 0]])
     d = np.concatenate([b, a[:500], b[500:1000], loops, [V - 1, 0, pool[5]]])
+    assert s.size == m and d.size == m
     order = rng.permutation(s.size)
     return s[order].astype(np.int32), d[order].astype(np.int32), isolated
 
 
-@pytest.fixture(scope="module", params=SIZES, ids=[f"V{v}" for v in SIZES])
+@pytest.fixture(scope="module", params=CASES,
+                ids=[f"V{v}" if m == BASE_EDGES else f"V{v}-m{m}" for v, m in CASES])
 def case(request):
     import graphframes_amd
 
-    V = request.param
-    s, d, isolated = generate(V)
+    V, m = request.param
+    s, d, isolated = generate(V, m=m)
+    assert s.size == m
     touched = np.zeros(V, bool)
     touched[s] = True
     touched[d] = True
