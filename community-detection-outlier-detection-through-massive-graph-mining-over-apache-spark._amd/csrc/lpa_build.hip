@@ -653,6 +653,8 @@ int finish_build(lpa_graph* g, int32_t* deg_own, int64_t m) {
   LPA_TRY(dev_alloc(g, (void**)&g->gword, sizeof(int32_t) * kGwordLen));
   LPA_HIP(hipMemsetAsync(g->gword, 0, sizeof(int32_t) * kGwordLen, s));
   LPA_TRY(dev_alloc(g, (void**)&g->fill_part, sizeof(u64) * 2 * kFillBlocks));
+  if (g->nranks == 1)  // superstep 3's fill-scatter form (launch_refresh)
+    LPA_TRY(dev_alloc(g, (void**)&g->gbits_next, sizeof(uint32_t) * ((g->vpad + 63) / 64 * 2)));
   LPA_TRY(dev_alloc(g, (void**)&g->abits, sizeof(unsigned long long) * ((g->arcs + 63) / 64 + 1)));
   LPA_TRY(dev_alloc(g, (void**)&g->lab[0], sizeof(int32_t) * g->vpad));
   LPA_TRY(dev_alloc(g, (void**)&g->lab[1], sizeof(int32_t) * g->vpad));

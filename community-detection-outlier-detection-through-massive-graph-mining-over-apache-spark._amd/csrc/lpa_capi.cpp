@@ -140,7 +140,7 @@ void destroy(lpa_graph* g) {
                   g->items_cc, g->hub_uoff, g->ucnt, g->crow, g->rdirty[0], g->rdirty[1],
                   g->udirty[0], g->udirty[1], g->fr_all, g->flist, g->ulist, g->fcnt, g->first_best, g->rstart,
                   g->blk_pieces, g->gbits, g->ugc, g->umx, g->ulist2, g->gdec, g->gword, g->al0, g->abits,
-                  g->glist, g->code2, g->al2};
+                  g->glist, g->code2, g->al2, g->fill_part, g->gbits_next};
   for (void* p : bufs) dev_free(g, p);
   if (!g->borrowed) {   // a borrowing L2 sub-graph uses its parent's pinned words
     if (g->h_flag) (void)hipHostFree(g->h_flag);
@@ -239,6 +239,7 @@ int create_common(int32_t device, hipStream_t stream, const int32_t* src, const 
   if (const char* f = getenv("LPA_KEEP_BITS")) g->keep_bits = atoi(f) ? 1 : 0;
   if (const char* f = getenv("LPA_SPARSE_AL")) g->sparse_al = atoi(f) ? 1 : 0;
   if (const char* f = getenv("LPA_FILL_SCATTER")) g->fill_scatter = atoi(f) < 0 ? 0 : atoi(f) > 2 ? 2 : atoi(f);
+  if (const char* f = getenv("LPA_FILL_STEP3")) g->fill_step3 = atoi(f) < 0 ? 0 : atoi(f) > 2 ? 2 : atoi(f);
   if (const char* f = getenv("LPA_TC_SHORT")) g->tc_short = atoi(f) < 0 ? 0 : atoi(f);
   if (const char* f = getenv("LPA_TC_WAVE")) g->tc_wave = atoi(f) < 0 ? 0 : atoi(f) > kTcWaveMax ? kTcWaveMax : atoi(f);
   if (const char* f = getenv("LPA_TC_LDS")) g->tc_lds = atoi(f) < 0 ? 0 : atoi(f) > kTcLdsMax ? kTcLdsMax : atoi(f);

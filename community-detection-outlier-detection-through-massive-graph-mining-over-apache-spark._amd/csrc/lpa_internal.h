@@ -76,6 +76,11 @@ constexpr double kFrontierFrac = 0.005;
 constexpr double kFillFrac = 0.0154;
 constexpr int kFillCap = 4096;
 constexpr int kFillCapShift = 15;
+// the same form in superstep 3's refresh, in place of k_al_scatter (lpa_refresh.hip, LPA_FILL_STEP3):
+// taken while the arcs of the columns off the giant label are at most this fraction of the
+// superstep's dirty arcs (half the break-even ratio at C3), the same cap
+// holds, and more than kFrontierFrac of the arcs are dirty
+constexpr double kFill3Ratio = 0.16;
 // superstep 1's column-run tiles (lpa_iter.hip k_first_runs): arcs per wave tile, 16 per
 // lane; the row-start bitmap holds whole tiles plus the next tile's first word
 constexpr int kRunTile = 1024;
@@ -224,6 +229,13 @@ enum GwordSlot {
                       //   and cleared wherever GW_AL_SPARSE is): the stream rebuilds stand down
   GW_FILL_CNT = 16,   // refreshes that took that form since the build or the last reset
   GW_FILL_TICKET = 17, // k_fill_decide's last-block ticket (zeroed by k_giant_pick)
+  // superstep 3's fill-scatter form (launch_refresh; all five written by k_giant_pick3 ahead of
+  // their readers in the same refresh, read by no other superstep)
+  GW_G3 = 18,         // the giant label of superstep 3's new vector
+  GW_TRY3 = 19,       // the form is worth counting (k_giant_pick3's gate)
+  GW_HOT3 = 20,       // hot-slot giant-bit count of that vector (GW_HOT_BITS keeps the old one's)
+  GW_FILL3 = 21,      // the form is taken (k_fill_decide's step-3 instance)
+  GW_FILL3_TICKET = 22, // ... and its last-block ticket
 };
 constexpr int kGwordLen = 24;
 // blocks of k_fill_decide at most: each leaves one partial (sum, longest) in lpa_graph::fill_part
@@ -289,6 +301,8 @@ struct lpa_graph {
   int sparse_al = 1;      // LPA_SPARSE_AL=0: a bits-mode rebuild also stores the giant label (dense al[])
   int fill_scatter = 1;   // LPA_FILL_SCATTER: the sparse bits-mode rebuild by fill and scatter (0: never,
                           // 1: the device decision, 2: whenever that rebuild runs -- tests)
+  int fill_step3 = 1;     // LPA_FILL_STEP3: superstep 3's refresh by fill and scatter (0: never, 1: the
+                          // device decision, 2: whenever its new vector is in bits mode -- tests)
   int conv_streams = 2;   // LPA_CONV_STREAMS: streams of a converged superstep's tally (1-3)
   int64_t vpad = 0;       // nranks * slice
   int64_t own_begin = 0;  // rank * slice
@@ -385,6 +399,8 @@ struct lpa_graph {
   int32_t* gword = nullptr;     // [kGwordLen] G of the last refreshed vector and the decisions of
                                 //     supersteps 2-4 that hang on it (GwordSlot)
   lpa::u64* fill_part = nullptr; // [2 kFillBlocks] k_fill_decide's per-block (sum, longest)
+  uint32_t* gbits_next = nullptr; // [vpad / 32] superstep 3's fill-scatter form: the bitmap of its new
+                                  // vector, copied over gbits only once the form is taken
   // giant codes (round 5, lpa_codes.h "Giant codes"): the refresh after superstep 1 (or
   // 2), when one label G carries the hubs but not half the hot slots (R-MAT), writes a
   // 2-bit code per arc instead of al[] (code 0 = G, else 1 + a label hash mod 3; 16 arcs

@@ -271,6 +271,27 @@ __device__ __forceinline__ void rebuild_all(const int32_t* __restrict__ col, int
   }
 }
 
+// (defined with the fill-scatter form below)
+__device__ __forceinline__ void sparse_mark(int32_t* __restrict__ gword, bool sparse, int32_t G);
+__device__ __forceinline__ void fill_arc_bits(unsigned long long* __restrict__ abits, int32_t* __restrict__ al,
+                                              int64_t arcs, int32_t G, int64_t nslots, int64_t tid, int64_t nth);
+
+// fill3 (host-set in superstep 3's refresh alone, fill_step3_now; every other launch passes 0
+// and does not read the word): gword[GW_FILL3] says that k_fill_decide's step-3 instance took the
+// fill-scatter form.  This kernel then scatters nothing.  It does its housekeeping (the next
+// counters, the chunk flags, *fr_all_next = 1), sets every arc bit, copies gbits_next over
+// gbits and does the form's bookkeeping; k_fill_scatter follows in a launch of its own and
+// writes the columns off the new G.  Four things hold this together:
+//  - The fallback needs the OLD gbits: left_g below reads the bitmap of the vector the sparse
+//    rebuild saw, so nothing writes gbits before this kernel has read gword[GW_FILL3], and the copy
+//    happens only under it.
+//  - The fill may not precede the decision (k_fill_decide's note): it is here, under the word.
+//  - No block of one launch may clear a bit that another block of the same launch may still
+//    fill: a taken form clears no bit in this launch at all, k_fill_scatter is the next one.
+//  - A taken form writes no frontier mark and syncs no label into Lold.  That is valid only
+//    because the next superstep writes every row: *fr_all_next = 1 here, and the host forces it
+//    as well (settle3_now -> force_all_next, lpa_iter.hip run_supersteps).
+// -DLPA_SPARSE_POISON: the fill poisons every al[] entry, as k_fill_decide's does.
 __global__ __launch_bounds__(256) void k_al_scatter(const int32_t* __restrict__ chlist,
                                                     const uint4* __restrict__ chflag16, int64_t ngroups,
                                                     const int32_t* __restrict__ cowner,
@@ -286,10 +307,41 @@ __global__ __launch_bounds__(256) void k_al_scatter(const int32_t* __restrict__ 
                                                     int32_t* __restrict__ Lold,
                                                     const int32_t* __restrict__ col_fold, int64_t arcs,
                                                     int32_t* __restrict__ gword, int keep_bits,
-                                                    const uint32_t* __restrict__ gbits,
-                                                    unsigned long long* __restrict__ abits) {
+                                                    uint32_t* __restrict__ gbits,
+                                                    unsigned long long* __restrict__ abits, int fill3 = 0,
+                                                    const uint32_t* __restrict__ gbits_next = nullptr,
+                                                    int64_t nslots = 0) {
   // the next superstep's counters (the other parity; no memset launch)
   if (blockIdx.x == 0 && threadIdx.x < 3) counters_next[threadIdx.x] = 0ull;
+  // (uniform: no block of this launch writes gword[GW_FILL3])
+  if (fill3 != 0 && gword[GW_FILL3] != 0) {
+    const int32_t G = gword[GW_G3];
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t nth = (int64_t)gridDim.x * blockDim.x;
+    if (tid == 0) {
+      *fr_all_next = 1;
+      // the sparse rebuild's bookkeeping, as k_fill_decide's after superstep 2; gword[GW_G] too, so that
+      // the k_giant_pick that follows (the same pick) sees no new G and keeps gword[GW_ABITS_OK]
+      gword[GW_G] = G;
+      sparse_mark(gword, true, G);
+      gword[GW_ABITS_OK] = 1;
+      gword[GW_FILL_CNT] += 1;
+    }
+    fill_arc_bits(abits, al, arcs, G, nslots, tid, nth);
+    // gbits = the bitmap of the vector this sparse refresh saw (nslots is a multiple of 64)
+    {
+      const unsigned long long* __restrict__ src = reinterpret_cast<const unsigned long long*>(gbits_next);
+      unsigned long long* __restrict__ dst = reinterpret_cast<unsigned long long*>(gbits);
+      for (int64_t i = tid; i < (nslots >> 6); i += nth) dst[i] = src[i];
+    }
+    // the changed columns' chunk flags (k_diff set them; the list needs no clearing)
+    uint4* __restrict__ fl = const_cast<uint4*>(chflag16);
+    for (int64_t gi = tid; gi < ngroups; gi += nth) {
+      const uint4 f = chflag16[gi];
+      if ((f.x | f.y | f.z | f.w) != 0u) fl[gi] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    return;
+  }
   const bool rebuild = rebuild_wanted(counters, thr);
   // al changes here (scatter, or the plain folded rebuild), so the arc giant bits go
   // stale: gword[GW_ABITS_OK] = 0 -- except in superstep 3's scatter (keep_bits, host-set), right
@@ -448,24 +500,31 @@ constexpr int kHotLabelsSingle = 40960;    // P = 1: the whole 160 KB of LDS
 // bits mode: 1,310,688 slots' bits (the last LDS word counts the set bits first)
 constexpr int64_t kHotBits = 32ll * (kHotLabelsSingle - 1);
 constexpr int kPickK = 1024;
-__global__ __launch_bounds__(1024) void k_giant_pick(const int32_t* __restrict__ L, int64_t n_real, int64_t S,
-                                                     int P, int32_t* __restrict__ gword) {
+// -> thread 0: the best table word (count << 32 | ~label) of the n = min(n_real, kPickK) top slots
+__device__ __forceinline__ u64 giant_pick_best(const int32_t* __restrict__ L, int64_t n, int64_t S, int P) {
   __shared__ u64 tab[2 * kPickK];
   __shared__ u64 wbest[kPickK / 64];
   const int t = threadIdx.x;
   tab[t] = 0ull;
   tab[t + kPickK] = 0ull;
   __syncthreads();
-  const int64_t n = n_real < kPickK ? n_real : kPickK;
   if (t < n) lds_insert(tab, 32 - 11, 2 * kPickK - 1, (u32)L[(int64_t)(t % P) * S + t / P], 1u);
   __syncthreads();
   const u64 b = wave_max_u64(umax64(tab[t], tab[t + kPickK]));
   if ((t & 63) == 0) wbest[t >> 6] = b;
   __syncthreads();
+  u64 m = 0ull;
   if (t == 0) {
-    u64 m = 0ull;
 #pragma unroll
     for (int k = 0; k < kPickK / 64; ++k) m = umax64(m, wbest[k]);
+  }
+  return m;
+}
+__global__ __launch_bounds__(1024) void k_giant_pick(const int32_t* __restrict__ L, int64_t n_real, int64_t S,
+                                                     int P, int32_t* __restrict__ gword) {
+  const int64_t n = n_real < kPickK ? n_real : kPickK;
+  const u64 m = giant_pick_best(L, n, S, P);
+  if (threadIdx.x == 0) {
     const int32_t G = (int32_t)(~(u32)m);
     if (G != gword[GW_G]) gword[GW_ABITS_OK] = 0;  // the arc giant bits are relative to the old G
     gword[GW_G] = G;
@@ -479,12 +538,38 @@ __global__ __launch_bounds__(1024) void k_giant_pick(const int32_t* __restrict__
   }
 }
 
+// Superstep 3's fill-scatter form (launch_refresh): the same pick on the NEW vector, ahead of
+// the scatter, into words of its own -- gword[GW_G], gword[GW_TRY] and gword[GW_FILL] keep the old vector's
+// values until k_al_scatter has run, whose fallback reads them (k_giant_pick follows it as in
+// every refresh and finds the same G).  gword[GW_TRY3], the gate of the two counting kernels
+// below: no rebuild is wanted (the rebuild would redo the refresh anyway) and, for the device
+// decision (mode 1), superstep 2's refresh took the form (gword[GW_FILL] still set: no pick ran
+// since) and the new G is worth trying; other graphs then pay three empty launches and no
+// pass over the label vector.
+__global__ __launch_bounds__(1024) void k_giant_pick3(const unsigned long long* __restrict__ counters, int64_t thr,
+                                                      const int32_t* __restrict__ L, int64_t n_real,
+                                                      int32_t* __restrict__ gword, int mode) {
+  const int64_t n = n_real < kPickK ? n_real : kPickK;
+  const u64 m = giant_pick_best(L, n, 0, 1);
+  if (threadIdx.x == 0) {
+    const bool try3 = n > 0 && 5 * (int64_t)(m >> 32) >= n;
+    gword[GW_G3] = (int32_t)(~(u32)m);
+    gword[GW_HOT3] = 0;
+    gword[GW_FILL3] = 0;
+    gword[GW_FILL3_TICKET] = 0;
+    gword[GW_TRY3] = !rebuild_wanted(counters, thr) && (mode == 2 || (gword[GW_FILL] != 0 && try3)) ? 1 : 0;
+  }
+}
+
 // (abits / nzero: the class-blocked rebuild that follows ORs the arc giant bits of its
 // pieces into abits[0, nzero): zeroed here, one launch ahead)
 // gword[GW_HOT_BITS] counts the set bits of the hot slots, slot i with (i & hmask) < hlim: the first
 // kHotBits slots at P = 1 (hmask all ones), the first hlim slots of every slice of a
 // rank-strided vector (hmask = slice - 1) -- the degree-ranked top set either way
-template <bool kIfWanted>
+// kStep3 (superstep 3's fill-scatter form, launch_refresh): the bitmap of the NEW vector into
+// `bits` = gbits_next, relative to gword[GW_G3], its hot-bit count into gword[GW_HOT3]; gword's sparse / fill words
+// and gbits stay as they are (k_al_scatter's fallback reads them) and nothing is zeroed
+template <bool kIfWanted, bool kStep3 = false>
 __global__ __launch_bounds__(256) void k_giant_bits(const unsigned long long* __restrict__ counters, int64_t thr,
                                                     const int32_t* __restrict__ L, int64_t n,
                                                     int32_t* __restrict__ gword,
@@ -492,20 +577,22 @@ __global__ __launch_bounds__(256) void k_giant_bits(const unsigned long long* __
                                                     unsigned long long* __restrict__ abits, int64_t nzero,
                                                     uint64_t hmask, int64_t hlim) {
   if (kIfWanted && !rebuild_wanted(counters, thr)) return;
+  if (kStep3 && gword[GW_TRY3] == 0) return;  // uniform (k_giant_pick3)
   // the hot-bit count: summed per block in LDS, one global atomic per block (a returning
   // atomic per wave on the one word serialised: ~2,500 of them, ~30 us at C3)
   __shared__ u32 bcnt;
   if (threadIdx.x == 0) bcnt = 0u;
   // a full rebuild follows (the LDS hot-set, small or code form): al[] is dense again unless
   // that rebuild takes the bits mode of one GPU and sets the word itself
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
+  if (!kStep3 && blockIdx.x == 0 && threadIdx.x == 0) {
     gword[GW_AL_SPARSE] = 0;
     gword[GW_FILL] = 0;
   }
   __syncthreads();
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nzero; i += (int64_t)gridDim.x * blockDim.x)
-    abits[i] = 0ull;
-  const int32_t G = gword[GW_G];
+  if (!kStep3)
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nzero; i += (int64_t)gridDim.x * blockDim.x)
+      abits[i] = 0ull;
+  const int32_t G = gword[kStep3 ? GW_G3 : GW_G];
   const int lane = threadIdx.x & 63;
   const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
   for (int64_t g0 = (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * 512; g0 < n; g0 += nw * 512) {
@@ -536,7 +623,7 @@ __global__ __launch_bounds__(256) void k_giant_bits(const unsigned long long* __
     }
   }
   __syncthreads();
-  if (threadIdx.x == 0 && bcnt) atomicAdd(&gword[GW_HOT_BITS], (int32_t)bcnt);
+  if (threadIdx.x == 0 && bcnt) atomicAdd(&gword[kStep3 ? GW_HOT3 : GW_HOT_BITS], (int32_t)bcnt);
 }
 
 // al[i] = lab(col[i]) over every arc by the calling grid (one wave per 512-arc batch,
@@ -1054,25 +1141,20 @@ __global__ __launch_bounds__(256) void k_al_rebuild_small(const unsigned long lo
 //     bookkeeping: gword[GW_FILL], sparse_mark, gword[GW_ABITS_OK], gword[GW_FILL_CNT].
 // -DLPA_SPARSE_POISON: every al[] entry is poisoned first (the stream, if it runs after all,
 // rewrites every entry in that build).
-template <bool kIfWanted>
-__global__ __launch_bounds__(1024) void k_fill_decide(const unsigned long long* __restrict__ counters, int64_t thr,
-                                                     const unsigned long long* __restrict__ gbits64, int64_t n_iso,
-                                                     const int64_t* __restrict__ cptr, int64_t arcs, int64_t nhb,
-                                                     int64_t nslots, int32_t* __restrict__ gword,
-                                                     unsigned long long* __restrict__ abits,
-                                                     int32_t* __restrict__ al, int mode, int64_t frac_arcs,
-                                                     int64_t cap, unsigned long long* __restrict__ part) {
-  if (kIfWanted && !rebuild_wanted(counters, thr)) return;
-  if (!(nhb > 0 && 2 * (int64_t)gword[GW_HOT_BITS] >= nhb)) return;  // not the bits mode (uniform)
-  const int32_t G = gword[GW_G];
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t nth = (int64_t)gridDim.x * blockDim.x;
+// Every arc bit of [0, arcs) set (the last word's tail stays clear, as the stream leaves it) by
+// the calling grid, thread tid of nth.  -DLPA_SPARSE_POISON: every al[] entry poisoned too.
+__device__ __forceinline__ void fill_arc_bits(unsigned long long* __restrict__ abits, int32_t* __restrict__ al,
+                                              int64_t arcs, int32_t G, int64_t nslots, int64_t tid, int64_t nth) {
   const int64_t nfw = arcs >> 6;
   {  // 16-B streaming stores (device allocations are 256-B aligned), the odd word and the tail apart
     v4i* __restrict__ a4 = reinterpret_cast<v4i*>(abits);
     v4i ones;
     ones.x = ones.y = ones.z = ones.w = -1;
+#ifdef LPA_FILL_PLAIN_STORES  // A/B variant build: ordinary stores
+    for (int64_t i = tid; i < (nfw >> 1); i += nth) a4[i] = ones;
+#else
     for (int64_t i = tid; i < (nfw >> 1); i += nth) __builtin_nontemporal_store(ones, a4 + i);
+#endif
   }
   if (tid == 0 && (nfw & 1)) abits[nfw - 1] = ~0ull;
   if (tid == 0 && (arcs & 63)) abits[nfw] = (1ull << (arcs & 63)) - 1ull;
@@ -1085,6 +1167,34 @@ __global__ __launch_bounds__(1024) void k_fill_decide(const unsigned long long* 
   (void)al;
   (void)nslots;
 #endif
+}
+
+// kStep3 (superstep 3's fill-scatter form, launch_refresh): the count and the decision alone,
+// on gbits64 = gbits_next and gword[GW_HOT3], into gword[GW_FILL3] and nothing else.  THE FILL MAY NOT PRECEDE
+// THIS DECISION there: after superstep 2 a refused form is followed by a stream rebuild that
+// rewrites every word, but here it is followed by k_al_scatter, which relies on the kept bits --
+// so k_al_scatter fills, once the form is taken, and does the form's bookkeeping.  Taken when
+// the new vector is in bits mode and (mode 2: always) no column off G is longer than cap, more
+// than fr_thr arcs are dirty (below that share superstep 4 would want the frontier marks the
+// form does not write, and the fill no longer pays) and the arcs of the columns off G are at
+// most kFill3Ratio of the dirty arcs.
+template <bool kIfWanted, bool kStep3 = false>
+__global__ __launch_bounds__(1024) void k_fill_decide(const unsigned long long* __restrict__ counters, int64_t thr,
+                                                     const unsigned long long* __restrict__ gbits64, int64_t n_iso,
+                                                     const int64_t* __restrict__ cptr, int64_t arcs, int64_t nhb,
+                                                     int64_t nslots, int32_t* __restrict__ gword,
+                                                     unsigned long long* __restrict__ abits,
+                                                     int32_t* __restrict__ al, int mode, int64_t frac_arcs,
+                                                     int64_t cap, unsigned long long* __restrict__ part,
+                                                     int64_t fr_thr = 0) {
+  if (kIfWanted && !rebuild_wanted(counters, thr)) return;
+  if (kStep3 && gword[GW_TRY3] == 0) return;  // uniform (k_giant_pick3)
+  if (!(nhb > 0 && 2 * (int64_t)gword[kStep3 ? GW_HOT3 : GW_HOT_BITS] >= nhb)) return;  // not the bits mode (uniform)
+  const int32_t G = gword[kStep3 ? GW_G3 : GW_G];
+  (void)G;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t nth = (int64_t)gridDim.x * blockDim.x;
+  if constexpr (!kStep3) fill_arc_bits(abits, al, arcs, G, nslots, tid, nth);
   // ---- the arcs of the columns off G: a wave takes kDecideWords bit words at a time (one
   // load), then four words' slots per round, their cptr loads in flight together ----
   constexpr int kDecideWords = 16;
@@ -1143,7 +1253,7 @@ __global__ __launch_bounds__(1024) void k_fill_decide(const unsigned long long* 
     part[2 * blockIdx.x] = sum;
     part[2 * blockIdx.x + 1] = mx;
     __threadfence();
-    s_last = atomicAdd(&gword[GW_FILL_TICKET], 1) == (int32_t)gridDim.x - 1;
+    s_last = atomicAdd(&gword[kStep3 ? GW_FILL3_TICKET : GW_FILL_TICKET], 1) == (int32_t)gridDim.x - 1;
   }
   __syncthreads();
   if (!s_last) return;  // uniform over the block
@@ -1157,6 +1267,12 @@ __global__ __launch_bounds__(1024) void k_fill_decide(const unsigned long long* 
   __syncthreads();  // (s_sum / s_max reused)
   reduce();
   if (threadIdx.x != 0) return;
+  if constexpr (kStep3) {
+    const int64_t dirty = (int64_t)counters[1];
+    if (mode == 2 || ((int64_t)mx <= cap && dirty > fr_thr && (double)sum <= kFill3Ratio * (double)dirty))
+      gword[GW_FILL3] = 1;
+    return;
+  }
   if (mode == 2 || ((int64_t)sum <= frac_arcs && (int64_t)mx <= cap)) {
     gword[GW_FILL] = 1;
     sparse_mark(gword, true, G);
@@ -1215,7 +1331,8 @@ constexpr bool kFillMerge = false;
 #else
 constexpr bool kFillMerge = true;
 #endif
-template <bool kIfWanted, bool kMerge>
+// kSlot: the gword word that says the form is taken (gword[GW_FILL3] in superstep 3's refresh)
+template <bool kIfWanted, bool kMerge, int kSlot = GW_FILL>
 __global__ __launch_bounds__(256) void k_fill_scatter(const unsigned long long* __restrict__ counters, int64_t thr,
                                                       const unsigned long long* __restrict__ gbits64, int64_t n_iso,
                                                       const int64_t* __restrict__ cptr,
@@ -1224,7 +1341,7 @@ __global__ __launch_bounds__(256) void k_fill_scatter(const unsigned long long* 
                                                       unsigned long long* __restrict__ abits,
                                                       const int32_t* __restrict__ gword) {
   if (kIfWanted && !rebuild_wanted(counters, thr)) return;
-  if (gword[GW_FILL] == 0) return;
+  if (gword[kSlot] == 0) return;
   const int lane = threadIdx.x & 63;
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6, ngrp = (n_iso + 63) >> 6;
@@ -1679,14 +1796,43 @@ int launch_refresh(lpa_graph* g, const int32_t* Lc, const int32_t* Ln, bool diff
     LPA_HIP(hipGetLastError());
     g->al_pending = false;  // the rebuild below (or this fill + the scatter) makes al valid
   }
+  // superstep 3 (fill_step3_now): the fill-scatter form in place of the scatter, decided on the
+  // device -- the pick, the bitmap and the count of the NEW vector ahead of k_al_scatter, which
+  // either scatters as ever or fills, and k_fill_scatter after it (k_al_scatter's note; the
+  // wanted-rebuild launches below follow either way and return at once when the form ran).
+  // Every other superstep and handle: none of these launches.
+  const bool fill3 = fill_step3_now(g) && !fold_rebuild && !gnow && g->vpad <= kHotMaxSlots;
+  const int64_t n_iso = g->bin_begin[BIN_ISO];
+  const int64_t fr_thr = (int64_t)(kFrontierFrac * (double)g->arcs);
+  if (fill3) {
+    const int64_t ngrp = (g->vpad + 511) / 512;
+    const unsigned gd = cap_grid(std::max<int64_t>((n_iso + 1023) / 1024, (g->arcs / 64 + 8191) / 8192), kFillBlocks);
+    hipLaunchKernelGGL(k_giant_pick3, dim3(1), dim3(kPickK), 0, s, ctr, thr, Ln, g->V, g->gword, g->fill_step3);
+    hipLaunchKernelGGL((k_giant_bits<false, true>), dim3(cap_grid((ngrp + 3) / 4, 4096)), dim3(256), 0, s, ctr, thr,
+                       Ln, g->vpad, g->gword, (unsigned long long*)g->gbits_next, g->abits, (int64_t)0, ~0ull,
+                       kHotBits);
+    hipLaunchKernelGGL((k_fill_decide<false, true>), dim3(gd), dim3(1024), 0, s, ctr, thr,
+                       (const unsigned long long*)g->gbits_next, n_iso, g->cptr, g->arcs,
+                       std::min<int64_t>(g->vpad, kHotBits), g->vpad, g->gword, g->abits, g->al, g->fill_step3,
+                       (int64_t)0, std::max<int64_t>(kFillCap, g->arcs >> kFillCapShift), g->fill_part, fr_thr);
+    LPA_HIP(hipGetLastError());
+  }
   hipLaunchKernelGGL(k_al_scatter, dim3(2048), dim3(256), 0, s, g->chlist, (const uint4*)g->chflag,
                      (g->n_chunk_scan + 15) / 16, g->cowner, g->cch, ctr,
                      g->counters + 4 * (par ^ 1), g->cptr,
                      g->cpos, Ln, gnow ? (int32_t*)nullptr : g->al, thr, fm, g->fr_all + (par ^ 1),
-                     g->frontier, (int64_t)(kFrontierFrac * (double)g->arcs), const_cast<int32_t*>(Lc),
+                     g->frontier, fr_thr, const_cast<int32_t*>(Lc),
                      (fold_rebuild && !gnow) ? g->col : (const int32_t*)nullptr, g->arcs, g->gword,
-                     keep_bits ? 1 : 0, g->gbits, g->abits);
+                     keep_bits ? 1 : 0, g->gbits, g->abits, fill3 ? 1 : 0, (const uint32_t*)g->gbits_next, g->vpad);
   LPA_HIP(hipGetLastError());
+  if (fill3) {
+    // (unchanged: it reads gbits, now the new vector's, as it does after superstep 2)
+    hipLaunchKernelGGL((k_fill_scatter<false, kFillMerge, GW_FILL3>),
+                       dim3(cap_grid((n_iso + 64 * 4 * kFillGroups - 1) / (64 * 4 * kFillGroups), 8192)), dim3(256), 0,
+                       s, ctr, thr, (const unsigned long long*)g->gbits, n_iso, g->cptr, g->cpos, Ln, g->al, g->abits,
+                       g->gword);
+    LPA_HIP(hipGetLastError());
+  }
   LPA_TRACE_POINT("scatter");
   if (ev_scatter) LPA_HIP(hipEventRecord(ev_scatter, s));  // profiling: scatter | rebuild
   if (gnow && gather_last_step(g)) {

@@ -13,7 +13,8 @@
 //              its refresh may take them as well; captured per (superstep, cur, par)
 //   3          rows settled from the arc giant bits of superstep 2's rebuild (settle3_now)
 //              or from the giant codes of superstep 2's refresh (code_tally3_now); its
-//              scatter keeps the arc giant bits (keep_bits_now); captured like superstep 2
+//              scatter keeps the arc giant bits (keep_bits_now), or its refresh takes the
+//              fill-scatter form and leaves exact ones (fill_step3_now); captured like superstep 2
 //   4          rows below the hubs settled from a fresh abits pass while every hub unit
 //              is re-tallied (settle4_now); the last one that is offered G, that queues
 //              the units last and whose row bins peel once; launched eagerly
@@ -94,6 +95,15 @@ inline bool rows_peel_once_now(const lpa_graph* g) { return g->since_reset <= 3;
 // (k_al_scatter; superstep 4's row settle reads them)
 inline bool keep_bits_now(const lpa_graph* g) {
   return g->since_reset == 2 && g->abits != nullptr && g->gbits != nullptr && !gather_now(g) && g->keep_bits;
+}
+// superstep 3's refresh may take the fill-scatter form in place of its scatter (one GPU, sparse
+// al[], outside gather mode, LPA_FILL_STEP3; the decision itself is taken on the device).  The
+// form writes no frontier marks and syncs no label: superstep 4 tallies or settles every row
+// (settle3_now sets force_all_next whenever abits exists, whatever the other switches)
+inline bool fill_step3_now(const lpa_graph* g) {
+  return g->since_reset == 2 && g->sparse_al && g->fill_scatter != 0 && g->fill_step3 != 0 && g->nranks == 1 &&
+         !g->gather && !g->no_scatter && g->rebuild_hot && g->cptr && g->cpos && g->abits && g->gbits &&
+         g->gbits_next && g->fill_part;
 }
 
 // from superstep kDenseSupersteps + 3 on a superstep is converged: frontier lists, captured

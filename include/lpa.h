@@ -103,7 +103,8 @@ typedef struct lpa_graph_info {
                               arcs' labels (LPA_SPARSE_AL=0: never; since ABI 15)      */
   int64_t fill_refreshes;  /* ... those of them that took the fill-scatter form: every arc
                               bit set, then only the columns off the giant label visited
-                              through the CSC index (LPA_FILL_SCATTER=0: never; since ABI 17) */
+                              through the CSC index (LPA_FILL_SCATTER=0: never; since ABI 17;
+                              superstep 3's refresh in that form, LPA_FILL_STEP3, counts too) */
 } lpa_graph_info;
 
 /* Outlier summary. */
