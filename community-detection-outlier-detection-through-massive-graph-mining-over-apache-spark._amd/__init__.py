@@ -8,13 +8,15 @@ include/lpa.h); importing this package does not load it -- the first call does,
 and fails loudly if it has not been built.
 """
 from .graph import Graph, Loopback, comm_unique_id, gen_chunglu, gen_rmat, gen_sbm, run_ranks
-from .graphframe import (GraphFrame, IndexedGraph, OutlierResult, connected_components, core_number, index_graph,
+from .graphframe import (GraphFrame, IndexedGraph, OutlierResult, bfs, connected_components, core_number,
+                         count_paths, enumerate_paths, index_graph,
                          k_core, label_propagation, louvain, outlier_scores, page_rank,
                          parallel_personalized_page_rank, shortest_paths, strongly_connected_components,
                          triangle_count)
 from . import ingest
 
 __all__ = ["Graph", "Loopback", "run_ranks", "GraphFrame", "IndexedGraph", "OutlierResult", "comm_unique_id", "gen_chunglu", "gen_rmat",
-           "gen_sbm", "connected_components", "core_number", "index_graph", "ingest", "k_core", "label_propagation", "louvain",
+           "gen_sbm", "bfs", "connected_components", "core_number", "count_paths", "enumerate_paths", "index_graph", "ingest", "k_core",
+           "label_propagation", "louvain",
            "outlier_scores", "page_rank", "parallel_personalized_page_rank", "shortest_paths", "strongly_connected_components",
            "triangle_count"]

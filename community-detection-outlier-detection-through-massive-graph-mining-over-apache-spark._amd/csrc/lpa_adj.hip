@@ -1,10 +1,11 @@
 // The edge-list builds that the algorithm calls share, and the kernels around them.
 //
-// Directed arcs (arcs_count / arcs_lists: lpa_sp.hip, lpa_scc.hip): the distinct non-loop
+// Directed arcs (arcs_count / arcs_lists: lpa_sp.hip, lpa_scc.hip, lpa_bfs.hip): the distinct non-loop
 // arcs of the input graph, as out-lists and in-lists.
 //   keys     (src << 32 | dst) of every in-range non-loop edge; anything else gets
-//            (V << 32 | V) and sorts behind every vertex.  The halves hold values up to V:
-//            bits_for(V) bits a half
+//            (V << 32 | V) and sorts behind every vertex, and so does an edge that the
+//            caller's keep mask (lpa_bfs.hip; null: every edge is kept) leaves out.  The
+//            halves hold values up to V: bits_for(V) bits a half
 //   sort     radix sort over both halves; a key that differs from its predecessor is kept
 //            (flag byte, u32 scan): E distinct arcs in (src, dst) order, E read on the host
 //   out      compaction; oo[u] = the first arc with source >= u (a binary search per
@@ -33,14 +34,16 @@ namespace {
 
 // ---- directed arcs ----
 // kLoops: loop[a] = 1 for every in-range self-loop (plain byte stores)
-template <bool kLoops>
+// kKeep: an edge with keep[i] == 0 is no edge (nor a loop)
+template <bool kLoops, bool kKeep>
 __global__ __launch_bounds__(256) void k_arc_keys(const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
                                                   int64_t m, u32 V, u64* __restrict__ keys,
-                                                  uint8_t* __restrict__ loop) {
+                                                  uint8_t* __restrict__ loop, const uint8_t* __restrict__ keep) {
   GRID_STRIDE(i, m) {
     const u32 a = (u32)__builtin_nontemporal_load(src + i), b = (u32)__builtin_nontemporal_load(dst + i);
-    keys[i] = a < V && b < V && a != b ? ((u64)a << 32) | b : ((u64)V << 32) | V;
-    if (kLoops && a == b && a < V) loop[a] = 1;
+    const bool kept = !kKeep || keep[i] != 0;
+    keys[i] = kept && a < V && b < V && a != b ? ((u64)a << 32) | b : ((u64)V << 32) | V;
+    if (kLoops && kept && a == b && a < V) loop[a] = 1;
   }
 }
 
@@ -197,7 +200,7 @@ int key_col(const u64* keys, int64_t n, int32_t* col, hipStream_t s) {
   return LPA_OK;
 }
 
-int arcs_count(lpa_graph* g, Tmp& tmp, uint8_t* loop, ArcLists* a) {
+int arcs_count(lpa_graph* g, Tmp& tmp, uint8_t* loop, ArcLists* a, const uint8_t* keep) {
   hipStream_t s = g->stream;
   const int64_t V = g->V, m = g->m;
   a->E = 0;
@@ -207,11 +210,9 @@ int arcs_count(lpa_graph* g, Tmp& tmp, uint8_t* loop, ArcLists* a) {
   LPA_TRY(tmp.get(&a->flag, m));
   LPA_TRY(tmp.get(&a->pos, m + 1));
   u64* keys = a->keys;
-  if (loop)
-    hipLaunchKernelGGL(k_arc_keys<true>, dim3(grid_for(m)), dim3(256), 0, s, g->e_src, g->e_dst, m, (u32)V, keys, loop);
-  else
-    hipLaunchKernelGGL(k_arc_keys<false>, dim3(grid_for(m)), dim3(256), 0, s, g->e_src, g->e_dst, m, (u32)V, keys,
-                       loop);
+  auto* k_keys = loop ? (keep ? k_arc_keys<true, true> : k_arc_keys<true, false>)
+                      : (keep ? k_arc_keys<false, true> : k_arc_keys<false, false>);
+  hipLaunchKernelGGL(k_keys, dim3(grid_for(m)), dim3(256), 0, s, g->e_src, g->e_dst, m, (u32)V, keys, loop, keep);
   LPA_HIP(hipGetLastError());
   LPA_TRY(radix_sort_u64(keys, keys + m, m, sh.both(), 2 * sh.ns, s));
   hipLaunchKernelGGL(k_arc_uniq, dim3(grid_for(m)), dim3(256), 0, s, keys, m, (u32)V, a->flag);

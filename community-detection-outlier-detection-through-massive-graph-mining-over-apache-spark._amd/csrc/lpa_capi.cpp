@@ -251,6 +251,9 @@ int create_common(int32_t device, hipStream_t stream, const int32_t* src, const 
   }
   if (const char* f = getenv("LPA_SP_ALPHA")) g->sp_alpha = atoi(f) < 0 ? 0 : atoi(f);
   if (const char* f = getenv("LPA_SP_PULL")) g->sp_pull = atoi(f) == 1 ? 1 : 0;
+  if (const char* f = getenv("LPA_BFS_ALPHA")) g->bfs_alpha = atoi(f) < 0 ? 0 : atoi(f);
+  if (const char* f = getenv("LPA_BFS_PULL")) g->bfs_pull = atoi(f) == 1 ? 1 : 0;
+  if (const char* f = getenv("LPA_BFS_TIMES")) g->bfs_times = atoi(f) == 1 ? 1 : 0;
   if (const char* f = getenv("LPA_SCC_BLOCK"))
     g->scc_block = atoi(f) < 0 ? 0 : atoi(f) > lpa::kSccTrimCap ? lpa::kSccTrimCap : atoi(f);
   if (const char* f = getenv("LPA_KC_SHORT")) g->kc_short = atoi(f) < 0 ? 0 : atoi(f);
@@ -785,6 +788,32 @@ int lpa_shortest_paths(lpa_graph* g, const int32_t* landmarks, int32_t n_landmar
   }
   LPA_HIP(hipSetDevice(g->device));
   return shortest_paths(g, landmarks, n_landmarks, dist_out, out_is_device, summary);
+}
+
+int lpa_bfs(lpa_graph* g, const uint8_t* from_mask, const uint8_t* to_mask, const uint8_t* edge_keep, int32_t max_len,
+            int32_t* level_out, uint8_t* on_edge_out, lpa_bfs_summary* summary) {
+  if (!g) {
+    set_error("null handle");
+    return LPA_EINVAL;
+  }
+  if (max_len < 0) {
+    set_error("lpa_bfs: max_len must not be negative, got %d", max_len);
+    return LPA_EINVAL;
+  }
+  if (g->V > 0 && (!from_mask || !to_mask)) {
+    set_error("lpa_bfs: null vertex mask");
+    return LPA_EINVAL;
+  }
+  if ((g->V > 0 && !level_out) || (g->V > 0 && g->m > 0 && !on_edge_out)) {
+    set_error("lpa_bfs: null output");
+    return LPA_EINVAL;
+  }
+  if (g->m > 0 && !g->e_src) {
+    set_error("lpa_bfs of a distributed job runs on rank 0 (the rank that keeps the edge list)");
+    return LPA_EINVAL;
+  }
+  LPA_HIP(hipSetDevice(g->device));
+  return bfs(g, from_mask, to_mask, edge_keep, max_len, level_out, on_edge_out, summary);
 }
 
 int lpa_strongly_connected_components(lpa_graph* g, int32_t max_iter, int32_t* comp_out, int32_t out_is_device,

@@ -110,6 +110,9 @@ constexpr int kPprBatch = 16;         // the default (DESIGN.md "Parallel person
 constexpr int kSpShort = 32;          // 8 lanes per row up to this length
 constexpr int kSpWave = 1024;         // a wave per row up to this length; longer: a block of 1024 per row
 constexpr int kSpAlpha = 14;          // pull when the frontier's in-arcs exceed the unfinished out-arcs / this
+// breadth-first search (lpa_bfs.hip): its row forms are the shortest paths' (kSpShort / kSpWave);
+// the default of its push / pull switch is theirs too (DESIGN.md "Breadth-first search": measured)
+constexpr int kBfsAlpha = kSpAlpha;   // pull when the frontier's out-arcs exceed the unseen vertices' in-arcs / this
 // strongly connected components (lpa_scc.hip): list lengths of its row forms (out + in lists in the
 // trim, out-lists in the colour push, in-lists in the colour pull and the mark) and the in-block trim
 constexpr int kSccShort = 32;         // 8 lanes per row up to this length
@@ -464,6 +467,10 @@ struct lpa_graph {
   // shortest paths (lpa_sp.hip): the push / pull switch of a level
   int sp_alpha = lpa::kSpAlpha;             // LPA_SP_ALPHA (>= 0; 0: never pull)
   int sp_pull = 0;                          // LPA_SP_PULL=1: pull at every level
+  // breadth-first search (lpa_bfs.hip): the push / pull switch of a level, and the stage clock
+  int bfs_alpha = lpa::kBfsAlpha;           // LPA_BFS_ALPHA (>= 0; 0: never pull)
+  int bfs_pull = 0;                         // LPA_BFS_PULL=1: pull at every level
+  int bfs_times = 0;                        // LPA_BFS_TIMES=1: a line of stage times on stderr per call
   // strongly connected components (lpa_scc.hip): the largest trim level that runs inside one block
   int scc_block = lpa::kSccBlockTrim;       // LPA_SCC_BLOCK (0 .. kSccTrimCap; 0: every level is a launch)
   // k-core decomposition (lpa_kcore.hip): list lengths up to which a queued row takes the short form and
@@ -694,7 +701,8 @@ int pr_build(lpa_graph* g, PrCsr* b);
 struct Tmp;
 // The distinct non-loop arcs of the directed graph, in two steps.  arcs_count: keys, sort,
 // flags, scan; synchronises once and leaves E (loop, nullable: [V] zeroed by the caller, set to
-// 1 at every vertex with a self-loop).  arcs_lists: the out-lists and in-lists from that.
+// 1 at every vertex with a self-loop; keep, nullable: [m] device bytes, an edge with keep == 0 is
+// no edge).  arcs_lists: the out-lists and in-lists from that.
 struct ArcLists {
   int64_t E = 0;               // distinct arcs
   int64_t *oo = nullptr, *io = nullptr;      // [V + 1] offsets of the out-lists / the in-lists
@@ -703,7 +711,7 @@ struct ArcLists {
   uint8_t* flag = nullptr;     // [m]
   u32* pos = nullptr;          // [m + 1]
 };
-int arcs_count(lpa_graph* g, Tmp& tmp, uint8_t* loop, ArcLists* a);
+int arcs_count(lpa_graph* g, Tmp& tmp, uint8_t* loop, ArcLists* a, const uint8_t* keep = nullptr);
 int arcs_lists(lpa_graph* g, Tmp& tmp, ArcLists* a);
 // The rows that take the wave form (short_max < L <= wave_max; L = off[v + 1] - off[v]) in
 // (*lists)[0, n_rows[0]) and the block form (longer) in (*lists)[V, V + n_rows[1]), ascending.
@@ -744,6 +752,11 @@ int parallel_pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, const i
 // landmark shortest paths of the directed graph (lpa_sp.hip); the landmarks are in [0, V)
 int shortest_paths(lpa_graph* g, const int32_t* landmarks, int32_t n_landmarks, int32_t* dist_out,
                    int32_t out_is_device, lpa_sp_summary* summary);
+
+// breadth-first search between two vertex sets over the kept edges (lpa_bfs.hip); the arguments
+// are checked by the caller
+int bfs(lpa_graph* g, const uint8_t* from_mask, const uint8_t* to_mask, const uint8_t* edge_keep, int32_t max_len,
+        int32_t* level_out, uint8_t* on_edge_out, lpa_bfs_summary* summary);
 
 // strongly connected components of the directed graph, GraphX's rounds (lpa_scc.hip)
 int strongly_connected_components(lpa_graph* g, int32_t max_iter, int32_t* comp_out, int32_t out_is_device,

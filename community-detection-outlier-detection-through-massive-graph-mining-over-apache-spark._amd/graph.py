@@ -530,6 +530,55 @@ class Graph:
                                                 ctypes.byref(summ) if stats else None))
         return (dist, summ.to_dict()) if stats else dist
 
+    # -- breadth-first search ---------------------------------------------------------
+    @staticmethod
+    def _mask(name, x, n):
+        """A boolean or uint8 array of length n as contiguous uint8 (TypeError for another dtype or
+        dimension, ValueError for another length)."""
+        a = np.asarray(x)
+        if a.dtype != np.bool_ and a.dtype != np.uint8:
+            raise TypeError(f"{name} must be a boolean or uint8 array, got dtype {a.dtype}")
+        if a.ndim != 1:
+            raise TypeError(f"{name} must be one-dimensional, got {a.ndim} dimensions")
+        if a.size != n:
+            raise ValueError(f"{name} must have {n} entries, got {a.size}")
+        return np.ascontiguousarray(a).view(np.uint8)
+
+    def bfs(self, from_mask, to_mask, edge_keep=None, max_path_length: int = 10, stats: bool = False):
+        """Breadth-first search between two vertex sets of the directed input graph (lpa_bfs;
+        GraphFrames ``lib.BFS``): F = the vertices of ``from_mask``, T = those of ``to_mask``
+        (boolean or uint8 arrays of ``num_vertices`` entries), over the input edges that
+        ``edge_keep`` (``num_edges`` entries, ``None``: all) keeps, self-loops never.  Returns
+        ``(length, level, edge_index)``: ``length`` is the fewest edges on a path from F to T, 0
+        when the sets share a vertex, -1 when there is no path of at most ``max_path_length``
+        edges (or a set is empty); ``level`` (int32, ``num_vertices`` entries) is the place of a
+        vertex on a path of ``length`` edges from F to T and -1 off all of them; ``edge_index``
+        (int64, ascending) lists the input edges on such a path, a duplicate edge beside its
+        twin.  Every path of ``length`` edges from F to T is a walk over those edges from level
+        0 to level ``length`` (``enumerate_paths`` lists them).  ``stats=True`` adds ``summary``,
+        a dict of arcs, sources, targets, length, reached, path_vertices, path_edges,
+        push_levels, pull_levels.  The result is identical across runs, handles and push / pull
+        schedules, ``level`` across input edge orders too.  The labels and the LPA state are not
+        touched."""
+        if not isinstance(max_path_length, (int, np.integer)) or isinstance(max_path_length, (bool, np.bool_)):
+            raise TypeError(f"max_path_length must be an int, got {type(max_path_length).__name__}")
+        if max_path_length < 0:
+            raise ValueError(f"max_path_length must not be negative, got {max_path_length}")
+        V, m = self.num_vertices, self.num_edges
+        fm = self._mask("from_mask", from_mask, V)
+        tm = self._mask("to_mask", to_mask, V)
+        keep = None if edge_keep is None else self._mask("edge_keep", edge_keep, m)
+        level = np.empty(V, dtype=np.int32)
+        on_edge = np.empty(m, dtype=np.uint8)
+        summ = _lib.LpaBfsSummary()
+        u8 = _lib._u8p
+        _lib.check(self._lib.lpa_bfs(self._handle(), fm.ctypes.data_as(u8), tm.ctypes.data_as(u8),
+                                     None if keep is None else keep.ctypes.data_as(u8),
+                                     min(int(max_path_length), 2 ** 31 - 1), level.ctypes.data_as(_lib._i32p),
+                                     on_edge.ctypes.data_as(u8), ctypes.byref(summ)))
+        res = (int(summ.length), level, np.flatnonzero(on_edge.view(np.bool_)).astype(np.int64, copy=False))
+        return res + (summ.to_dict(),) if stats else res
+
     # -- strongly connected components ------------------------------------------------
     def strongly_connected_components(self, max_iter=None, out=None, sizes: bool = False):
         """Strongly connected components of the directed input graph

@@ -110,6 +110,103 @@ def _check_core_k(k, name="k"):
         raise ValueError(f"{name} must not be negative, but got {k}")
 
 
+def _check_bfs(maxPathLength, maxPaths):
+    """The argument checks of GraphFrame.bfs that need no table, before any device work."""
+    if not isinstance(maxPathLength, (int, np.integer)) or isinstance(maxPathLength, (bool, np.bool_)):
+        raise TypeError(f"maxPathLength must be an int, got {type(maxPathLength).__name__}")
+    if maxPathLength < 0:
+        # graphframes.lib.BFS.run: require(maxPathLength >= 0, ...)
+        raise ValueError(f"requirement failed: BFS maxPathLength must be >= 0, but was set to {maxPathLength}")
+    if maxPaths is not None:
+        if not isinstance(maxPaths, (int, np.integer)) or isinstance(maxPaths, (bool, np.bool_)):
+            raise TypeError(f"maxPaths must be an int or None, got {type(maxPaths).__name__}")
+        if maxPaths < 0:
+            raise ValueError(f"maxPaths must not be negative, got {maxPaths}")
+
+
+def _bfs_mask(frame: pd.DataFrame, expr, name: str) -> np.ndarray:
+    """``expr`` over ``frame`` as a boolean array of its length: a str goes through
+    ``DataFrame.eval``, a callable is called with the frame, a boolean Series or array is taken
+    positionally."""
+    if isinstance(expr, str):
+        try:
+            val = frame.eval(expr)
+        except Exception as e:  # noqa: BLE001 -- pandas raises many types for a bad expression
+            raise ValueError(f"{name}: cannot evaluate {expr!r}: {e}") from e
+    elif callable(expr):
+        val = expr(frame)
+    elif isinstance(expr, (pd.Series, np.ndarray)):
+        val = expr
+    else:
+        raise TypeError(f"{name} must be a str, a callable or a boolean Series or array, got {type(expr).__name__}")
+    if not isinstance(val, (pd.Series, np.ndarray)):
+        raise TypeError(f"{name} must yield a boolean column, got {type(val).__name__}")
+    a = np.asarray(val)
+    if a.dtype != np.bool_:
+        raise TypeError(f"{name} must yield a boolean column, got dtype {a.dtype}")
+    if a.ndim != 1:
+        raise TypeError(f"{name} must yield one column, got {a.ndim} dimensions")
+    if a.size != len(frame):
+        raise ValueError(f"{name} must yield {len(frame)} entries, got {a.size}")
+    return a
+
+
+def _path_dag(level, src, dst, edge_index):
+    """The marked edges grouped by source, ascending edge index inside a group: (sorted edge
+    indices, their targets, start of each vertex's group [V + 1])."""
+    level = np.asarray(level)
+    eidx = np.asarray(edge_index, dtype=np.int64)
+    es = np.asarray(src)[eidx].astype(np.int64)
+    order = np.lexsort((eidx, es))
+    off = np.zeros(level.size + 1, dtype=np.int64)
+    np.cumsum(np.bincount(es, minlength=level.size), out=off[1:])
+    return eidx[order], np.asarray(dst)[eidx[order]].astype(np.int64), off
+
+
+def count_paths(level, src, dst, edge_index, length) -> int:
+    """The number of rows ``enumerate_paths`` would return, counted over the DAG level by level
+    (exact below 2^53, float64 above)."""
+    if length <= 0:
+        return 0
+    level = np.asarray(level)
+    eidx = np.asarray(edge_index, dtype=np.int64)
+    es, ed = np.asarray(src)[eidx].astype(np.int64), np.asarray(dst)[eidx].astype(np.int64)
+    n = (level == length).astype(np.float64)      # paths from the vertex to a target
+    le = level[es]
+    for l in range(int(length) - 1, -1, -1):
+        at = le == l
+        np.add.at(n, es[at], n[ed[at]])
+    return int(n[level == 0].sum())
+
+
+def enumerate_paths(level, src, dst, edge_index, length):
+    """Every path of ``length`` edges of a ``Graph.bfs`` result: ``level`` [V], the edge list
+    ``src`` / ``dst`` it was built on, the marked ``edge_index``.  Returns ``(verts [n, L + 1]
+    int32, edges [n, L] int64)``: row i is one path, its vertices (dense ids) and the indices of
+    its edges; the rows are sorted by the tuple of edge indices.  One level is one join: every
+    path is repeated by the out-count of its last vertex (``np.repeat``).  A pure host
+    function."""
+    L = int(length)
+    if L <= 0:
+        return np.empty((0, max(L, 0) + 1), np.int32), np.empty((0, 0), np.int64)
+    level = np.asarray(level)
+    se, sd, off = _path_dag(level, src, dst, edge_index)
+    eidx = np.asarray(edge_index, dtype=np.int64)
+    es = np.asarray(src)[eidx].astype(np.int64)
+    first = np.sort(eidx[level[es] == 0])
+    verts = [np.asarray(src)[first].astype(np.int64), np.asarray(dst)[first].astype(np.int64)]
+    edges = [first]
+    for _ in range(1, L):
+        end = verts[-1]
+        cnt = off[end + 1] - off[end]
+        rep = np.repeat(np.arange(end.size), cnt)
+        start = np.cumsum(cnt) - cnt
+        pos = off[end][rep] + (np.arange(rep.size) - start[rep])
+        verts = [c[rep] for c in verts] + [sd[pos]]
+        edges = [c[rep] for c in edges] + [se[pos]]
+    return np.stack(verts, axis=1).astype(np.int32), np.stack(edges, axis=1)
+
+
 def _check_cc_algorithm(algorithm):
     if algorithm not in CC_ALGORITHMS:
         # graphframes.lib.ConnectedComponents.setAlgorithm: require(supportedAlgorithms.contains(value), ...)
@@ -454,6 +551,76 @@ class GraphFrame:
             maps[:] = [{keys[l]: int(dist[l, v]) for l in np.flatnonzero(dist[:, v] >= 0)} for v in range(V)]
         return _attach(self._v, ig, {DISTANCES: maps})
 
+    def bfs(self, fromExpr, toExpr, edgeFilter=None, maxPathLength: int = 10, *, maxPaths=None) -> pd.DataFrame:
+        """``GraphFrame.bfs(fromExpr, toExpr, edgeFilter, maxPathLength)`` (GraphFrames
+        ``lib.BFS``): every shortest path from a vertex satisfying ``fromExpr`` to a vertex
+        satisfying ``toExpr`` over the edges satisfying ``edgeFilter`` (``None``: all), of at
+        most ``maxPathLength`` edges; self-loops are never on a path, a duplicate edge gives one
+        more path.
+
+        Expressions are **pandas** syntax, not Spark SQL: a ``str`` is evaluated with
+        ``DataFrame.eval`` on the vertex frame (the edge frame for ``edgeFilter``), so write
+        ``"id == 'a'"``, not ``"id = 'a'"``; it must yield a boolean column.  A boolean Series or
+        array of the frame's length is taken positionally; a callable is called with the frame.
+        Where an id repeats in the vertex frame its first row stands for the vertex.
+
+        The result has two-level columns, the pandas form of Spark's struct columns: the top
+        level is ``from, e0, v1, e1, ..., to``, the second every vertex column (vertex groups)
+        or every edge column (edge groups), so ``paths["from"]["id"]`` reads as
+        ``paths.select("from.id")`` does.  One row per path, sorted by the tuple of input-edge
+        row numbers ``(e0, e1, ...)`` (GraphFrames promises no order).  When the two sets share
+        a vertex the result is those vertices, sorted by id, under ``from`` and ``to``; when a
+        set is empty or no path of at most ``maxPathLength`` edges exists it is
+        ``vertices.iloc[0:0]``; neither of the first two touches the GPU.
+        ``.attrs["length"]`` is the number of edges of a path (0 for shared vertices, -1 for
+        none), ``.attrs["paths"]`` the number of rows.  ``maxPaths``: the paths are counted
+        before they are materialised, and a count above it raises ``ValueError``."""
+        _check_bfs(maxPathLength, maxPaths)
+        v, e = self._v, self._e
+        fm = _bfs_mask(v, fromExpr, "fromExpr")
+        tm = _bfs_mask(v, toExpr, "toExpr")
+        ef = None if edgeFilter is None else _bfs_mask(e, edgeFilter, "edgeFilter")
+        ig = self._indexed()
+        V = ig.num_vertices
+        # the first row of every id stands for the vertex
+        pos = np.searchsorted(ig.ids, v[ID].to_numpy())
+        rep = np.zeros(V, dtype=np.int64)
+        rep[pos[::-1]] = np.arange(len(v) - 1, -1, -1)
+        F, T = fm[rep], tm[rep]
+
+        def none():
+            out = v.iloc[0:0].copy()
+            out.attrs["length"], out.attrs["paths"] = -1, 0
+            return out
+
+        if not F.any() or not T.any():
+            return none()
+        both = np.flatnonzero(F & T)
+        if both.size:
+            rows = v.iloc[rep[both]].reset_index(drop=True)
+            out = pd.concat([rows, rows], axis=1, keys=["from", "to"])
+            out.attrs["length"], out.attrs["paths"] = 0, int(both.size)
+            return out
+        keep = None if ef is None else ef[ig.kept]
+        length, level, eidx = self._gpu_graph().bfs(F, T, keep, int(maxPathLength))
+        if length <= 0:
+            return none()
+        n = count_paths(level, ig.src, ig.dst, eidx, length)
+        if maxPaths is not None and n > maxPaths:
+            raise ValueError(f"bfs: {n} paths of {length} edges, more than maxPaths = {maxPaths}")
+        verts, edges = enumerate_paths(level, ig.src, ig.dst, eidx, length)
+        in_row = np.flatnonzero(ig.kept)   # edge index of the dense graph -> row of the edge frame
+        names, parts = [], []
+        for j in range(length + 1):
+            names.append("from" if j == 0 else "to" if j == length else f"v{j}")
+            parts.append(v.iloc[rep[verts[:, j]]].reset_index(drop=True))
+            if j < length:
+                names.append(f"e{j}")
+                parts.append(e.iloc[in_row[edges[:, j]]].reset_index(drop=True))
+        out = pd.concat(parts, axis=1, keys=names)
+        out.attrs["length"], out.attrs["paths"] = int(length), int(len(out))
+        return out
+
     def inDegrees(self) -> pd.DataFrame:
         """Vertices + ``inDegree`` (int64): the kept edges ending at each vertex, duplicates
         counted.  Every vertex has a row, with 0 where GraphFrames' property leaves the
@@ -586,6 +753,18 @@ def shortest_paths(vertices: pd.DataFrame, edges: pd.DataFrame, landmarks, devic
     gf = GraphFrame(vertices, edges, device=device)
     try:
         return gf.shortestPaths(landmarks)
+    finally:
+        gf.close()
+
+
+def bfs(vertices: pd.DataFrame, edges: pd.DataFrame, fromExpr, toExpr, edgeFilter=None, maxPathLength: int = 10, *,
+        maxPaths=None, device: int = 0) -> pd.DataFrame:
+    """Function form of ``GraphFrame(vertices, edges).bfs(fromExpr, toExpr, edgeFilter,
+    maxPathLength, maxPaths=maxPaths)``."""
+    _check_bfs(maxPathLength, maxPaths)
+    gf = GraphFrame(vertices, edges, device=device)
+    try:
+        return gf.bfs(fromExpr, toExpr, edgeFilter, maxPathLength, maxPaths=maxPaths)
     finally:
         gf.close()
 

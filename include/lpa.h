@@ -472,6 +472,63 @@ int lpa_shortest_paths(lpa_graph* g, const int32_t* landmarks /* host, dense ids
                        int32_t out_is_device, lpa_sp_summary* summary /* nullable */);
 
 /*
+ * Breadth-first search between two vertex sets (GraphFrames lib.BFS / GraphFrame.bfs(fromExpr,
+ * toExpr, edgeFilter, maxPathLength)) over the DIRECTED input graph.  F = the vertices with
+ * from_mask != 0, T = those with to_mask != 0; the kept edges are the input edges with
+ * edge_keep != 0 (null: all of them).  m and the edge order are the handle's input edge list.
+ * An edge with an end outside [0, V) is no edge; a self-loop is never on a path.  L = the
+ * smallest number of kept, non-loop edges on a directed path src -> dst from a vertex of F to a
+ * vertex of T.  With 1 <= L <= max_len the result describes EVERY path of L edges from F to T
+ * (GraphFrames' result rows, which the caller enumerates): level_out[v] = i for a vertex that is
+ * the i-th of such a path (0 in F, L in T), -1 for every other vertex; on_edge_out[e] = 1 for an
+ * input edge e = (a, b) that is kept, no loop, and has level_out[a] >= 0 and level_out[b] ==
+ * level_out[a] + 1 (a duplicate edge is marked like its twin: one more path), 0 elsewhere.  The
+ * result paths are exactly the walks over marked edges from level 0 to level L.
+ *   F or T empty           length = -1, every level -1, no edge marked, reached = 0; no search
+ *   F and T share a vertex length = 0, level_out = 0 exactly on their common vertices, no edge
+ *                          marked, reached = |F|; no search
+ *   max_len == 0           can only give 0 or -1
+ *   no path of <= max_len  length = -1, every level -1, no edge marked
+ * V == 0: success, nothing written but the summary ({0, 0, 0, -1, 0, 0, 0, 0, 0}).  LPA_EINVAL for
+ * max_len < 0, for a null mask or level_out with V > 0, for a null on_edge_out with V > 0 and
+ * m > 0.  The three masks and the two outputs are host memory; summary is nullable (arcs is
+ * counted only when it is given or a search runs).  The call blocks until the work is done.
+ * One bit per vertex (bitmaps of ceil(V / 64) words); every level either a push along the
+ * frontier's out-lists (64-bit atomic ORs of one bit) or a pull in which every unseen vertex
+ * scans its in-list up to the first frontier vertex, chosen per level by Beamer's rule; the
+ * search stops at the first level that holds a vertex of T, at an empty frontier or at max_len;
+ * a backward sweep then keeps, level by level, the vertices with an arc to a kept vertex of the
+ * next level (DESIGN.md "Breadth-first search").  OR commutes: both outputs and every summary
+ * field but push_levels / pull_levels are a function of (V, edge list, masks, max_len) alone,
+ * identical across runs, handles and schedules; level_out is also identical across input edge
+ * orders and on_edge_out follows its edges through a permutation.  push_levels + pull_levels is
+ * L when a path is found, otherwise the levels expanded before the frontier emptied or max_len
+ * was reached.  All working memory is stream-ordered temporaries, the labels and every other
+ * piece of lpa_step's state are neither read nor written, nothing is kept on the handle.  On a
+ * distributed job (nranks > 1) only rank 0 keeps the edge list this needs; the other ranks
+ * return LPA_EINVAL.  Since ABI 18.
+ */
+typedef struct lpa_bfs_summary {
+  int64_t arcs;          /* distinct directed non-loop arcs of the kept edges                 */
+  int64_t sources;       /* |F|                                                               */
+  int64_t targets;       /* |T|                                                               */
+  int64_t length;        /* L; 0 if F and T share a vertex; -1 if no path within max_len      */
+  int64_t reached;       /* vertices the forward search gave a level, F included              */
+  int64_t path_vertices; /* vertices on a result path (F∩T's size when length == 0)           */
+  int64_t path_edges;    /* input edges marked in on_edge_out                                 */
+  int64_t push_levels;
+  int64_t pull_levels;   /* forward levels by form; their sum = levels expanded               */
+} lpa_bfs_summary;       /* 72 bytes */
+int lpa_bfs(lpa_graph* g,
+            const uint8_t* from_mask /* [V] host, nonzero = in F */,
+            const uint8_t* to_mask   /* [V] host */,
+            const uint8_t* edge_keep /* [m] host, nullable = keep all */,
+            int32_t max_len,
+            int32_t* level_out  /* [V] host: lev of a path vertex, -1 elsewhere */,
+            uint8_t* on_edge_out /* [m] host: 1 for an input edge on a result path */,
+            lpa_bfs_summary* summary /* nullable */);
+
+/*
  * Strongly connected components (GraphX lib.StronglyConnectedComponents /
  * GraphFrame.stronglyConnectedComponents(maxIter)) of the DIRECTED input graph.  Duplicate
  * edges change nothing; an edge with an end outside [0, V) is not an edge; a self-loop is kept
@@ -657,8 +714,9 @@ int lpa_degrees(lpa_graph* g, int32_t* deg_out);
  * ABI 14: lpa_louvain.
  * ABI 15: sparse_refreshes.
  * ABI 16: lpa_core_numbers.
- * ABI 17: fill_refreshes. */
-#define LPA_ABI_VERSION 17
+ * ABI 17: fill_refreshes.
+ * ABI 18: lpa_bfs. */
+#define LPA_ABI_VERSION 18
 int lpa_abi_version(void);
 int lpa_graph_get_info(const lpa_graph* g, lpa_graph_info* info);
 int lpa_graph_get_info_sized(const lpa_graph* g, lpa_graph_info* info, int64_t info_size);
