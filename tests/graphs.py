@@ -628,3 +628,146 @@ def bh_saturating_labels(V=65536, block=37, heavy_blocks=6, seed=3):
     lab[at + 2 * coll.size:at + 128] = heavy
     lab[at + 256:at + 256 * (heavy_blocks + 1)] = heavy
     return lab.astype(np.int32), coll.astype(np.int32), heavy
+
+
+# ---- the label exchange's gadgets (tests/exchange_ref.py, tests/test_gpu_exchange_edges.py) ----
+class Gadgets:
+    """Disjoint union of small gadgets on consecutive ids, each with a label history known in
+    closed form (input edges are undirected votes, parallel edges count): they put chosen
+    numbers of changed labels at chosen supersteps.  Every method files the ids it makes under
+    `groups[name]`.  The first gadget of every fixture is the core clique on ids 0..c-1, so
+    that label 0 is the giant label."""
+
+    def __init__(self):
+        self.n = 0
+        self.s, self.d = [], []
+        self.groups = {}
+
+    def ids(self, k, name):
+        a = np.arange(self.n, self.n + k, dtype=np.int64)
+        self.n += k
+        self.groups[name] = np.concatenate([self.groups[name], a]) if name in self.groups else a
+        return a
+
+    def edges(self, a, b, mult=1):
+        self.s.append(np.repeat(np.asarray(a, dtype=np.int64).ravel(), mult))
+        self.d.append(np.repeat(np.asarray(b, dtype=np.int64).ravel(), mult))
+
+    def clique(self, c, mult=1, name="still"):
+        """c >= 3 vertices, every pair joined: superstep 1 gives (second smallest id, smallest,
+        smallest, ...), from superstep 2 on every vertex holds the smallest id for ever."""
+        v = self.ids(c, name)
+        iu, ju = np.triu_indices(c, 1)
+        self.edges(v[iu], v[ju], mult)
+        return v
+
+    def blinkers(self, pairs, mult=1, name="blink"):
+        """Two vertices and `mult` parallel edges: they swap labels in every superstep for
+        ever (2 changes per pair per superstep, both labels distinct from every other)."""
+        v = self.ids(2 * pairs, name).reshape(pairs, 2)
+        self.edges(v[:, 0], v[:, 1], mult)
+        return v
+
+    def paths3(self, k, mult=1, name="blink"):
+        """Paths a - b - c (ids ascending): (b, a, b), (a, b, a), ... -- three changes per path
+        per superstep for ever; the middle vertex has twice the ends' degree."""
+        v = self.ids(3 * k, name).reshape(k, 3)
+        self.edges(v[:, 0], v[:, 1], mult)
+        self.edges(v[:, 1], v[:, 2], mult)
+        return v
+
+    def isolated(self, k, name="iso"):
+        return self.ids(k, name)
+
+    def still(self, k, mult=1, name="still"):
+        """k vertices (k = 3, 4 or >= 6) in cliques of 4 (k % 3 of them) and 3: each settled on
+        its smallest id from superstep 2 on."""
+        assert k in (0, 3, 4) or k >= 6, k
+        n4 = k % 3
+        for c, n in ((4, n4), (3, (k - 4 * n4) // 3)):
+            v = self.ids(c * n, name).reshape(n, c)
+            iu, ju = np.triu_indices(c, 1)
+            self.edges(v[:, iu], v[:, ju], mult)
+
+    def build(self, pad_to=0):
+        if pad_to > self.n:
+            self.isolated(pad_to - self.n)
+        s = np.concatenate(self.s) if self.s else np.zeros(0, np.int64)
+        d = np.concatenate(self.d) if self.d else np.zeros(0, np.int64)
+        return self.n, s.astype(np.int32), d.astype(np.int32), self.groups
+
+
+def blinker_field(V, pairs=0, paths=0, core=4, core_mult=1):
+    """Core clique (ids 0..core-1, all label 0 from superstep 2 on; core_mult parallel edges per
+    pair: with enough of them the blinkers dirty <= 0.5 % of a rank's arcs and the converged
+    tallies walk their frontier lists), `pairs` blinker pairs, `paths` three-vertex blinker
+    paths, isolated vertices up to V ids: from superstep 3 on exactly 2 pairs + 3 paths labels
+    change per superstep, none of them to label 0."""
+    g = Gadgets()
+    g.clique(core, mult=core_mult, name="core")
+    if pairs:
+        g.blinkers(pairs)
+    if paths:
+        g.paths3(paths)
+    assert g.n <= V, (g.n, V)
+    return g.build(pad_to=V)
+
+
+def fuse_broom(n, D, c=16, share=1, blink=0, pad_to=0, tri_mult=2, ballast=0):
+    """A timed burst of n changes.  Core clique on ids 0..c-1; ceil(n / share) triangles with
+    every edge tri_mult-fold (each settles on its smallest id T_i; 2 tri_mult > share, so the
+    leaves never outvote it); n leaves, each with one edge to a triangle's first vertex (`share`
+    leaves per triangle) and one to the hub; `blink` blinker pairs; isolated ids up to pad_to;
+    then, on the largest ids, a fuse: a path of D vertices from core vertex 0 to the hub, every
+    hop n + 1 parallel edges.  The hub repeats the fuse's end one superstep late and the leaves
+    follow the hub when its label is below their T_i: they are still from superstep 4 through
+    D + 1 and all n change in every superstep from D + 2 on (to label 0 at D + 2, D + 4, ...).
+    The fuse, the hub and core vertex 0 (n + 1 fuse votes against its c - 1 core votes) blink
+    throughout.  ballast: a settled 4-clique of that many parallel edges per pair, whose arcs
+    keep the dirty ones below 0.5 % of a rank's, so that the converged tallies walk their lists."""
+    assert 2 * tri_mult > share >= 1 and D >= 1
+    g = Gadgets()
+    core = g.clique(c, name="core")
+    if ballast:
+        g.clique(4, mult=ballast, name="ballast")
+    ntri = -(-n // share)
+    tri = g.ids(3 * ntri, "tri").reshape(ntri, 3)
+    for a, b in ((0, 1), (0, 2), (1, 2)):
+        g.edges(tri[:, a], tri[:, b], tri_mult)
+    leaves = g.ids(n, "leaves")
+    g.edges(leaves, tri[np.arange(n) // share, 0])
+    if blink:
+        g.blinkers(blink)
+    if pad_to > g.n + D + 1:
+        g.isolated(pad_to - (g.n + D + 1))
+    fuse = g.ids(D, "fuse")
+    hub = g.ids(1, "hub")
+    g.edges(leaves, np.full(n, hub[0]))
+    chain = np.concatenate([core[:1], fuse, hub])
+    g.edges(chain[:-1], chain[1:], n + 1)
+    return g.build()
+
+
+def odd_slice_field(P, slice_):
+    """V = P * slice_ vertices, none isolated, for the tight slices (P = 3, or LPA_POW2_SLICES=0):
+    in the plain order (degree descending, id ascending; degree rank k at slot k // P of rank
+    k % P) the blinking vertices hold slots 0, 63, 64 and slice_ - 1 of every rank and the
+    vertices between them are settled cliques, the core among them (ids 0..7)."""
+    assert slice_ % 64 == 0 and slice_ >= 192 and P in (2, 3, 4)
+    g = Gadgets()
+    g.clique(8, mult=4, name="core")                        # degree 28
+    if P == 3:
+        g.paths3(1, mult=100, name="top")                   # degrees 100, 200, 100: ranks 0..2
+    else:
+        g.blinkers(P // 2, mult=100, name="top")            # degree 100: ranks 0..P-1
+    g.still(63 * P - P - 8, mult=10, name="still_a")        # degrees 20 / 30: up to rank 63 P
+    g.blinkers(P, mult=10, name="mid")                      # ranks 63 P .. 65 P - 1: slots 63, 64
+    tail = 5 if P == 3 else P                               # P = 3: a path (middle: degree 2) + a pair
+    g.still(P * slice_ - 65 * P - tail, mult=2, name="still_b")   # degrees 4 / 6
+    if P == 3:
+        g.paths3(1, name="tail")
+        g.blinkers(1, name="tail")
+    else:
+        g.blinkers(P // 2, name="tail")
+    assert g.n == P * slice_
+    return g.build()
