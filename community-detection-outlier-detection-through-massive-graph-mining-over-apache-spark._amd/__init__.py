@@ -8,15 +8,15 @@ include/lpa.h); importing this package does not load it -- the first call does,
 and fails loudly if it has not been built.
 """
 from .graph import Graph, Loopback, comm_unique_id, gen_chunglu, gen_rmat, gen_sbm, run_ranks
-from .graphframe import (GraphFrame, IndexedGraph, OutlierResult, bfs, connected_components, core_number,
-                         count_paths, enumerate_paths, index_graph,
-                         k_core, label_propagation, louvain, outlier_scores, page_rank,
-                         parallel_personalized_page_rank, shortest_paths, strongly_connected_components,
-                         triangle_count)
+from .graphframe import (GraphFrame, IndexedGraph, MotifTerm, OutlierResult, ParsedMotif, bfs, connected_components,
+                         core_number, count_paths, enumerate_paths, find, index_graph,
+                         k_core, label_propagation, louvain, motif_count, outlier_scores, page_rank,
+                         parallel_personalized_page_rank, parse_motif, plan_motif, shortest_paths,
+                         strongly_connected_components, triangle_count)
 from . import ingest
 
 __all__ = ["Graph", "Loopback", "run_ranks", "GraphFrame", "IndexedGraph", "OutlierResult", "comm_unique_id", "gen_chunglu", "gen_rmat",
            "gen_sbm", "bfs", "connected_components", "core_number", "count_paths", "enumerate_paths", "index_graph", "ingest", "k_core",
            "label_propagation", "louvain",
            "outlier_scores", "page_rank", "parallel_personalized_page_rank", "shortest_paths", "strongly_connected_components",
-           "triangle_count"]
+           "triangle_count", "find", "motif_count", "parse_motif", "plan_motif", "MotifTerm", "ParsedMotif"]

@@ -137,6 +137,20 @@ class LpaBfsSummary(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LpaMotifTerm(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("src_var", "dst_var", "negated", "want_edge")]
+
+
+class LpaMotifSummary(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int64) for k in ("rows", "edges", "self_loops", "steps", "peak_rows", "overflow_step",
+                                              "overflow_rows")] + [("table_rows", ctypes.c_int64 * 16)]
+
+    def to_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "table_rows"}
+        d["table_rows"] = list(self.table_rows[: max(int(self.steps), 0)])
+        return d
+
+
 class LpaSccSummary(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in ("n_components", "n_singletons", "largest_size", "largest_id",
                                               "rounds", "trimmed", "unresolved")]
@@ -219,6 +233,12 @@ SIGNATURES = {
     "lpa_shortest_paths": (ctypes.c_int, [_vp, _i32p, ctypes.c_int32, _vp, ctypes.c_int32,
                                           ctypes.POINTER(LpaSpSummary)]),
     "lpa_bfs": (ctypes.c_int, [_vp, _u8p, _u8p, _u8p, ctypes.c_int32, _i32p, _u8p, ctypes.POINTER(LpaBfsSummary)]),
+    "lpa_motif": (ctypes.c_int, [_vp, ctypes.c_int32, _u8p, ctypes.POINTER(LpaMotifTerm), ctypes.c_int32,
+                                 ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(_vp),
+                                 ctypes.POINTER(LpaMotifSummary)]),
+    "lpa_motif_vertex_column": (ctypes.c_int, [_vp, ctypes.c_int32, _i32p]),
+    "lpa_motif_edge_column": (ctypes.c_int, [_vp, ctypes.c_int32, _i64p]),
+    "lpa_motif_result_destroy": (None, [_vp]),
     "lpa_strongly_connected_components": (ctypes.c_int, [_vp, ctypes.c_int32, _vp, ctypes.c_int32, _vp,
                                                          ctypes.POINTER(LpaSccSummary)]),
     "lpa_louvain": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int32, _vp,
@@ -245,6 +265,12 @@ SIGNATURES = {
                                    ctypes.c_uint64, _vp, _vp, ctypes.c_int32, _vp]),
     "lpa_gen_chunglu": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_uint64, _vp, _vp, ctypes.c_int32, _vp]),
+}
+
+# the symbols whose return type is none of int, void and const char* (SIGNATURES is held to
+# exactly the header's symbols of those three types by tests/test_host_api.py)
+WIDE_SIGNATURES = {
+    "lpa_motif_rows": (ctypes.c_int64, [_vp]),
 }
 
 _lib = None
@@ -275,7 +301,7 @@ def load():
         pass
     # LPA_LIB_PATH: a diagnostic build of the same library (csrc/Makefile `trace`)
     lib = ctypes.CDLL(os.environ.get("LPA_LIB_PATH") or LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(WIDE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -23,6 +23,15 @@
 // The two families keep their own sentinel, pass count and scan type: at V = 2^8, 2^16 and
 // 2^24 bits_for(V) takes one more pass a half than bits_for(V - 1).
 //
+// Edge rows (edge_lists: lpa_motif.hip): every in-range edge row of the MULTIGRAPH, self-loops and
+// duplicates kept, as out-lists and in-lists that carry the row's index in the input.
+//   keys     (src << 32 | dst), anything else (V << 32 | V); the payload is the edge row
+//   sort     radix sort with the payload over both halves.  LSD and stable, the payload in
+//            input order: rows of one (src, dst) stay in edge-row order and no digit is spent
+//            on the row.  oo[] by binary search (oo[V] = the valid rows), ocol[] the low half,
+//            oeid[] the payload
+//   in       the halves swapped, sorted again by the new high half alone: (dst, src, row)
+//
 // Also here, once: the bounds binary search, the low half as col[], the pull-form row lists
 // (form_lists) and the component sizes and summary of lpa_cc.hip and lpa_scc.hip.
 #include "lpa_device.h"
@@ -88,6 +97,29 @@ __global__ __launch_bounds__(256) void k_edge_mark(const u64* __restrict__ keys,
   GRID_STRIDE(i, m) {
     const u64 k = keys[i];
     first[i] = ((u32)(k >> 32) != (u32)k && (i == 0 || keys[i - 1] != k)) ? 1 : 0;
+  }
+}
+
+// ---- edge rows (the multigraph) ----
+// keys[i] = (src << 32 | dst) of an in-range edge row, loops and duplicates kept; anything else
+// gets (V << 32 | V).  vals[i] = i, the payload the sort carries
+__global__ __launch_bounds__(256) void k_edge_row_keys(const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
+                                                       int64_t m, u32 V, u64* __restrict__ keys,
+                                                       u64* __restrict__ vals) {
+  GRID_STRIDE(i, m) {
+    const u32 a = (u32)__builtin_nontemporal_load(src + i), b = (u32)__builtin_nontemporal_load(dst + i);
+    keys[i] = a < V && b < V ? ((u64)a << 32) | b : ((u64)V << 32) | V;
+    vals[i] = (u64)i;
+  }
+}
+
+// the halves of every key swapped in place, the payload copied beside it
+__global__ __launch_bounds__(256) void k_edge_row_swap(u64* __restrict__ keys, const u64* __restrict__ vals, int64_t m,
+                                                       u64* __restrict__ ivals) {
+  GRID_STRIDE(i, m) {
+    const u64 k = keys[i];
+    keys[i] = (k << 32) | (k >> 32);
+    ivals[i] = vals[i];
   }
 }
 
@@ -246,6 +278,51 @@ int arcs_lists(lpa_graph* g, Tmp& tmp, ArcLists* a) {
     LPA_HIP(hipMemsetAsync(a->oo, 0, sizeof(int64_t) * (size_t)(V + 1), s));
     LPA_HIP(hipMemsetAsync(a->io, 0, sizeof(int64_t) * (size_t)(V + 1), s));
   }
+  return LPA_OK;
+}
+
+int edge_lists(lpa_graph* g, Tmp& tmp, bool want_in, EdgeLists* l) {
+  hipStream_t s = g->stream;
+  const int64_t V = g->V, m = g->m;
+  l->mv = 0;
+  LPA_TRY(tmp.get(&l->oo, V + 1));
+  if (want_in) LPA_TRY(tmp.get(&l->io, V + 1));
+  if (m == 0) {
+    LPA_HIP(hipMemsetAsync(l->oo, 0, sizeof(int64_t) * (size_t)(V + 1), s));
+    if (want_in) LPA_HIP(hipMemsetAsync(l->io, 0, sizeof(int64_t) * (size_t)(V + 1), s));
+    return LPA_OK;
+  }
+  const HalfShifts sh(bits_for((uint64_t)V));   // the halves hold values up to V (a dropped edge)
+  u64 *keys = nullptr, *vals = nullptr, *tk = nullptr, *tv = nullptr;
+  LPA_TRY(tmp.get(&keys, m));
+  LPA_TRY(tmp.get(&vals, m));
+  LPA_TRY(tmp.get(&tk, m));
+  LPA_TRY(tmp.get(&tv, m));
+  LPA_TRY(tmp.get(&l->ocol, m));
+  hipLaunchKernelGGL(k_edge_row_keys, dim3(grid_for(m)), dim3(256), 0, s, g->e_src, g->e_dst, m, (u32)V, keys, vals);
+  LPA_HIP(hipGetLastError());
+  // stable, the payload in input order: equal (src, dst) keep their edge rows ascending
+  LPA_TRY(radix_sort_u64_kv(keys, vals, tk, tv, m, sh.both(), 2 * sh.ns, s));
+  LPA_TRY(key_bounds(keys, m, V, true, l->oo, s));   // oo[V] = the valid rows: a dropped edge sorts behind them
+  LPA_TRY(key_col(keys, m, l->ocol, s));
+  l->oeid = reinterpret_cast<int64_t*>(vals);
+  if (want_in) {
+    u64* ivals = nullptr;
+    LPA_TRY(tmp.get(&ivals, m));
+    LPA_TRY(tmp.get(&l->icol, m));
+    hipLaunchKernelGGL(k_edge_row_swap, dim3(grid_for(m)), dim3(256), 0, s, keys, vals, m, ivals);
+    LPA_HIP(hipGetLastError());
+    // by the new high half alone: (src, edge row) stays ascending inside a destination
+    LPA_TRY(radix_sort_u64_kv(keys, ivals, tk, tv, m, sh.hi(), sh.ns, s));
+    LPA_TRY(key_bounds(keys, m, V, true, l->io, s));
+    LPA_TRY(key_col(keys, m, l->icol, s));
+    l->ieid = reinterpret_cast<int64_t*>(ivals);
+  }
+  tmp.drop(tv);
+  tmp.drop(tk);
+  tmp.drop(keys);
+  LPA_HIP(hipMemcpyAsync(&l->mv, l->oo + V, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  LPA_HIP(hipStreamSynchronize(s));
   return LPA_OK;
 }
 

@@ -816,6 +816,125 @@ int lpa_bfs(lpa_graph* g, const uint8_t* from_mask, const uint8_t* to_mask, cons
   return bfs(g, from_mask, to_mask, edge_keep, max_len, level_out, on_edge_out, summary);
 }
 
+int lpa_motif(lpa_graph* g, int32_t n_vars, const uint8_t* var_out, const lpa_motif_term* terms, int32_t n_terms,
+              int64_t max_rows, int32_t count_only, lpa_motif_result** result_out, lpa_motif_summary* summary) {
+  if (result_out) *result_out = nullptr;
+  if (!g) {
+    set_error("null handle");
+    return LPA_EINVAL;
+  }
+  if (n_vars < 1 || n_vars > 32) {
+    set_error("lpa_motif: n_vars must be in [1, 32], got %d", n_vars);
+    return LPA_EINVAL;
+  }
+  if (n_terms < 1 || n_terms > 16 || !terms) {
+    set_error("lpa_motif: n_terms must be in [1, 16] with a term array, got %d", n_terms);
+    return LPA_EINVAL;
+  }
+  if ((count_only != 0) != (result_out == nullptr)) {
+    set_error("lpa_motif: result_out must be null exactly when count_only is set");
+    return LPA_EINVAL;
+  }
+  bool bound[32] = {};
+  int n_pos = 0, n_neg = 0;
+  for (int32_t t = 0; t < n_terms; ++t) {
+    const int32_t a = terms[t].src_var, b = terms[t].dst_var;
+    if (a < 0 || a >= n_vars || b < 0 || b >= n_vars) {
+      set_error("lpa_motif: term %d names variable %d, outside [0, %d)", t, a < 0 || a >= n_vars ? a : b, n_vars);
+      return LPA_EINVAL;
+    }
+    if (terms[t].negated) {
+      if (t == 0) {
+        set_error("lpa_motif: term 0 is negated; the first term seeds the table");
+        return LPA_EINVAL;
+      }
+      if (!bound[a] || !bound[b]) {
+        set_error("lpa_motif: negated term %d reads variable %d before a positive term binds it", t,
+                  bound[a] ? b : a);
+        return LPA_EINVAL;
+      }
+      ++n_neg;
+    } else {
+      if (t > 0 && !bound[a] && !bound[b]) {
+        set_error("lpa_motif: term %d shares no variable with the positive terms before it", t);
+        return LPA_EINVAL;
+      }
+      bound[a] = bound[b] = true;
+      ++n_pos;
+    }
+  }
+  if (n_pos > 8 || n_neg > 8) {
+    set_error("lpa_motif: at most 8 positive and 8 negated terms, got %d and %d", n_pos, n_neg);
+    return LPA_EINVAL;
+  }
+  for (int32_t v = 0; var_out && v < n_vars; ++v)
+    if (var_out[v] != 0 && !bound[v]) {
+      set_error("lpa_motif: var_out names variable %d, which no positive term binds", v);
+      return LPA_EINVAL;
+    }
+  if (g->m > 0 && !g->e_src) {
+    set_error("lpa_motif of a distributed job runs on rank 0 (the rank that keeps the edge list)");
+    return LPA_EINVAL;
+  }
+  lpa_motif_result* res = nullptr;
+  if (!count_only) {
+    res = new (std::nothrow) lpa_motif_result();
+    if (!res) {
+      set_error("lpa_motif: no host memory for the result object");
+      return LPA_ENOMEM;
+    }
+    res->device = g->device;
+    for (int32_t v = 0; var_out && v < n_vars; ++v) res->has_v[v] = var_out[v] != 0;
+    for (int32_t t = 0; t < n_terms; ++t) res->has_e[t] = !terms[t].negated && terms[t].want_edge != 0;
+  }
+  int rc = LPA_OK;
+  hipError_t e = hipSetDevice(g->device);
+  if (e != hipSuccess) {
+    set_error("hipSetDevice(%d) failed: %s", g->device, hipGetErrorString(e));
+    rc = LPA_EHIP;
+  } else {
+    rc = motif(g, n_vars, var_out, terms, n_terms, max_rows, count_only, res, summary);
+  }
+  if (rc != LPA_OK) {
+    lpa_motif_result_destroy(res);
+    return rc;
+  }
+  if (result_out) *result_out = res;
+  return LPA_OK;
+}
+
+int64_t lpa_motif_rows(const lpa_motif_result* r) { return r ? r->rows : 0; }
+
+int lpa_motif_vertex_column(const lpa_motif_result* r, int32_t var, int32_t* out) {
+  if (!r || var < 0 || var >= 32 || !r->has_v[var] || (r->rows > 0 && !out)) {
+    set_error("lpa_motif_vertex_column: the result has no column for variable %d", var);
+    return LPA_EINVAL;
+  }
+  if (r->rows > 0) {
+    LPA_HIP(hipSetDevice(r->device));
+    LPA_HIP(hipMemcpy(out, r->vcol[var], sizeof(int32_t) * (size_t)r->rows, hipMemcpyDeviceToHost));
+  }
+  return LPA_OK;
+}
+
+int lpa_motif_edge_column(const lpa_motif_result* r, int32_t term, int64_t* out) {
+  if (!r || term < 0 || term >= 16 || !r->has_e[term] || (r->rows > 0 && !out)) {
+    set_error("lpa_motif_edge_column: the result has no edge column for term %d", term);
+    return LPA_EINVAL;
+  }
+  if (r->rows > 0) {
+    LPA_HIP(hipSetDevice(r->device));
+    LPA_HIP(hipMemcpy(out, r->ecol[term], sizeof(int64_t) * (size_t)r->rows, hipMemcpyDeviceToHost));
+  }
+  return LPA_OK;
+}
+
+void lpa_motif_result_destroy(lpa_motif_result* r) {
+  if (!r) return;
+  if (r->slab && hipSetDevice(r->device) == hipSuccess) (void)hipFree(r->slab);
+  delete r;
+}
+
 int lpa_strongly_connected_components(lpa_graph* g, int32_t max_iter, int32_t* comp_out, int32_t out_is_device,
                                       int64_t* size_out, lpa_scc_summary* summary) {
   if (!g) {

@@ -546,6 +546,19 @@ struct lpa_graph {
   hipEvent_t bin_ev[LPA_STATS_MAX_ITERS * lpa::kBinEvents] = {};
 };
 
+// The final table of an lpa_motif call: one plain device allocation (hipMalloc on `device`, not
+// the handle's stream-ordered pool), a column per variable of var_out and per wanted edge;
+// independent of the handle
+struct lpa_motif_result {
+  int64_t rows = 0;
+  int32_t* vcol[32] = {};   // device, by variable; null: not in the result
+  int64_t* ecol[16] = {};   // device, by term; null: not in the result
+  bool has_v[32] = {};      // the result has the column (rows == 0: without memory)
+  bool has_e[16] = {};
+  void* slab = nullptr;
+  int device = 0;
+};
+
 namespace lpa {
 
 // allocation helpers (track bytes on the handle)
@@ -713,6 +726,17 @@ struct ArcLists {
 };
 int arcs_count(lpa_graph* g, Tmp& tmp, uint8_t* loop, ArcLists* a, const uint8_t* keep = nullptr);
 int arcs_lists(lpa_graph* g, Tmp& tmp, ArcLists* a);
+// Every in-range edge row of the multigraph (self-loops and duplicates kept) with its index in the
+// input: the out-lists sorted by (src, dst, edge row), the in-lists (want_in) by (dst, src, edge
+// row).  mv = the valid rows (= oo[V]), read on the host: one synchronisation.  m == 0: the
+// offsets zeroed and no other array
+struct EdgeLists {
+  int64_t mv = 0;
+  int64_t *oo = nullptr, *io = nullptr;         // [V + 1] offsets
+  int32_t *ocol = nullptr, *icol = nullptr;     // [mv] the other end of every row
+  int64_t *oeid = nullptr, *ieid = nullptr;     // [mv] its edge row
+};
+int edge_lists(lpa_graph* g, Tmp& tmp, bool want_in, EdgeLists* l);
 // The rows that take the wave form (short_max < L <= wave_max; L = off[v + 1] - off[v]) in
 // (*lists)[0, n_rows[0]) and the block form (longer) in (*lists)[V, V + n_rows[1]), ascending.
 // n_rows is host memory, valid after the caller's next synchronisation of the stream
@@ -757,6 +781,11 @@ int shortest_paths(lpa_graph* g, const int32_t* landmarks, int32_t n_landmarks, 
 // are checked by the caller
 int bfs(lpa_graph* g, const uint8_t* from_mask, const uint8_t* to_mask, const uint8_t* edge_keep, int32_t max_len,
         int32_t* level_out, uint8_t* on_edge_out, lpa_bfs_summary* summary);
+
+// motif finding over the directed multigraph (lpa_motif.hip); the arguments are checked by the
+// caller, res (null iff count_only) comes in empty
+int motif(lpa_graph* g, int32_t n_vars, const uint8_t* var_out, const lpa_motif_term* terms, int32_t n_terms,
+          int64_t max_rows, int32_t count_only, lpa_motif_result* res, lpa_motif_summary* summary);
 
 // strongly connected components of the directed graph, GraphX's rounds (lpa_scc.hip)
 int strongly_connected_components(lpa_graph* g, int32_t max_iter, int32_t* comp_out, int32_t out_is_device,

@@ -579,6 +579,69 @@ class Graph:
         res = (int(summ.length), level, np.flatnonzero(on_edge.view(np.bool_)).astype(np.int64, copy=False))
         return res + (summ.to_dict(),) if stats else res
 
+    # -- motif finding ----------------------------------------------------------------
+    def motif(self, n_vars: int, terms, var_out=None, max_rows=None, count_only: bool = False, stats: bool = False):
+        """Motif finding over the directed input multigraph (lpa_motif; GraphFrames
+        ``GraphFrame.find``) for a parsed pattern: ``n_vars`` vertex variables and ``terms``, a
+        sequence of ``(src_var, dst_var, negated, want_edge)`` run in that order.  The first term
+        is positive; a later positive term shares a variable with the ones before it; a negated
+        term reads bound variables only.  A row is one assignment of vertices to the bound
+        variables and of input edge rows to the positive terms: duplicate edges multiply rows,
+        variables need not differ, self-loops are edges.  ``var_out`` lists the variables whose
+        columns are wanted (``None``: every bound one).  Returns ``(vertex_cols, edge_cols)``:
+        ``vertex_cols[var]`` int32 dense ids, ``edge_cols[term]`` int64 input edge rows for the
+        terms with ``want_edge``, all of one length, in the library's deterministic row order;
+        with ``count_only`` the exact row count alone, nothing materialised.  ``max_rows``
+        (``None`` or <= 0: no cap) bounds every table, intermediate or final: a step that needs
+        more raises ``ValueError`` naming the step and the rows it needed.  ``stats=True`` adds
+        ``summary``, a dict of rows, edges, self_loops, steps, peak_rows, overflow_step,
+        overflow_rows, table_rows.  The labels and the LPA state are not touched."""
+        tl = [tuple(int(x) for x in t) for t in terms]
+        if any(len(t) != 4 for t in tl):
+            raise ValueError("a motif term is (src_var, dst_var, negated, want_edge)")
+        n_vars = int(n_vars)
+        arr = (_lib.LpaMotifTerm * max(len(tl), 1))()
+        bound = set()
+        for i, (a, b, neg, we) in enumerate(tl):
+            arr[i] = _lib.LpaMotifTerm(a, b, neg, we)
+            if not neg:
+                bound.update((a, b))
+        if var_out is None:
+            var_out = sorted(v for v in bound if 0 <= v < n_vars)
+        var_out = [int(v) for v in var_out]
+        if any(v < 0 or v >= n_vars for v in var_out):
+            raise ValueError(f"var_out names a variable outside [0, {n_vars})")
+        mask = np.zeros(max(n_vars, 1), dtype=np.uint8)
+        mask[var_out] = 1
+        cap = 0 if max_rows is None else int(max_rows)
+        summ = _lib.LpaMotifSummary()
+        res = ctypes.c_void_p()
+        lib = self._lib
+        try:
+            rc = lib.lpa_motif(self._handle(), n_vars, mask.ctypes.data_as(_lib._u8p), arr, len(tl), cap,
+                               1 if count_only else 0, None if count_only else ctypes.byref(res), ctypes.byref(summ))
+            if rc == _lib.LPA_EOVERFLOW and summ.overflow_step >= 0:
+                raise ValueError(f"motif: step {summ.overflow_step} needs {summ.overflow_rows} rows, "
+                                 f"more than max_rows = {cap}")
+            _lib.check(rc)
+            if count_only:
+                out = int(summ.rows)
+                return (out, summ.to_dict()) if stats else out
+            rows = int(lib.lpa_motif_rows(res))
+            vcols, ecols = {}, {}
+            for v in var_out:
+                col = np.empty(rows, dtype=np.int32)
+                _lib.check(lib.lpa_motif_vertex_column(res, v, col.ctypes.data_as(_lib._i32p)))
+                vcols[v] = col
+            for i, (_, _, neg, we) in enumerate(tl):
+                if we and not neg:
+                    col = np.empty(rows, dtype=np.int64)
+                    _lib.check(lib.lpa_motif_edge_column(res, i, col.ctypes.data_as(_lib._i64p)))
+                    ecols[i] = col
+            return (vcols, ecols, summ.to_dict()) if stats else (vcols, ecols)
+        finally:
+            lib.lpa_motif_result_destroy(res)
+
     # -- strongly connected components ------------------------------------------------
     def strongly_connected_components(self, max_iter=None, out=None, sizes: bool = False):
         """Strongly connected components of the directed input graph

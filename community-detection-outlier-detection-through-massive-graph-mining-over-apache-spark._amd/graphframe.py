@@ -25,6 +25,7 @@ Ties are broken by the smallest label.
 """
 from __future__ import annotations
 
+import re
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -205,6 +206,182 @@ def enumerate_paths(level, src, dst, edge_index, length):
         verts = [c[rep] for c in verts] + [sd[pos]]
         edges = [c[rep] for c in edges] + [se[pos]]
     return np.stack(verts, axis=1).astype(np.int32), np.stack(edges, axis=1)
+
+
+MOTIF_MAX_TERMS = 8   # positive terms, and negated terms, of one pattern
+
+_MOTIF_EDGE = re.compile(r"^(!?)\(([A-Za-z0-9_]*)\)-\[([A-Za-z0-9_]*)\]->\(([A-Za-z0-9_]*)\)$")
+_MOTIF_VERTEX = re.compile(r"^\(([A-Za-z0-9_]+)\)$")
+
+
+@dataclass(frozen=True)
+class MotifTerm:
+    """One edge term of a motif: ``src`` / ``dst`` / ``edge`` are the names (``None``:
+    anonymous), ``src_var`` / ``dst_var`` the vertex variables (an anonymous vertex is a fresh
+    one).  ``str(term)`` is the term as GraphFrames writes it."""
+    src: str | None
+    dst: str | None
+    edge: str | None
+    negated: bool
+    src_var: int
+    dst_var: int
+
+    def __str__(self):
+        return "{}({})-[{}]->({})".format("!" if self.negated else "", self.src or "", self.edge or "",
+                                          self.dst or "")
+
+
+@dataclass(frozen=True)
+class ParsedMotif:
+    """A parsed pattern: its edge ``terms`` in pattern order, the ``lone`` vertex terms' names,
+    ``names`` = the named elements as ``(name, "v" | "e")`` in order of first appearance,
+    ``var_names[var]`` the name of a vertex variable (``None``: anonymous)."""
+    terms: tuple
+    lone: tuple
+    names: tuple
+    var_names: tuple
+
+    @property
+    def n_vars(self) -> int:
+        return len(self.var_names)
+
+
+def parse_motif(pattern) -> ParsedMotif:
+    """Parse a GraphFrames motif: terms separated by ``;``, whitespace free; a term is
+    ``(a)-[e]->(b)``, with ``!`` in front when negated, or a lone vertex ``(a)``; ``()`` and
+    ``[]`` are anonymous.  Every named vertex is one variable wherever it appears, every ``()``
+    a fresh one, every positive term has its own edge variable.  A pure host function: raises
+    ``ValueError`` naming the offending term for every pattern this implementation refuses
+    (see ``GraphFrame.find``)."""
+    if not isinstance(pattern, str):
+        raise TypeError(f"pattern must be a str, got {type(pattern).__name__}")
+    text = "".join(pattern.split())
+    if not text:
+        raise ValueError("find: the pattern is empty")
+    terms, lone, var_names = [], [], []
+    kind, var_of, edge_term = {}, {}, {}
+
+    def name_of(name, k, term):
+        if kind.setdefault(name, k) != k:
+            raise ValueError(f"find: term '{term}': the name '{name}' is used both for a vertex and for an edge")
+
+    def vertex(name, term):
+        if not name:
+            var_names.append(None)
+            return len(var_names) - 1
+        name_of(name, "v", term)
+        if name not in var_of:
+            var_of[name] = len(var_names)
+            var_names.append(name)
+        return var_of[name]
+
+    for raw in text.split(";"):
+        mv = _MOTIF_VERTEX.match(raw)
+        if mv:
+            name_of(mv.group(1), "v", raw)
+            lone.append(mv.group(1))
+            continue
+        me = _MOTIF_EDGE.match(raw)
+        if not me:
+            raise ValueError(f"find: the term '{raw}' does not parse; a term is (a)-[e]->(b), !(a)-[]->(b) or (a)")
+        neg, a, e, b = me.group(1) == "!", me.group(2), me.group(3), me.group(4)
+        if neg and e:
+            raise ValueError(f"find: term '{raw}': a negated term cannot name its edge")
+        if neg and (not a or not b):
+            raise ValueError(f"find: term '{raw}': a negated term cannot have an anonymous vertex")
+        if e:
+            name_of(e, "e", raw)
+            if e in edge_term:
+                raise ValueError(f"find: term '{raw}': the edge name '{e}' is already used by '{edge_term[e]}'")
+            edge_term[e] = raw
+        if neg:   # a negated term binds nothing: its variables are looked up once every term is read
+            terms.append((a, b, None, True, raw))
+        else:
+            terms.append(MotifTerm(a or None, b or None, e or None, False, vertex(a, raw), vertex(b, raw)))
+    for i, t in enumerate(terms):
+        if isinstance(t, tuple):
+            a, b, _, _, raw = t
+            for nm in (a, b):
+                name_of(nm, "v", raw)
+                if nm not in var_of:
+                    raise ValueError(f"find: term '{raw}': no positive term binds the vertex '{nm}'")
+            terms[i] = MotifTerm(a, b, None, True, var_of[a], var_of[b])
+    # the named elements in order of first appearance in the pattern
+    order = []
+    for raw in text.split(";"):
+        for nm in re.findall(r"[A-Za-z0-9_]+", raw):
+            if (nm, kind[nm]) not in order:
+                order.append((nm, kind[nm]))
+    pos = [t for t in terms if not t.negated]
+    n_neg = len(terms) - len(pos)
+    if len(pos) > MOTIF_MAX_TERMS or n_neg > MOTIF_MAX_TERMS:
+        raise ValueError(f"find: the pattern '{text}' has {len(pos)} positive and {n_neg} negated terms, "
+                         f"more than {MOTIF_MAX_TERMS} of a kind")
+    for nm in lone:
+        if nm not in var_of and not (len(lone) == 1 and not terms):
+            raise ValueError(f"find: the lone term '({nm})' occurs in no edge term; a cross-join is not supported")
+    if not order:
+        raise ValueError(f"find: the pattern '{text}' names nothing")
+    # the positive terms form one connected pattern
+    if pos:
+        seen, todo = {pos[0].src_var, pos[0].dst_var}, list(pos[1:])
+        while todo:
+            nxt = [t for t in todo if t.src_var not in seen and t.dst_var not in seen]
+            if len(nxt) == len(todo):
+                raise ValueError(f"find: term '{todo[0]}' is not connected to '{pos[0]}'; "
+                                 "a cross-join of disconnected patterns is not supported")
+            for t in todo:
+                if t not in nxt:
+                    seen.update((t.src_var, t.dst_var))
+            todo = nxt
+    return ParsedMotif(tuple(terms), tuple(lone), tuple(order), tuple(var_names))
+
+
+def plan_motif(parsed: ParsedMotif) -> list:
+    """The execution order of a parsed pattern's edge terms, as indices into ``parsed.terms``.
+    The first positive term is the one that binds the most named variables; then always a term
+    with both ends bound (a close: it can only keep or drop rows per parallel edge, and never
+    needs a new column) before an extend; ties go to pattern order.  A negated term runs right
+    after the positive term that binds the last of its variables, so it prunes the table
+    before the next extension multiplies it."""
+    terms = parsed.terms
+    pos = [i for i, t in enumerate(terms) if not t.negated]
+    neg = [i for i, t in enumerate(terms) if t.negated]
+    if not pos:
+        return []
+
+    def named(i):
+        t = terms[i]
+        return len({v for v in (t.src_var, t.dst_var) if parsed.var_names[v] is not None})
+
+    first = max(pos, key=lambda i: (named(i), -i))
+    plan, bound, left = [], set(), [i for i in pos if i != first]
+
+    def run(i):
+        plan.append(i)
+        bound.update((terms[i].src_var, terms[i].dst_var))
+        for j in list(neg):
+            if terms[j].src_var in bound and terms[j].dst_var in bound:
+                plan.append(j)
+                neg.remove(j)
+
+    run(first)
+    while left:
+        close = [i for i in left if terms[i].src_var in bound and terms[i].dst_var in bound]
+        ext = [i for i in left if terms[i].src_var in bound or terms[i].dst_var in bound]
+        nxt = (close or ext)[0]   # parse_motif has checked that the pattern is connected
+        left.remove(nxt)
+        run(nxt)
+    return plan
+
+
+def _check_max_rows(maxRows):
+    if maxRows is None:
+        return
+    if not isinstance(maxRows, (int, np.integer)) or isinstance(maxRows, (bool, np.bool_)):
+        raise TypeError(f"maxRows must be an int or None, got {type(maxRows).__name__}")
+    if maxRows <= 0:
+        raise ValueError(f"maxRows must be greater than 0, got {maxRows}")
 
 
 def _check_cc_algorithm(algorithm):
@@ -621,6 +798,88 @@ class GraphFrame:
         out.attrs["length"], out.attrs["paths"] = int(length), int(len(out))
         return out
 
+    def _first_rows(self) -> np.ndarray:
+        """The row of the vertex frame that stands for every dense id: the first one."""
+        ig = self._indexed()
+        pos = np.searchsorted(ig.ids, self._v[ID].to_numpy())
+        rep = np.zeros(ig.num_vertices, dtype=np.int64)
+        rep[pos[::-1]] = np.arange(len(self._v) - 1, -1, -1)
+        return rep
+
+    def _motif_terms(self, parsed: ParsedMotif, plan, want_edges: bool):
+        return [(parsed.terms[i].src_var, parsed.terms[i].dst_var, int(parsed.terms[i].negated),
+                 int(want_edges and parsed.terms[i].edge is not None)) for i in plan]
+
+    def find(self, pattern: str, *, maxRows=None) -> pd.DataFrame:
+        """``GraphFrame.find(pattern)`` (GraphFrames motif finding): structural pattern matching
+        such as ``g.find("(a)-[e]->(b); (b)-[e2]->(a)")``.
+
+        A pattern is terms separated by ``;``.  A term is ``(a)-[e]->(b)``, negated with a
+        leading ``!``, or a lone vertex ``(a)``; ``()`` and ``[]`` are anonymous.  A named
+        vertex is one variable wherever it appears, every ``()`` a fresh one, every positive
+        term has its own edge.  A row is one assignment of vertices to the vertex variables and
+        of **rows of the edge frame** to the positive terms' edges such that every edge goes
+        from its ``src`` variable's vertex to its ``dst`` variable's; a negated term keeps the
+        rows for which no edge row goes from its first vertex to its second.  There is one row
+        per assignment of all variables, the anonymous ones included, which are then dropped:
+        duplicate edges and anonymous elements multiply rows as a chain of joins does, rows are
+        never deduplicated, and variables need not be distinct (in
+        ``"(a)-[e]->(b); (b)-[e2]->(a)"`` a self-loop matches with ``a == b``; filter
+        afterwards, ``m[m["a"]["id"] != m["b"]["id"]]``).  Edges whose ``src`` or ``dst`` is no
+        vertex id are no edges.
+
+        Refused with ``ValueError``, before any device work: an empty pattern or a term that
+        does not parse; a name used for a vertex and an edge; an edge name in two terms; a
+        named edge in a negated term; a negated term with an anonymous vertex or with a vertex
+        no positive term binds; positive terms that are not one connected pattern (GraphFrames
+        would cross-join); a lone ``(a)`` that occurs in no edge term unless it is the whole
+        pattern; a pattern that names nothing; more than 8 positive or 8 negated terms.
+
+        The result has two-level columns, as ``bfs``: the top level is the named elements in
+        order of first appearance in the pattern, the second every vertex column (vertex names)
+        or every edge column (edge names).  Where an id repeats in the vertex frame its first
+        row stands for the vertex.  Rows are sorted by the tuple of (dense vertex id or edge
+        row) in column order.  ``.attrs["rows"]`` is the row count, ``.attrs["plan"]`` the terms
+        in the order they ran.  An empty result keeps the columns.  ``(a)`` alone returns the
+        vertices under ``a`` without touching the GPU.  ``maxRows`` bounds every table,
+        intermediate ones too: a step that needs more raises ``ValueError``."""
+        parsed = parse_motif(pattern)
+        _check_max_rows(maxRows)
+        plan = plan_motif(parsed)
+        v, e = self._v, self._e
+        ig = self._indexed()
+        rep = self._first_rows()
+        if not plan:
+            rows = v.iloc[rep].reset_index(drop=True)
+            out = pd.concat([rows], axis=1, keys=[parsed.lone[0]])
+            out.attrs["rows"], out.attrs["plan"] = int(len(out)), []
+            return out
+        terms = self._motif_terms(parsed, plan, True)
+        var_of = {nm: i for i, nm in enumerate(parsed.var_names) if nm is not None}
+        term_of = {parsed.terms[i].edge: k for k, i in enumerate(plan) if parsed.terms[i].edge is not None}
+        vcols, ecols = self._gpu_graph().motif(parsed.n_vars, terms, var_out=sorted(var_of.values()),
+                                               max_rows=maxRows)
+        cols = [vcols[var_of[nm]] if k == "v" else ecols[term_of[nm]] for nm, k in parsed.names]
+        order = np.lexsort(tuple(c for c in reversed(cols)))
+        in_row = np.flatnonzero(ig.kept)   # edge index of the dense graph -> row of the edge frame
+        parts = []
+        for (nm, k), c in zip(parsed.names, cols):
+            c = c[order]
+            parts.append((v.iloc[rep[c]] if k == "v" else e.iloc[in_row[c]]).reset_index(drop=True))
+        out = pd.concat(parts, axis=1, keys=[nm for nm, _ in parsed.names])
+        out.attrs["rows"], out.attrs["plan"] = int(len(out)), [str(parsed.terms[i]) for i in plan]
+        return out
+
+    def motifCount(self, pattern: str) -> int:
+        """The exact number of rows ``find(pattern)`` would return, with nothing materialised:
+        every step runs, the last table is only counted.  This package's own addition
+        (GraphFrames has ``find(pattern).count()``, which builds the rows first)."""
+        parsed = parse_motif(pattern)
+        plan = plan_motif(parsed)
+        if not plan:
+            return int(self._indexed().num_vertices)
+        return self._gpu_graph().motif(parsed.n_vars, self._motif_terms(parsed, plan, False), count_only=True)
+
     def inDegrees(self) -> pd.DataFrame:
         """Vertices + ``inDegree`` (int64): the kept edges ending at each vertex, duplicates
         counted.  Every vertex has a row, with 0 where GraphFrames' property leaves the
@@ -765,6 +1024,26 @@ def bfs(vertices: pd.DataFrame, edges: pd.DataFrame, fromExpr, toExpr, edgeFilte
     gf = GraphFrame(vertices, edges, device=device)
     try:
         return gf.bfs(fromExpr, toExpr, edgeFilter, maxPathLength, maxPaths=maxPaths)
+    finally:
+        gf.close()
+
+
+def find(vertices: pd.DataFrame, edges: pd.DataFrame, pattern: str, *, maxRows=None, device: int = 0) -> pd.DataFrame:
+    """Function form of ``GraphFrame(vertices, edges).find(pattern, maxRows=maxRows)``."""
+    parse_motif(pattern)
+    gf = GraphFrame(vertices, edges, device=device)
+    try:
+        return gf.find(pattern, maxRows=maxRows)
+    finally:
+        gf.close()
+
+
+def motif_count(vertices: pd.DataFrame, edges: pd.DataFrame, pattern: str, device: int = 0) -> int:
+    """Function form of ``GraphFrame(vertices, edges).motifCount(pattern)``."""
+    parse_motif(pattern)
+    gf = GraphFrame(vertices, edges, device=device)
+    try:
+        return gf.motifCount(pattern)
     finally:
         gf.close()
 

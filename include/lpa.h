@@ -694,6 +694,72 @@ int lpa_core_numbers(lpa_graph* g, int32_t max_k /* INT32_MAX: no cap */, int32_
                      int32_t* simple_degree_out /* nullable */, int32_t out_is_device,
                      lpa_core_summary* summary /* nullable */);
 
+/*
+ * Motif finding (GraphFrames GraphFrame.find(pattern)) over the DIRECTED input MULTIGRAPH.  The
+ * caller has parsed the pattern into n_vars vertex variables and n_terms terms; a term is an
+ * edge src_var -> dst_var, negated or not.  A result row is one assignment of vertices to the
+ * vertex variables that positive terms bind, and of input edge rows to the positive terms, such
+ * that every positive term's edge row goes from its src variable's vertex to its dst
+ * variable's vertex, and no input edge row goes from a negated term's src vertex to its dst
+ * vertex.  One row per assignment: duplicate edge rows and variables that are not in the output
+ * multiply rows, variables need not be distinct (a self-loop matches a -> b with a == b), rows
+ * are never deduplicated.  An edge with an end outside [0, V) is no edge; self-loops and
+ * duplicates are edges.
+ * The terms run in the order given.  The first term must be positive (it seeds the table with
+ * every valid edge row, in edge-row order; with src_var == dst_var, the self-loops); every later
+ * positive term must share a variable with the positive terms before it (an extension along the
+ * out-lists or in-lists, or, with both ends bound, a close: the row times the number of
+ * parallel edges); a negated term must have both variables bound by earlier positive terms.
+ * var_out[v] != 0 asks for variable v's column (nullable: none), want_edge for a positive term's
+ * edge-row column.  max_rows > 0 bounds EVERY table, intermediate or final: it is checked from
+ * the scan's total before the table is allocated, and a step that needs more returns
+ * LPA_EOVERFLOW with overflow_step / overflow_rows set in the summary (the summary is written
+ * on that path too) and nothing allocated left behind; max_rows <= 0: no cap.  count_only != 0
+ * runs every step but never fills the last table: rows is exact, result_out must be null.
+ * Otherwise *result_out receives a result object that owns the final table (one plain device
+ * allocation on the handle's device, which the last fill wrote) and nothing of the handle: it
+ * stays valid after later calls and after lpa_graph_destroy, until lpa_motif_result_destroy.
+ * lpa_motif_vertex_column / lpa_motif_edge_column copy a column to the host (dense vertex ids,
+ * int32; input edge rows, int64; `rows` entries) and return LPA_EINVAL for a column that was
+ * not asked for.  V == 0 or m == 0: success, zero rows, a valid empty result.
+ * LPA_EINVAL for a null handle, n_vars outside [1, 32], n_terms outside [1, 16] or more than 8
+ * positive or 8 negated terms, a variable index out of range, a negated first term, a positive
+ * term that shares no variable with the earlier positive ones, a negated term with an unbound
+ * variable, var_out naming a variable no positive term binds, result_out null without
+ * count_only or the reverse.  LPA_ENOMEM when a table cannot be allocated (the temporaries are
+ * released).  The call blocks until the work is done; one host synchronisation per term.
+ * Every step is counts, an int64 exclusive scan and a fill that writes the children of a row in
+ * list order and the rows in their order (DESIGN.md "Motif finding"): the final table, row for
+ * row, and every summary field are a function of (V, edge list, terms) alone, identical across
+ * runs and handles.  table_rows[t] is the table after term t; a table without rows ends the
+ * call (steps = the terms run so far, the later entries 0).  All working memory is
+ * stream-ordered temporaries, the labels and every other piece of lpa_step's state are neither
+ * read nor written, nothing is kept on the handle.  On a distributed job (nranks > 1) only rank
+ * 0 keeps the edge list this needs; the other ranks return LPA_EINVAL.  Since ABI 19.
+ */
+typedef struct lpa_motif_term {
+  int32_t src_var, dst_var, negated, want_edge;
+} lpa_motif_term;
+typedef struct lpa_motif_summary {
+  int64_t rows;            /* rows of the final table                                         */
+  int64_t edges;           /* valid input edge rows                                           */
+  int64_t self_loops;      /* self-loops among them                                           */
+  int64_t steps;           /* terms executed                                                  */
+  int64_t peak_rows;       /* largest table of the call                                       */
+  int64_t overflow_step;   /* term index that exceeded max_rows, else -1                      */
+  int64_t overflow_rows;   /* rows that step needed                                           */
+  int64_t table_rows[16];  /* rows after each term, in execution order                        */
+} lpa_motif_summary;       /* 184 bytes */
+typedef struct lpa_motif_result lpa_motif_result;
+int lpa_motif(lpa_graph* g, int32_t n_vars, const uint8_t* var_out /* [n_vars], nullable */,
+              const lpa_motif_term* terms, int32_t n_terms, int64_t max_rows,
+              int32_t count_only, lpa_motif_result** result_out /* null iff count_only */,
+              lpa_motif_summary* summary /* nullable */);
+int64_t lpa_motif_rows(const lpa_motif_result* r);
+int lpa_motif_vertex_column(const lpa_motif_result* r, int32_t var, int32_t* out /* host [rows] */);
+int lpa_motif_edge_column(const lpa_motif_result* r, int32_t term, int64_t* out /* host [rows] */);
+void lpa_motif_result_destroy(lpa_motif_result* r);   /* null: no-op */
+
 /* Symmetrised degree of every vertex (dense ids), host output. */
 int lpa_degrees(lpa_graph* g, int32_t* deg_out);
 
@@ -715,8 +781,10 @@ int lpa_degrees(lpa_graph* g, int32_t* deg_out);
  * ABI 15: sparse_refreshes.
  * ABI 16: lpa_core_numbers.
  * ABI 17: fill_refreshes.
- * ABI 18: lpa_bfs. */
-#define LPA_ABI_VERSION 18
+ * ABI 18: lpa_bfs.
+ * ABI 19: lpa_motif, lpa_motif_rows, lpa_motif_vertex_column, lpa_motif_edge_column,
+ *         lpa_motif_result_destroy. */
+#define LPA_ABI_VERSION 19
 int lpa_abi_version(void);
 int lpa_graph_get_info(const lpa_graph* g, lpa_graph_info* info);
 int lpa_graph_get_info_sized(const lpa_graph* g, lpa_graph_info* info, int64_t info_size);
