@@ -8,8 +8,9 @@ include/lpa.h); importing this package does not load it -- the first call does,
 and fails loudly if it has not been built.
 """
 from .graph import Graph, Loopback, comm_unique_id, gen_chunglu, gen_rmat, gen_sbm, run_ranks
-from .graphframe import (GraphFrame, IndexedGraph, MotifTerm, OutlierResult, ParsedMotif, bfs, connected_components,
-                         core_number, count_paths, enumerate_paths, find, index_graph,
+from .graphframe import (AggregateMessages, CompiledMessage, GraphFrame, IndexedGraph, MessageAggregate, MessageExpr,
+                         MotifTerm, OutlierResult, ParsedMotif, aggregate_messages, bfs, compile_message,
+                         connected_components, core_number, count_paths, enumerate_paths, find, index_graph,
                          k_core, label_propagation, louvain, motif_count, outlier_scores, page_rank,
                          parallel_personalized_page_rank, parse_motif, plan_motif, shortest_paths,
                          strongly_connected_components, triangle_count)
@@ -19,4 +20,5 @@ __all__ = ["Graph", "Loopback", "run_ranks", "GraphFrame", "IndexedGraph", "Outl
            "gen_sbm", "bfs", "connected_components", "core_number", "count_paths", "enumerate_paths", "index_graph", "ingest", "k_core",
            "label_propagation", "louvain",
            "outlier_scores", "page_rank", "parallel_personalized_page_rank", "shortest_paths", "strongly_connected_components",
-           "triangle_count", "find", "motif_count", "parse_motif", "plan_motif", "MotifTerm", "ParsedMotif"]
+           "triangle_count", "find", "motif_count", "parse_motif", "plan_motif", "MotifTerm", "ParsedMotif",
+           "AggregateMessages", "aggregate_messages", "compile_message", "CompiledMessage", "MessageExpr", "MessageAggregate"]

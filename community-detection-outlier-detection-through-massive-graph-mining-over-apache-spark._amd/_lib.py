@@ -151,6 +151,28 @@ class LpaMotifSummary(ctypes.Structure):
         return d
 
 
+LPA_AM_MAX_OPS = 64
+LPA_AM_MAX_STACK = 8
+LPA_AM_MAX_CONSTS = 16
+LPA_AM_MAX_COLUMNS = 8
+# opcodes of a message program (include/lpa.h LPA_AM_*), by value
+AM_OPCODES = ("const", "src", "dst", "edge", "add", "sub", "mul", "div", "neg", "abs", "eq", "ne", "lt", "le", "gt",
+              "ge", "and", "or", "not", "when", "when_else")
+
+
+class LpaAmProgram(ctypes.Structure):
+    _fields_ = [("n_ops", ctypes.c_int32), ("n_consts", ctypes.c_int32), ("ops", ctypes.c_uint32 * LPA_AM_MAX_OPS),
+                ("consts", ctypes.c_double * LPA_AM_MAX_CONSTS)]
+
+
+class LpaAmSummary(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int64) for k in ("edges", "messages_to_src", "messages_to_dst", "nulls", "receivers",
+                                              "rows_short", "rows_wave", "rows_block", "max_row")]
+
+    def to_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class LpaSccSummary(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in ("n_components", "n_singletons", "largest_size", "largest_id",
                                               "rounds", "trimmed", "unresolved")]
@@ -239,6 +261,9 @@ SIGNATURES = {
     "lpa_motif_vertex_column": (ctypes.c_int, [_vp, ctypes.c_int32, _i32p]),
     "lpa_motif_edge_column": (ctypes.c_int, [_vp, ctypes.c_int32, _i64p]),
     "lpa_motif_result_destroy": (None, [_vp]),
+    "lpa_aggregate_messages": (ctypes.c_int, [_vp, ctypes.POINTER(LpaAmProgram), ctypes.POINTER(LpaAmProgram), _vp,
+                                              ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp,
+                                              ctypes.POINTER(LpaAmSummary)]),
     "lpa_strongly_connected_components": (ctypes.c_int, [_vp, ctypes.c_int32, _vp, ctypes.c_int32, _vp,
                                                          ctypes.POINTER(LpaSccSummary)]),
     "lpa_louvain": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int32, _vp,

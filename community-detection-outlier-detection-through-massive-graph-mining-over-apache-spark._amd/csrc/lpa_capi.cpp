@@ -245,6 +245,8 @@ int create_common(int32_t device, hipStream_t stream, const int32_t* src, const 
   if (const char* f = getenv("LPA_TC_LDS")) g->tc_lds = atoi(f) < 0 ? 0 : atoi(f) > kTcLdsMax ? kTcLdsMax : atoi(f);
   if (const char* f = getenv("LPA_PR_SHORT")) g->pr_short = atoi(f) < 0 ? 0 : atoi(f);
   if (const char* f = getenv("LPA_PR_WAVE")) g->pr_wave = atoi(f) < 0 ? 0 : atoi(f);
+  if (const char* f = getenv("LPA_AM_SHORT")) g->am_short = atoi(f) < 0 ? 0 : atoi(f);
+  if (const char* f = getenv("LPA_AM_WAVE")) g->am_wave = atoi(f) < 0 ? 0 : atoi(f);
   if (const char* f = getenv("LPA_PPR_BATCH")) {
     const int b = atoi(f);
     g->ppr_batch = b == 4 || b == 8 || b == 16 ? b : lpa::kPprBatch;
@@ -901,6 +903,114 @@ int lpa_motif(lpa_graph* g, int32_t n_vars, const uint8_t* var_out, const lpa_mo
   }
   if (result_out) *result_out = res;
   return LPA_OK;
+}
+
+// A message program as lpa_aggregate_messages takes it (include/lpa.h): false with the error set
+static bool am_program_ok(const lpa_am_program* p, const char* name, int32_t n_vcols, int32_t n_ecols,
+                          bool* reads_v, bool* reads_e) {
+  if (p->n_ops < 1 || p->n_ops > LPA_AM_MAX_OPS) {
+    set_error("lpa_aggregate_messages: %s has %d ops, outside [1, %d]", name, p->n_ops, LPA_AM_MAX_OPS);
+    return false;
+  }
+  if (p->n_consts < 0 || p->n_consts > LPA_AM_MAX_CONSTS) {
+    set_error("lpa_aggregate_messages: %s has %d constants, outside [0, %d]", name, p->n_consts, LPA_AM_MAX_CONSTS);
+    return false;
+  }
+  int depth = 0;
+  for (int i = 0; i < p->n_ops; ++i) {
+    const uint32_t op = p->ops[i] & 0xFFFFu, arg = p->ops[i] >> 16;
+    int pops = 2;
+    switch (op) {
+      case LPA_AM_CONST:
+        pops = 0;
+        if ((int32_t)arg >= p->n_consts) {
+          set_error("lpa_aggregate_messages: %s op %d reads constant %u of %d", name, i, arg, p->n_consts);
+          return false;
+        }
+        break;
+      case LPA_AM_SRC:
+      case LPA_AM_DST:
+        pops = 0;
+        *reads_v = true;
+        if ((int32_t)arg >= n_vcols) {
+          set_error("lpa_aggregate_messages: %s op %d reads vertex column %u of %d", name, i, arg, n_vcols);
+          return false;
+        }
+        break;
+      case LPA_AM_EDGE:
+        pops = 0;
+        *reads_e = true;
+        if ((int32_t)arg >= n_ecols) {
+          set_error("lpa_aggregate_messages: %s op %d reads edge column %u of %d", name, i, arg, n_ecols);
+          return false;
+        }
+        break;
+      case LPA_AM_NEG:
+      case LPA_AM_ABS:
+      case LPA_AM_NOT:
+        pops = 1;
+        break;
+      case LPA_AM_WHEN_ELSE:
+        pops = 3;
+        break;
+      default:
+        if (op >= LPA_AM_NOPS) {
+          set_error("lpa_aggregate_messages: %s op %d has the unknown opcode %u", name, i, op);
+          return false;
+        }
+        break;
+    }
+    if (depth < pops) {
+      set_error("lpa_aggregate_messages: %s op %d underflows the stack (%d values, %d needed)", name, i, depth, pops);
+      return false;
+    }
+    depth += 1 - pops;
+    if (depth > LPA_AM_MAX_STACK) {
+      set_error("lpa_aggregate_messages: %s op %d overflows the stack of %d values", name, i, LPA_AM_MAX_STACK);
+      return false;
+    }
+  }
+  if (depth != 1) {
+    set_error("lpa_aggregate_messages: %s leaves %d values on the stack, not 1", name, depth);
+    return false;
+  }
+  return true;
+}
+
+int lpa_aggregate_messages(lpa_graph* g, const lpa_am_program* to_src, const lpa_am_program* to_dst,
+                           const double* vcols, int32_t n_vcols, const double* ecols, int32_t n_ecols,
+                           int64_t* count_out, double* sum_out, double* min_out, double* max_out,
+                           lpa_am_summary* summary) {
+  // the programs first: they are checked without a handle
+  if (!to_src && !to_dst) {
+    set_error("lpa_aggregate_messages: both programs are null; to_src, to_dst, or both have to be provided");
+    return LPA_EINVAL;
+  }
+  if (n_vcols < 0 || n_vcols > LPA_AM_MAX_COLUMNS || n_ecols < 0 || n_ecols > LPA_AM_MAX_COLUMNS) {
+    set_error("lpa_aggregate_messages: n_vcols and n_ecols must be in [0, %d], got %d and %d", LPA_AM_MAX_COLUMNS,
+              n_vcols, n_ecols);
+    return LPA_EINVAL;
+  }
+  bool reads_v = false, reads_e = false;
+  if (to_src && !am_program_ok(to_src, "to_src", n_vcols, n_ecols, &reads_v, &reads_e)) return LPA_EINVAL;
+  if (to_dst && !am_program_ok(to_dst, "to_dst", n_vcols, n_ecols, &reads_v, &reads_e)) return LPA_EINVAL;
+  if (!g) {
+    set_error("null handle");
+    return LPA_EINVAL;
+  }
+  if ((reads_v && !vcols) || (reads_e && !ecols)) {
+    set_error("lpa_aggregate_messages: null %s column pointer, and a program reads a column",
+              reads_v && !vcols ? "vertex" : "edge");
+    return LPA_EINVAL;
+  }
+  if (g->m > 0 && !g->e_src) {
+    set_error("lpa_aggregate_messages of a distributed job runs on rank 0 (the rank that keeps the edge list)");
+    return LPA_EINVAL;
+  }
+  LPA_HIP(hipSetDevice(g->device));
+  // columns no program reads are not uploaded
+  return aggregate_messages(g, to_src, to_dst, vcols, reads_v ? n_vcols : 0, ecols, reads_e ? n_ecols : 0, count_out,
+                            sum_out, min_out, max_out, summary);
 }
 
 int64_t lpa_motif_rows(const lpa_motif_result* r) { return r ? r->rows : 0; }

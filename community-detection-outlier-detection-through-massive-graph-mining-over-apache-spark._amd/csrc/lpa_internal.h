@@ -133,6 +133,9 @@ constexpr int kLvShort = 32;          // 8 lanes per row up to this length, no t
 constexpr int kLvWave = 256;          // a wave per row up to this length; longer: a block of 1024 per row
 constexpr int kLvWaveSlots = 512;     // (community, weight) slots of a wave's table: 6 KB, 24 KB a block of 4 waves
 constexpr int kLvBlockSlots = 4096;   // ... of the block form's table: 48 KB, under the 64 KB of a plain launch
+// message aggregation (lpa_agg.hip): default message-list lengths of its row forms
+constexpr int kAmShort = 32;          // 8 lanes per row up to this length
+constexpr int kAmWave = 1024;         // a wave per row up to this length; longer: a block of 1024 per row
 __host__ __device__ inline uint32_t col_class(int32_t c, uint32_t ncls) { return ((uint32_t)c >> 10) & (ncls - 1u); }
 
 struct Segment {   // one unit of a seg-bin row
@@ -485,6 +488,10 @@ struct lpa_graph {
   int lv_wave = lpa::kLvWave;               // LPA_LV_WAVE  (>= 0; 0, or <= LPA_LV_SHORT: no row takes the wave form)
   int lv_table = lpa::kLvBlockSlots;        // LPA_LV_TABLE (0 .. kLvBlockSlots, rounded down to a power of two;
                                             //   0: every wave-form and block-form row spills)
+  // message aggregation (lpa_agg.hip): message-list lengths up to which a row takes the short form and the
+  // wave form (longer: the block form); a row without messages always takes the short form
+  int am_short = lpa::kAmShort;             // LPA_AM_SHORT (>= 0; 0: no row with a message takes the short form)
+  int am_wave = lpa::kAmWave;               // LPA_AM_WAVE  (>= 0; 0, or <= LPA_AM_SHORT: no row takes the wave form)
   int serial = 0;                           // LPA_SERIAL=1: all tally kernels on one stream (profiling)
   int use_graphs = 1;                       // LPA_GRAPHS=0: no captured superstep graphs
   // captured supersteps: [0, 4) converged per (cur, par); [4, 12) supersteps 2 and 3 per
@@ -786,6 +793,12 @@ int bfs(lpa_graph* g, const uint8_t* from_mask, const uint8_t* to_mask, const ui
 // caller, res (null iff count_only) comes in empty
 int motif(lpa_graph* g, int32_t n_vars, const uint8_t* var_out, const lpa_motif_term* terms, int32_t n_terms,
           int64_t max_rows, int32_t count_only, lpa_motif_result* res, lpa_motif_summary* summary);
+
+// message aggregation over the directed multigraph (lpa_agg.hip); the programs and the other
+// arguments are checked by the caller
+int aggregate_messages(lpa_graph* g, const lpa_am_program* to_src, const lpa_am_program* to_dst, const double* vcols,
+                       int32_t n_vcols, const double* ecols, int32_t n_ecols, int64_t* count_out, double* sum_out,
+                       double* min_out, double* max_out, lpa_am_summary* summary);
 
 // strongly connected components of the directed graph, GraphX's rounds (lpa_scc.hip)
 int strongly_connected_components(lpa_graph* g, int32_t max_iter, int32_t* comp_out, int32_t out_is_device,

@@ -642,6 +642,63 @@ class Graph:
         finally:
             lib.lpa_motif_result_destroy(res)
 
+    # -- message aggregation ----------------------------------------------------------
+    @staticmethod
+    def _am_program(prog):
+        """A compiled message (``ops``: (opcode, argument) pairs, ``consts``: floats) as the C ABI's
+        fixed-size struct; ``None`` stays ``None``."""
+        if prog is None:
+            return None
+        ops, consts = list(prog.ops), list(prog.consts)
+        if len(ops) > _lib.LPA_AM_MAX_OPS or len(consts) > _lib.LPA_AM_MAX_CONSTS:
+            raise ValueError(f"a message program holds at most {_lib.LPA_AM_MAX_OPS} ops and "
+                             f"{_lib.LPA_AM_MAX_CONSTS} constants, got {len(ops)} and {len(consts)}")
+        p = _lib.LpaAmProgram()
+        p.n_ops, p.n_consts = len(ops), len(consts)
+        for i, (op, arg) in enumerate(ops):
+            if not 0 <= int(op) <= 0xFFFF or not 0 <= int(arg) <= 0xFFFF:
+                raise ValueError(f"op {i}: opcode and argument are 16-bit values, got {op} and {arg}")
+            p.ops[i] = int(op) | (int(arg) << 16)
+        for i, c in enumerate(consts):
+            p.consts[i] = float(c)
+        return p
+
+    def aggregate_messages(self, to_src, to_dst, vcols=None, ecols=None, stats: bool = False):
+        """Message aggregation over the directed input multigraph (lpa_aggregate_messages;
+        GraphFrames ``aggregateMessages``): every input edge evaluates the compiled message
+        ``to_dst`` for its destination and ``to_src`` for its source (``compile_message``
+        results or ``None``, not both ``None``), every vertex reduces what it receives.
+        ``vcols`` is ``[n_vcols, num_vertices]`` float64, ``ecols`` ``[n_ecols, num_edges]``
+        float64 in the handle's input edge order (``None``: no columns).  Returns a dict of
+        ``num_vertices``-entry arrays: ``count`` (int64), ``sum`` (0.0 where count is 0),
+        ``min`` and ``max`` (NaN where count is 0); with ``stats=True`` ``(dict, summary)``,
+        the summary a dict of edges, messages_to_src, messages_to_dst, nulls, receivers,
+        rows_short, rows_wave, rows_block, max_row.  Duplicate edges send again; a null
+        message is not delivered.  ``count``, ``min`` and ``max`` depend on the inputs alone;
+        ``sum`` is bit-identical across calls and handles, and across input edge orders for a
+        program that reads no edge column.  The labels and the LPA state are not touched."""
+        V, m = self.num_vertices, self.num_edges
+
+        def cols(x, n, name):
+            if x is None:
+                return np.empty((0, n), dtype=np.float64)
+            a = np.ascontiguousarray(x, dtype=np.float64)
+            if a.ndim != 2 or a.shape[1] != n:
+                raise ValueError(f"{name} must have the shape [columns, {n}], got {list(a.shape)}")
+            return a
+
+        vc, ec = cols(vcols, V, "vcols"), cols(ecols, m, "ecols")
+        ps, pd_ = self._am_program(to_src), self._am_program(to_dst)
+        out = dict(count=np.empty(V, dtype=np.int64), sum=np.empty(V, dtype=np.float64),
+                   min=np.empty(V, dtype=np.float64), max=np.empty(V, dtype=np.float64))
+        summ = _lib.LpaAmSummary()
+        _lib.check(self._lib.lpa_aggregate_messages(
+            self._handle(), None if ps is None else ctypes.byref(ps), None if pd_ is None else ctypes.byref(pd_),
+            vc.ctypes.data if vc.shape[0] else None, vc.shape[0], ec.ctypes.data if ec.shape[0] else None,
+            ec.shape[0], out["count"].ctypes.data, out["sum"].ctypes.data, out["min"].ctypes.data,
+            out["max"].ctypes.data, ctypes.byref(summ) if stats else None))
+        return (out, summ.to_dict()) if stats else out
+
     # -- strongly connected components ------------------------------------------------
     def strongly_connected_components(self, max_iter=None, out=None, sizes: bool = False):
         """Strongly connected components of the directed input graph

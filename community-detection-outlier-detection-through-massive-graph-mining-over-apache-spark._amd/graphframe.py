@@ -31,6 +31,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import pandas as pd
 
+from . import _lib
 from .graph import Graph
 
 ID, SRC, DST, LABEL = "id", "src", "dst", "label"
@@ -382,6 +383,349 @@ def _check_max_rows(maxRows):
         raise TypeError(f"maxRows must be an int or None, got {type(maxRows).__name__}")
     if maxRows <= 0:
         raise ValueError(f"maxRows must be greater than 0, got {maxRows}")
+
+
+# ---- message aggregation: the expression layer (pure host) ----
+AM_MAX_OPS = _lib.LPA_AM_MAX_OPS                  # ops of one compiled message
+AM_MAX_STACK = _lib.LPA_AM_MAX_STACK              # operand stack depth of its evaluation
+AM_MAX_CONSTS = _lib.LPA_AM_MAX_CONSTS            # distinct constants of one message
+AM_MAX_VERTEX_COLUMNS = _lib.LPA_AM_MAX_COLUMNS   # vertex columns of one call, both directions together
+AM_MAX_EDGE_COLUMNS = _lib.LPA_AM_MAX_COLUMNS     # edge columns of one call, both directions together
+AM_MSG_NAME = "MSG"
+AM_EXACT_INT = 2 ** 53                            # integers up to this magnitude are exact in binary64
+_AM_OPCODE = {name: i for i, name in enumerate(_lib.AM_OPCODES)}
+_AM_BINARY = {"add": "+", "sub": "-", "mul": "*", "div": "/", "eq": "==", "ne": "!=", "lt": "<", "le": "<=",
+              "gt": ">", "ge": ">=", "and": "&", "or": "|"}
+_AM_UNARY = {"neg": "-", "not": "~"}
+_AM_BOOL_OPS = ("eq", "ne", "lt", "le", "gt", "ge", "and", "or", "not")
+_AM_COLUMN_KINDS = {"src": "vertex", "dst": "vertex", "edge": "edge"}
+AM_AGGREGATES = ("sum", "min", "max", "avg", "count")
+
+
+class MessageExpr:
+    """A node of a message expression: ``AM.src["x"] * 2 + AM.edge["w"]``.  Built by the
+    operators and by ``AggregateMessages``; never evaluated on the host."""
+    __slots__ = ("op", "args", "value", "is_bool")
+
+    def __init__(self, op, args=(), value=None, is_bool=False):
+        self.op, self.args, self.value, self.is_bool = op, tuple(args), value, bool(is_bool)
+
+    @staticmethod
+    def of(x):
+        """An operand: an expression, or a plain Python / numpy number or bool as a constant."""
+        if isinstance(x, MessageExpr):
+            return x
+        if isinstance(x, MessageAggregate):
+            raise ValueError(f"{x} is an aggregate: it is aggCol, not an operand of an expression")
+        if isinstance(x, (bool, np.bool_)):
+            return MessageExpr("const", value=1.0 if x else 0.0, is_bool=True)
+        if isinstance(x, (int, np.integer)):
+            if abs(int(x)) > AM_EXACT_INT:
+                raise ValueError(f"the constant {x} is beyond +-2^53 and not exact in binary64")
+            return MessageExpr("const", value=float(int(x)))
+        if isinstance(x, (float, np.floating)):
+            if not np.isfinite(x):
+                raise ValueError(f"the constant {x} is not finite")
+            return MessageExpr("const", value=float(x))
+        raise TypeError(f"a message operand is an expression or a number, got {type(x).__name__}")
+
+    def _binary(self, op, other, swap=False):
+        a, b = self, MessageExpr.of(other)
+        if swap:
+            a, b = b, a
+        if op in ("and", "or"):
+            for x in (a, b):
+                x._need_bool(_AM_BINARY[op])
+        return MessageExpr(op, (a, b), is_bool=op in _AM_BOOL_OPS)
+
+    def _need_bool(self, what):
+        if not self.is_bool:
+            raise ValueError(f"{what} takes comparison results, got {self}; compare a column first, as in "
+                             f"({self} != 0)")
+
+    def __add__(self, o): return self._binary("add", o)
+    def __radd__(self, o): return self._binary("add", o, True)
+    def __sub__(self, o): return self._binary("sub", o)
+    def __rsub__(self, o): return self._binary("sub", o, True)
+    def __mul__(self, o): return self._binary("mul", o)
+    def __rmul__(self, o): return self._binary("mul", o, True)
+    def __truediv__(self, o): return self._binary("div", o)
+    def __rtruediv__(self, o): return self._binary("div", o, True)
+    def __eq__(self, o): return self._binary("eq", o)
+    def __ne__(self, o): return self._binary("ne", o)
+    def __lt__(self, o): return self._binary("lt", o)
+    def __le__(self, o): return self._binary("le", o)
+    def __gt__(self, o): return self._binary("gt", o)
+    def __ge__(self, o): return self._binary("ge", o)
+    def __and__(self, o): return self._binary("and", o)
+    def __rand__(self, o): return self._binary("and", o, True)
+    def __or__(self, o): return self._binary("or", o)
+    def __ror__(self, o): return self._binary("or", o, True)
+    def __neg__(self): return MessageExpr("neg", (self,))
+    def __abs__(self): return MessageExpr("abs", (self,))
+
+    def __invert__(self):
+        self._need_bool("~")
+        return MessageExpr("not", (self,), is_bool=True)
+
+    __hash__ = None   # == builds an expression
+
+    def __bool__(self):
+        raise TypeError("a message expression has no truth value: combine conditions with & | ~, not and / or / not")
+
+    def otherwise(self, value):
+        """The value of a ``when`` whose condition is false or null."""
+        if self.op != "when" or len(self.args) != 2:
+            raise ValueError("otherwise() follows when(condition, value), once")
+        v = MessageExpr.of(value)
+        return MessageExpr("when", self.args + (v,), is_bool=self.is_bool and v.is_bool)
+
+    def same(self, other) -> bool:
+        """Structural equality (``==`` builds a comparison)."""
+        return (isinstance(other, MessageExpr) and self.op == other.op and self.value == other.value
+                and len(self.args) == len(other.args) and all(a.same(b) for a, b in zip(self.args, other.args)))
+
+    def walk(self):
+        """Every node, operands before their operator."""
+        for a in self.args:
+            yield from a.walk()
+        yield self
+
+    def __str__(self):
+        if self.op == "const":
+            return repr(self.value)
+        if self.op in _AM_COLUMN_KINDS:
+            return f"{self.op}[{self.value!r}]"
+        if self.op == "msg":
+            return AM_MSG_NAME
+        if self.op in _AM_BINARY:
+            return f"({self.args[0]} {_AM_BINARY[self.op]} {self.args[1]})"
+        if self.op in _AM_UNARY:
+            return f"({_AM_UNARY[self.op]}{self.args[0]})"
+        if self.op == "abs":
+            return f"abs({self.args[0]})"
+        s = f"when({self.args[0]}, {self.args[1]})"
+        return s + (f".otherwise({self.args[2]})" if len(self.args) == 3 else "")
+
+    __repr__ = __str__
+
+
+class MessageAggregate:
+    """``AM.sum(AM.msg)`` and its kin: what ``aggCol`` is.  ``alias(name)`` names the column."""
+
+    def __init__(self, kind, expr, name=None):
+        self.kind, self.expr, self._name = kind, expr, name
+
+    def alias(self, name):
+        return MessageAggregate(self.kind, self.expr, str(name))
+
+    @property
+    def name(self) -> str:
+        """The result column: the alias, or Spark's default ``sum(MSG)``."""
+        return self._name if self._name is not None else f"{self.kind}({AM_MSG_NAME})"
+
+    def __str__(self):
+        return f"{self.kind}({self.expr})"
+
+    __repr__ = __str__
+
+
+class _MessageColumns:
+    def __init__(self, kind):
+        self._kind = kind
+
+    def __getitem__(self, name):
+        if not isinstance(name, str):
+            raise TypeError(f"AM.{self._kind}[...] takes a column name, got {type(name).__name__}")
+        return MessageExpr(self._kind, value=name)
+
+
+class AggregateMessages:
+    """The vocabulary of ``GraphFrame.aggregateMessages``, used as ``AM`` the way
+    ``graphframes.lib.AggregateMessages`` is::
+
+        from graphframes_amd import AggregateMessages as AM
+        g.aggregateMessages(AM.sum(AM.msg).alias("crossing"),
+                            sendToSrc=AM.when(AM.src["label"] != AM.dst["label"], 1.0),
+                            sendToDst=AM.when(AM.src["label"] != AM.dst["label"], 1.0))
+
+    ``AM.src["col"]`` / ``AM.dst["col"]`` read a vertex column of the edge's source /
+    destination, ``AM.edge["col"]`` an edge column, ``AM.msg`` is the message (in ``aggCol``
+    only), ``AM.lit(x)`` a constant; a plain Python number is accepted wherever an operand is.
+    Operands combine with ``+ - * /``, unary ``-``, ``abs()``, the six comparisons, and
+    ``& | ~`` on comparison results.  ``AM.when(cond, value)`` optionally takes
+    ``.otherwise(value)``.  The aggregates are ``AM.sum``, ``AM.min``, ``AM.max``, ``AM.avg``
+    (alias ``AM.mean``) and ``AM.count`` of ``AM.msg``, each with an optional ``.alias(name)``;
+    the default names are Spark's, ``sum(MSG)`` and so on.
+
+    These are this package's expressions over pandas frames, not Spark SQL columns: strings such
+    as ``"src.x + 1"`` and functions of ``pyspark.sql.functions`` are not understood.  Everything
+    is evaluated in IEEE binary64; a comparison is worth 1.0 or 0.0.  Null follows Spark where
+    that is cheap to state: an operator with a null operand gives null; ``x / 0`` gives null, as
+    Spark SQL does; a ``when`` without ``otherwise`` gives null where its condition is false; a
+    null condition takes the ``otherwise`` branch, or gives null when there is none; a null
+    message is not delivered.  One deviation: ``&`` and ``|`` with a null operand give null (Spark
+    has three-valued logic: ``false & null`` is false there)."""
+    src = _MessageColumns("src")
+    dst = _MessageColumns("dst")
+    edge = _MessageColumns("edge")
+    msg = MessageExpr("msg")
+
+    @staticmethod
+    def lit(x):
+        return MessageExpr.of(x)
+
+    @staticmethod
+    def when(condition, value):
+        c = MessageExpr.of(condition)
+        c._need_bool("when()'s condition")
+        v = MessageExpr.of(value)
+        return MessageExpr("when", (c, v), is_bool=v.is_bool)
+
+    @staticmethod
+    def sum(x): return MessageAggregate("sum", x)
+    @staticmethod
+    def min(x): return MessageAggregate("min", x)
+    @staticmethod
+    def max(x): return MessageAggregate("max", x)
+    @staticmethod
+    def avg(x): return MessageAggregate("avg", x)
+    @staticmethod
+    def count(x): return MessageAggregate("count", x)
+    mean = avg
+
+
+@dataclass(frozen=True)
+class CompiledMessage:
+    """A message expression as the postfix program the kernels interpret (include/lpa.h
+    ``lpa_am_program``): ``ops`` are (opcode, 16-bit argument) pairs, the argument an index into
+    ``consts``, ``vertex_columns`` or ``edge_columns`` for the opcodes that push."""
+    ops: tuple
+    consts: tuple
+    vertex_columns: tuple
+    edge_columns: tuple
+    depth: int
+
+    def decode(self) -> MessageExpr:
+        """The expression back from the program."""
+        st = []
+        for code, arg in self.ops:
+            op = _lib.AM_OPCODES[code]
+            if op == "const":
+                st.append(MessageExpr("const", value=self.consts[arg]))
+            elif op in ("src", "dst"):
+                st.append(MessageExpr(op, value=self.vertex_columns[arg]))
+            elif op == "edge":
+                st.append(MessageExpr(op, value=self.edge_columns[arg]))
+            else:
+                n = 1 if op in ("neg", "abs", "not") else 3 if op == "when_else" else 2
+                args = st[len(st) - n:]
+                del st[len(st) - n:]
+                st.append(MessageExpr("when" if op == "when_else" else op, args))
+        assert len(st) == 1
+        return st[0]
+
+
+def compile_message(expr, vertex_columns=(), edge_columns=()) -> CompiledMessage:
+    """Compile a message expression to its postfix program: operands left to right, then their
+    operator.  ``vertex_columns`` / ``edge_columns``: names that already hold the first column
+    indices (the other direction's of the same call); the result's lists extend them.  Pure host
+    code.  ``ValueError`` for ``AM.msg`` inside the message and for a limit exceeded: more than
+    AM_MAX_OPS ops, a stack deeper than AM_MAX_STACK, more than AM_MAX_CONSTS constants, more
+    than AM_MAX_VERTEX_COLUMNS or AM_MAX_EDGE_COLUMNS columns."""
+    root = MessageExpr.of(expr)
+    ops, consts = [], []
+    names = {"vertex": list(vertex_columns), "edge": list(edge_columns)}
+    caps = {"vertex": AM_MAX_VERTEX_COLUMNS, "edge": AM_MAX_EDGE_COLUMNS}
+    depth = top = 0
+    for node in root.walk():
+        if node.op == "msg":
+            raise ValueError(f"AM.msg appears inside the message {root}: it is what aggCol aggregates")
+        if node.op == "const":
+            bits = np.float64(node.value).tobytes()   # 0.0 and -0.0 are two constants
+            at = [np.float64(c).tobytes() for c in consts]
+            if bits not in at:
+                consts.append(node.value)
+                at.append(bits)
+            arg, pops = at.index(bits), 0
+        elif node.op in _AM_COLUMN_KINDS:
+            kind = _AM_COLUMN_KINDS[node.op]
+            if node.value not in names[kind]:
+                names[kind].append(node.value)
+            arg, pops = names[kind].index(node.value), 0
+        else:
+            arg, pops = 0, len(node.args)
+        code = "when_else" if node.op == "when" and pops == 3 else node.op
+        ops.append((_AM_OPCODE[code], arg))
+        depth += 1 - pops
+        top = max(top, depth)
+    if len(ops) > AM_MAX_OPS:
+        raise ValueError(f"the message {root} compiles to {len(ops)} ops, more than AM_MAX_OPS = {AM_MAX_OPS}")
+    if top > AM_MAX_STACK:
+        raise ValueError(f"the message {root} needs a stack of {top} values, more than AM_MAX_STACK = {AM_MAX_STACK}")
+    if len(consts) > AM_MAX_CONSTS:
+        raise ValueError(f"the message {root} holds {len(consts)} constants, more than AM_MAX_CONSTS = "
+                         f"{AM_MAX_CONSTS}")
+    for kind in ("vertex", "edge"):
+        if len(names[kind]) > caps[kind]:
+            raise ValueError(f"the call reads {len(names[kind])} {kind} columns ({', '.join(names[kind])}), more "
+                             f"than AM_MAX_{kind.upper()}_COLUMNS = {caps[kind]}")
+    return CompiledMessage(tuple(ops), tuple(consts), tuple(names["vertex"]), tuple(names["edge"]), top)
+
+
+def _check_agg_col(aggCol) -> MessageAggregate:
+    if not isinstance(aggCol, MessageAggregate) or aggCol.kind not in AM_AGGREGATES:
+        raise ValueError(f"aggCol must be AM.sum, AM.min, AM.max, AM.avg or AM.count of AM.msg, got {aggCol!r}")
+    e = aggCol.expr
+    if isinstance(e, MessageExpr) and e.op != "msg":
+        for node in e.walk():
+            if node.op in _AM_COLUMN_KINDS:
+                raise ValueError(f"aggCol {aggCol} reads AM.{node.op}[{node.value!r}]: it aggregates AM.msg alone; "
+                                 "columns belong in sendToSrc / sendToDst")
+    if not isinstance(e, MessageExpr) or e.op != "msg":
+        raise ValueError(f"aggCol must aggregate exactly AM.msg, got {aggCol}")
+    return aggCol
+
+
+def _am_column(frame: pd.DataFrame, name: str, kind: str) -> np.ndarray:
+    """A column an expression reads, as float64; refused unless every value is exact and finite."""
+    if name not in frame.columns:
+        raise ValueError(f"the {kind} frame has no column {name!r}; it has: {','.join(map(str, frame.columns))}")
+    col = frame[name]
+    dt = col.dtype
+    types = pd.api.types
+    if not (types.is_bool_dtype(dt) or (types.is_numeric_dtype(dt) and not types.is_complex_dtype(dt))):
+        raise ValueError(f"column {name!r} of the {kind} frame is not numeric or bool: dtype {dt}")
+    bad = ValueError(f"column {name!r} of the {kind} frame holds NaN, None or an infinite value")
+    if col.isna().any():
+        raise bad
+    if types.is_bool_dtype(dt):
+        return col.to_numpy(dtype=bool).astype(np.float64)
+    if types.is_integer_dtype(dt):
+        a = col.to_numpy(dtype=np.uint64 if types.is_unsigned_integer_dtype(dt) else np.int64)
+        if a.size and (int(a.max()) > AM_EXACT_INT or int(a.min()) < -AM_EXACT_INT):
+            raise ValueError(f"column {name!r} of the {kind} frame holds an integer beyond +-2^53, not exact in "
+                             "binary64")
+        return a.astype(np.float64)
+    a = col.to_numpy(dtype=np.float64)
+    if not np.isfinite(a).all():
+        raise bad
+    return a
+
+
+def _am_prepare(v: pd.DataFrame, e: pd.DataFrame, aggCol, sendToSrc, sendToDst):
+    """The host side of aggregateMessages, before any handle: (aggregate, to_src, to_dst, vertex
+    columns [n][rows of v], edge columns [n][rows of e])."""
+    if sendToSrc is None and sendToDst is None:
+        raise ValueError("Either `sendToSrc`, `sendToDst`, or both have to be provided")
+    agg = _check_agg_col(aggCol)
+    to_src = None if sendToSrc is None else compile_message(sendToSrc)
+    to_dst = None if sendToDst is None else compile_message(
+        sendToDst, *(() if to_src is None else (to_src.vertex_columns, to_src.edge_columns)))
+    last = to_dst if to_dst is not None else to_src
+    vcols = [_am_column(v, name, "vertex") for name in last.vertex_columns]
+    ecols = [_am_column(e, name, "edge") for name in last.edge_columns]
+    return agg, to_src, to_dst, vcols, ecols
 
 
 def _check_cc_algorithm(algorithm):
@@ -880,6 +1224,42 @@ class GraphFrame:
             return int(self._indexed().num_vertices)
         return self._gpu_graph().motif(parsed.n_vars, self._motif_terms(parsed, plan, False), count_only=True)
 
+    def aggregateMessages(self, aggCol, sendToSrc=None, sendToDst=None) -> pd.DataFrame:
+        """``GraphFrame.aggregateMessages(aggCol, sendToSrc, sendToDst)``: every edge sends the
+        value of ``sendToSrc`` to its source and of ``sendToDst`` to its destination (either may
+        be omitted, not both), every vertex aggregates what it receives with ``aggCol``.  The
+        expressions are built from ``AggregateMessages`` (used as ``AM``; its docstring has the
+        vocabulary, the null rules and the one deviation from Spark): this package's expressions
+        over pandas frames, not Spark SQL columns or strings.
+
+        Returns a DataFrame with ``id`` and the aggregate column (``sum(MSG)`` and so on, or the
+        alias), one row per vertex that received at least one non-null message, sorted by ``id``.
+        Sums, minima, maxima and averages are float64, ``count`` is int64; ``avg`` is
+        ``sum / count``.  Edges whose ``src`` or ``dst`` is no vertex id are no edges, a duplicate
+        edge sends again, a self-loop with both directions given delivers both messages to its
+        vertex; where an id repeats in the vertex frame its first row stands for the vertex.
+
+        Refused with ``ValueError`` before any device work: neither direction given; an
+        ``aggCol`` that is not one of the five aggregates of exactly ``AM.msg``; ``AM.msg``
+        inside a message; a column the frame lacks; a column that is not numeric or bool; a
+        column that holds NaN, None or an infinite value, or an integer beyond +-2^53; a message
+        beyond AM_MAX_OPS ops, AM_MAX_STACK stack values or AM_MAX_CONSTS constants, or a call
+        that reads more than AM_MAX_VERTEX_COLUMNS vertex or AM_MAX_EDGE_COLUMNS edge columns.
+        A bare comparison as a message sends 1.0 or 0.0."""
+        agg, to_src, to_dst, vcols, ecols = _am_prepare(self._v, self._e, aggCol, sendToSrc, sendToDst)
+        ig = self._indexed()
+        rep = self._first_rows()
+        V, m = ig.num_vertices, int(ig.src.size)
+        vc = np.stack([c[rep] for c in vcols]) if vcols else np.empty((0, V), dtype=np.float64)
+        ec = np.stack([c[ig.kept] for c in ecols]) if ecols else np.empty((0, m), dtype=np.float64)
+        res = self._gpu_graph().aggregate_messages(to_src, to_dst, vc, ec)
+        got = res["count"] > 0
+        if agg.kind == "avg":
+            values = res["sum"][got] / res["count"][got]
+        else:
+            values = res[agg.kind][got]
+        return pd.DataFrame({ID: ig.ids[got], agg.name: values})
+
     def inDegrees(self) -> pd.DataFrame:
         """Vertices + ``inDegree`` (int64): the kept edges ending at each vertex, duplicates
         counted.  Every vertex has a row, with 0 where GraphFrames' property leaves the
@@ -1034,6 +1414,17 @@ def find(vertices: pd.DataFrame, edges: pd.DataFrame, pattern: str, *, maxRows=N
     gf = GraphFrame(vertices, edges, device=device)
     try:
         return gf.find(pattern, maxRows=maxRows)
+    finally:
+        gf.close()
+
+
+def aggregate_messages(vertices: pd.DataFrame, edges: pd.DataFrame, aggCol, sendToSrc=None, sendToDst=None,
+                       device: int = 0) -> pd.DataFrame:
+    """Function form of ``GraphFrame(vertices, edges).aggregateMessages(aggCol, sendToSrc,
+    sendToDst)``; the host checks run before a handle is created."""
+    gf = GraphFrame(vertices, edges, device=device)
+    try:
+        return gf.aggregateMessages(aggCol, sendToSrc=sendToSrc, sendToDst=sendToDst)
     finally:
         gf.close()
 

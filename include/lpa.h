@@ -760,6 +760,87 @@ int lpa_motif_vertex_column(const lpa_motif_result* r, int32_t var, int32_t* out
 int lpa_motif_edge_column(const lpa_motif_result* r, int32_t term, int64_t* out /* host [rows] */);
 void lpa_motif_result_destroy(lpa_motif_result* r);   /* null: no-op */
 
+/*
+ * Message aggregation (GraphFrames GraphFrame.aggregateMessages) over the DIRECTED input
+ * MULTIGRAPH.  Every kept edge row src -> dst evaluates a message program: to_dst's value goes
+ * to dst, to_src's to src (either may be null, not both).  Every vertex reduces the messages it
+ * receives to their count, sum, min and max, in IEEE binary64.  Duplicates are edges of their own
+ * (they send again), a self-loop with both programs delivers both messages to its vertex, an edge
+ * with an end outside [0, V) is no edge.
+ * A program is postfix code over an operand stack of at most LPA_AM_MAX_STACK values: op word =
+ * opcode | argument << 16.  CONST k pushes consts[k]; SRC c / DST c push vcols[c][src] /
+ * vcols[c][dst]; EDGE c pushes ecols[c][edge row]; ADD SUB MUL DIV, the comparisons EQ NE LT LE GT
+ * GE (1.0 or 0.0) and AND OR (operands != 0.0 are true) pop b, then a, and push a op b; NEG ABS NOT
+ * replace the top; WHEN pops value, then condition, and pushes the value where the condition is
+ * true; WHEN_ELSE pops otherwise, value, condition.  A value may be null: an operator with a null
+ * operand gives null (AND and OR too: no three-valued logic), x / 0 gives null, a WHEN whose
+ * condition is false or null gives null, a WHEN_ELSE whose condition is false or null gives its
+ * otherwise operand.  Both branches of a conditional are evaluated.  A null message is not
+ * delivered.  The program must leave exactly one value.
+ * vcols: host [n_vcols][V]; ecols: host [n_ecols][m], in the handle's input edge order.  The
+ * outputs are host arrays of V entries, each nullable (only the wanted ones are written):
+ * count_out (0 for a vertex that received nothing), sum_out (0.0 there), min_out and max_out (NaN
+ * there).  summary (nullable) holds integers only: nulls = the messages evaluated and not
+ * delivered; receivers = vertices with count > 0; rows_* = the vertices by kernel form; max_row =
+ * the longest message list (in-degree if to_dst, plus out-degree if to_src).
+ * LPA_EINVAL, with a lpa_last_error() text, for both programs null; a malformed program (n_ops
+ * outside [1, LPA_AM_MAX_OPS], n_consts outside [0, LPA_AM_MAX_CONSTS], an unknown opcode, a
+ * constant or column index out of range, stack underflow, a stack deeper than LPA_AM_MAX_STACK,
+ * an end depth other than 1); a null handle; n_vcols or n_ecols outside [0, LPA_AM_MAX_COLUMNS];
+ * a null column pointer when a column is read.  The programs are validated on the host, before
+ * the handle is looked at and before anything is launched; the kernels trust them.  V == 0 or no
+ * valid edge: success, the outputs at their empty values.
+ * A vertex's message list is its in-list rows, sorted by (src, edge row), then its out-list rows,
+ * sorted by (dst, edge row).  Rows of up to LPA_AM_SHORT entries (default 32) take 8 lanes each,
+ * up to LPA_AM_WAVE (default 1024) a wave, longer ones a block of 1024 (both read at create time;
+ * 0, or LPA_AM_WAVE <= LPA_AM_SHORT: no row takes that form, except that an empty row is always a
+ * short one).  Every lane accumulates its strided share in list order, then an xor-shuffle tree,
+ * then, in the block form, the wave partials in order; no floating-point atomics, no fused
+ * multiply-adds (DESIGN.md "Message aggregation").  Hence count, min, max and every summary
+ * integer except rows_* are a function of the inputs alone (min prefers -0.0 to +0.0, max the
+ * reverse); sum is bit-identical across calls and handles with the same boundaries, and across
+ * input edge orders whenever parallel edges carry equal messages (any program that reads no edge
+ * column).  With finite columns a NaN message can only come from overflow; min and max are then
+ * unspecified.  All working memory is stream-ordered temporaries, the labels and every other
+ * piece of lpa_step's state are neither read nor written, nothing is kept on the handle.  On a
+ * distributed job (nranks > 1) only rank 0 keeps the edge list this needs; the other ranks return
+ * LPA_EINVAL.  Since ABI 20.
+ */
+#define LPA_AM_MAX_OPS 64
+#define LPA_AM_MAX_STACK 8
+#define LPA_AM_MAX_CONSTS 16
+#define LPA_AM_MAX_COLUMNS 8   /* vertex columns, and edge columns, of one call */
+enum {
+  LPA_AM_CONST = 0, LPA_AM_SRC = 1, LPA_AM_DST = 2, LPA_AM_EDGE = 3,
+  LPA_AM_ADD = 4, LPA_AM_SUB = 5, LPA_AM_MUL = 6, LPA_AM_DIV = 7,
+  LPA_AM_NEG = 8, LPA_AM_ABS = 9,
+  LPA_AM_EQ = 10, LPA_AM_NE = 11, LPA_AM_LT = 12, LPA_AM_LE = 13, LPA_AM_GT = 14, LPA_AM_GE = 15,
+  LPA_AM_AND = 16, LPA_AM_OR = 17, LPA_AM_NOT = 18,
+  LPA_AM_WHEN = 19, LPA_AM_WHEN_ELSE = 20,
+  LPA_AM_NOPS = 21
+};
+typedef struct lpa_am_program {
+  int32_t n_ops, n_consts;
+  uint32_t ops[LPA_AM_MAX_OPS];       /* opcode | argument << 16                               */
+  double consts[LPA_AM_MAX_CONSTS];
+} lpa_am_program;          /* 392 bytes */
+typedef struct lpa_am_summary {
+  int64_t edges;             /* valid input edge rows                                         */
+  int64_t messages_to_src;   /* delivered (non-null) messages, by direction                   */
+  int64_t messages_to_dst;
+  int64_t nulls;             /* evaluated and not delivered                                   */
+  int64_t receivers;         /* vertices with count > 0                                       */
+  int64_t rows_short, rows_wave, rows_block;   /* vertices by kernel form                     */
+  int64_t max_row;           /* the longest message list                                      */
+} lpa_am_summary;          /* 72 bytes */
+int lpa_aggregate_messages(lpa_graph* g, const lpa_am_program* to_src /* nullable */,
+                           const lpa_am_program* to_dst /* nullable */,
+                           const double* vcols /* host [n_vcols][V] */, int32_t n_vcols,
+                           const double* ecols /* host [n_ecols][m] */, int32_t n_ecols,
+                           int64_t* count_out /* host [V], nullable */, double* sum_out /* nullable */,
+                           double* min_out /* nullable */, double* max_out /* nullable */,
+                           lpa_am_summary* summary /* nullable */);
+
 /* Symmetrised degree of every vertex (dense ids), host output. */
 int lpa_degrees(lpa_graph* g, int32_t* deg_out);
 
@@ -783,8 +864,9 @@ int lpa_degrees(lpa_graph* g, int32_t* deg_out);
  * ABI 17: fill_refreshes.
  * ABI 18: lpa_bfs.
  * ABI 19: lpa_motif, lpa_motif_rows, lpa_motif_vertex_column, lpa_motif_edge_column,
- *         lpa_motif_result_destroy. */
-#define LPA_ABI_VERSION 19
+ *         lpa_motif_result_destroy.
+ * ABI 20: lpa_aggregate_messages. */
+#define LPA_ABI_VERSION 20
 int lpa_abi_version(void);
 int lpa_graph_get_info(const lpa_graph* g, lpa_graph_info* info);
 int lpa_graph_get_info_sized(const lpa_graph* g, lpa_graph_info* info, int64_t info_size);
