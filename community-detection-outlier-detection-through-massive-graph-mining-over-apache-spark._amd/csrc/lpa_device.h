@@ -130,6 +130,106 @@ __device__ __forceinline__ u64 wave_max_u64_split(u64 v) {
   return ((u64)hi << 32) | lo;
 }
 
+__device__ __forceinline__ int64_t readlane_i64(int64_t x, int l) {
+  return (int64_t)readlane_u64((u64)x, l);
+}
+
+// ---------------------------------------------------------------------------
+// Row spans: a wave that owns one long row reads the row's elements [i0, last] of an
+// array (bit words, per-unit counts) K x 64 at a time.  span_load issues the loads of one
+// step back to back and the caller masks by span_idx after them -- so the first use waits
+// once and the K loads are in flight together, where a `for (i = i0 + lane; i <= last;
+// i += 64)` loop pays one memory latency per 64 elements.  Inside the row's last round an
+// index past `last` is clamped to `last` (in bounds); a round that lies past `last`
+// altogether is not issued (a uniform branch: i0 and last are the same in every lane) and
+// reads as 0 -- most hub rows are short, and K clamped rounds for a row that needs one
+// measured slower than the loop they replaced (rejected table of round 13).
+// The lanes address the row by a 32-bit offset from its uniform base, one register per
+// load.  The row must not be empty (last >= i0 for the first step) and shorter than 2^31.
+// ---------------------------------------------------------------------------
+constexpr int kSpanK = 8;
+template <int K, typename T>
+__device__ __forceinline__ void span_load(T (&x)[K], const T* __restrict__ p, int64_t i0, int64_t last,
+                                          int lane) {
+  const T* __restrict__ row = p + i0;   // uniform
+  const int64_t n1 = last - i0;         // uniform: the last element's offset; < 0 past the row
+  const u32 cap = (u32)(n1 > 0 ? n1 : 0);
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    x[k] = T(0);
+    if ((int64_t)k * 64 <= n1) {        // uniform
+      const u32 o = (u32)(k * 64 + lane);
+      x[k] = row[o < cap ? o : cap];
+    }
+  }
+}
+// element k of this lane in the step at i0: its index, and whether it lies inside the row
+__device__ __forceinline__ int64_t span_idx(int64_t i0, int k, int lane) { return i0 + k * 64 + lane; }
+
+// Bounds off[v], off[v + 1] of 64 rows of a wave in one load pair per lane: lane k holds
+// row v0 + k * stride (0, 0 past n).  A row takes its bounds by readlane (span_pair_at),
+// so they are in registers long before the row's turn and no bounds load sits between
+// two rows' span loads (as span_batch for the wave bins).
+struct SpanPair {
+  int64_t b, e;
+};
+__device__ __forceinline__ SpanPair span_pair_batch(const int64_t* __restrict__ off, int64_t v0, int64_t stride,
+                                                    int64_t n, int lane) {
+  SpanPair s;
+  s.b = s.e = 0;
+  const int64_t v = v0 + (int64_t)lane * stride;
+  if (v < n) {
+    s.b = off[v];
+    s.e = off[v + 1];
+  }
+  return s;
+}
+__device__ __forceinline__ SpanPair span_pair_at(const SpanPair& s, int q) {
+  SpanPair r;
+  r.b = readlane_i64(s.b, q);
+  r.e = readlane_i64(s.e, q);
+  return r;
+}
+
+// A hub row's giant-decision sums over its units [u0, u1) (k_lpa_units_giant /
+// k_lpa_units_code2 left ugc[u] = the unit's G votes, umx[u] = its rivals' bound): wave
+// sums of ugc (sg) and of umx, whole (sm) and as the three 10-bit bucket counts of the
+// 2-bit codes (s1..s3).  Each is at most the row's degree (< 2^31), so 32 bits hold it.
+// Called by a full wave; 2 x kSpanK loads in flight per 512 units.
+struct UnitSums {
+  u32 sg, sm, s1, s2, s3;
+};
+__device__ __forceinline__ UnitSums span_unit_sums(const uint32_t* __restrict__ ugc,
+                                                   const uint32_t* __restrict__ umx, int64_t u0, int64_t u1,
+                                                   int lane) {
+  constexpr int K = kSpanK;
+  UnitSums r = {0u, 0u, 0u, 0u, 0u};
+  if (u1 > u0) {  // uniform (a hub row has >= 2 units; span_load needs a last element)
+#pragma unroll 1
+    for (int64_t i0 = u0; i0 < u1; i0 += K * 64) {
+      u32 g[K], m[K];
+      span_load<K>(g, ugc, i0, u1 - 1, lane);
+      span_load<K>(m, umx, i0, u1 - 1, lane);
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const bool in = span_idx(i0, k, lane) < u1;
+        const u32 mm = in ? m[k] : 0u;
+        r.sg += in ? g[k] : 0u;
+        r.sm += mm;
+        r.s1 += mm & 1023u;
+        r.s2 += (mm >> 10) & 1023u;
+        r.s3 += mm >> 20;
+      }
+    }
+  }
+  r.sg = wave_sum_u32(r.sg);
+  r.sm = wave_sum_u32(r.sm);
+  r.s1 = wave_sum_u32(r.s1);
+  r.s2 = wave_sum_u32(r.s2);
+  r.s3 = wave_sum_u32(r.s3);
+  return r;
+}
+
 __device__ __forceinline__ u32 hash_slot(u32 label, int shift) {
   return (label * 0x9E3779B1u) >> shift;
 }

@@ -222,50 +222,34 @@ __global__ __launch_bounds__(256) void k_hub_decide(int64_t h_end, const int64_t
   if (!on) return;  // uniform: k_lpa_units_giant counted nothing
   const bool code = gsel[GW_CODE] != 0;   // uniform
   const int64_t ha = hb2 < h_end ? hb2 : h_end;
-  for (int64_t h = (int64_t)blockIdx.x * 4 + w; h < ha; h += stride) {
-    const int64_t u0 = uoff[h];
-    const int nu = (int)(uoff[h + 1] - u0);
-    u64 sg = 0, sm = 0;
-    if (code) {
-      u64 s1 = 0, s2 = 0, s3 = 0;
-      for (int j = lane; j < nu; j += 64) {
-        const u32 m = umx[u0 + j];
-        sg += ugc[u0 + j];
-        s1 += m & 1023u;
-        s2 += (m >> 10) & 1023u;
-        s3 += m >> 20;
+  // (the row's unit counts through span_unit_sums, its bounds by 64-row batches: the longest
+  // row's 1.4K units at C3 are 3 rounds of 16 loads, not 23 rounds of two)
+  for (int64_t hb = (int64_t)blockIdx.x * 4 + w; hb < ha; hb += 64 * stride) {
+    const SpanPair ub = span_pair_batch(uoff, hb, stride, ha, lane);
+#pragma unroll 1
+    for (int p = 0; p < 64; ++p) {
+      const int64_t h = hb + (int64_t)p * stride;
+      if (h >= ha) break;  // uniform
+      const SpanPair ur = span_pair_at(ub, p);
+      const int64_t u0 = ur.b;
+      const int nu = (int)(ur.e - u0);
+      const UnitSums us = span_unit_sums(ugc, umx, u0, ur.e, lane);
+      const u32 sg = us.sg;
+      const u32 sm = code ? max(us.s1, max(us.s2, us.s3)) : us.sm;
+      if (sg > sm) {
+        if (lane == 0) {
+          Ln[h] = G;
+          wcount[h] = -1;
+        }
+      } else {
+        int base = 0;
+        if (lane == 0) {
+          wcount[h] = 0;
+          base = atomicAdd(&ndec[GD_UNITS], nu);
+        }
+        base = __shfl(base, 0, 64);
+        for (int j = lane; j < nu; j += 64) ulist2[base + j] = (int32_t)(u0 + j);
       }
-      for (int off = 32; off > 0; off >>= 1) {
-        sg += __shfl_xor(sg, off, 64);
-        s1 += __shfl_xor(s1, off, 64);
-        s2 += __shfl_xor(s2, off, 64);
-        s3 += __shfl_xor(s3, off, 64);
-      }
-      sm = s1 > s2 ? s1 : s2;
-      sm = sm > s3 ? sm : s3;
-    } else {
-      for (int j = lane; j < nu; j += 64) {
-        sg += ugc[u0 + j];
-        sm += umx[u0 + j];
-      }
-      for (int off = 32; off > 0; off >>= 1) {
-        sg += __shfl_xor(sg, off, 64);
-        sm += __shfl_xor(sm, off, 64);
-      }
-    }
-    if (sg > sm) {
-      if (lane == 0) {
-        Ln[h] = G;
-        wcount[h] = -1;
-      }
-    } else {
-      int base = 0;
-      if (lane == 0) {
-        wcount[h] = 0;
-        base = atomicAdd(&ndec[GD_UNITS], nu);
-      }
-      base = __shfl(base, 0, 64);
-      for (int j = lane; j < nu; j += 64) ulist2[base + j] = (int32_t)(u0 + j);
     }
   }
   // block-tier rows: a lane per row
@@ -1276,10 +1260,16 @@ int build_hub_tables(lpa_graph* g, const int32_t* deg_own) {
 // k_hub_decide over the unit-tallied rows [0, h_end), then the exact unit tally of the
 // units it listed (k_lpa_units in list mode, launched by the caller's lambda)
 int launch_hub_decide(lpa_graph* g, int32_t* Lown, int64_t h_end, const int32_t* gsel) {
+  return launch_hub_decide_rows(g->stream, h_end, g->hub_uoff, g->ugc, g->umx, gsel, Lown, g->hub_wcount,
+                                g->ulist2, g->gdec, block_rows_begin(g), g->glist);
+}
+
+int launch_hub_decide_rows(hipStream_t s, int64_t h_end, const int64_t* uoff, const uint32_t* ugc,
+                           const uint32_t* umx, const int32_t* gsel, int32_t* Ln, int32_t* wcount,
+                           int32_t* ulist2, int32_t* ndec, int64_t hb2, int32_t* glist, int max_blocks) {
   if (h_end <= 0) return LPA_OK;
-  hipLaunchKernelGGL(k_hub_decide, dim3(grid_cap((h_end + 3) / 4, 2048)), dim3(256), 0, g->stream, h_end,
-                     g->hub_uoff, g->ugc, g->umx, gsel, Lown, g->hub_wcount, g->ulist2, g->gdec,
-                     block_rows_begin(g), g->glist);
+  hipLaunchKernelGGL(k_hub_decide, dim3(grid_cap((h_end + 3) / 4, max_blocks > 0 ? max_blocks : 2048)), dim3(256),
+                     0, s, h_end, uoff, ugc, umx, gsel, Ln, wcount, ulist2, ndec, hb2, glist);
   LPA_HIP(hipGetLastError());
   return LPA_OK;
 }

@@ -617,6 +617,19 @@ int build_hub_tables(lpa_graph* g, const int32_t* deg_own);  // lpa_hub.hip
 int launch_hub_combine(lpa_graph* g, int32_t* Lown, bool fork, bool join = true,
                        bool giant = false);  // lpa_hub.hip
 int launch_hub_decide(lpa_graph* g, int32_t* Lown, int64_t h_end, const int32_t* gsel);  // lpa_hub.hip
+// The hub-row kernels that read a whole row per wave (the row-span loads of lpa_device.h) on
+// plain device arrays: the schedule's own launches go through these, and so does
+// tools/microbench/hub_rows_check.hip.  max_blocks = 0: the schedule's grid cap (2048).
+int launch_hub_decide_rows(hipStream_t s, int64_t h_end, const int64_t* uoff, const uint32_t* ugc,
+                           const uint32_t* umx, const int32_t* gsel, int32_t* Ln, int32_t* wcount,
+                           int32_t* ulist2, int32_t* ndec, int64_t hb2, int32_t* glist,
+                           int max_blocks = 0);  // lpa_hub.hip
+int launch_settle_big(hipStream_t s, const int64_t* rp, const u64* abits, int64_t n_hub, const int32_t* fr_all,
+                      const int32_t* gword, int32_t* Ln, uint8_t* rdirty, uint8_t* udirty, const int64_t* uoff,
+                      int max_blocks = 0);  // lpa_iter.hip
+int launch_code_settle_hubs(hipStream_t s, const int64_t* uoff, const uint32_t* ugc, const uint32_t* umx,
+                            int64_t n_hub, const int32_t* gword, int32_t* Ln, uint8_t* rdirty, uint8_t* udirty,
+                            int max_blocks = 0);  // lpa_iter.hip
 // (the phases of the schedule, block_mode_now / fused_now / ...: lpa_schedule.h)
 
 // refresh stage (lpa_refresh.hip)

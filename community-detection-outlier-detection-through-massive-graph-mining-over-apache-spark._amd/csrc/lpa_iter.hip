@@ -542,10 +542,6 @@ __device__ __forceinline__ SpanBatch span_batch(const int64_t* __restrict__ rp, 
   }
   return sb;
 }
-__device__ __forceinline__ int64_t readlane_i64(int64_t x, int l) {
-  return (int64_t)(((u64)(u32)__builtin_amdgcn_readlane((int)(u32)((u64)x >> 32), l) << 32) |
-                   (u64)(u32)__builtin_amdgcn_readlane((int)(u32)(u64)x, l));
-}
 // item q of the two batches (q < 64: cur, else nxt; uniform).  A branch, not a select:
 // readlane is convergent (not speculated), so the cur side never waits for nxt's load.
 __device__ __forceinline__ RowSpan span_at(const SpanBatch& cur, const SpanBatch& nxt, int q) {
@@ -1699,30 +1695,75 @@ __device__ __forceinline__ unsigned long long range_mask(int64_t x, int64_t w0, 
   return m;
 }
 
-// hub rows [0, n_hub) (> 1024 arcs): one wave per row
-__global__ __launch_bounds__(256) void k_settle_big(const int64_t* __restrict__ rp,
+// hub rows [0, n_hub) (> 1024 arcs, never empty): one wave per row, kSettleRows rows of a
+// wave in flight.  The wave's row and unit bounds come by 64-row batches (span_pair_batch);
+// the first kSettleK x 64 bit words of each of the next kSettleRows rows (16,384 arcs: the
+// whole row for 99 % of C3's hub rows) are issued together, then each row is counted in turn
+// -- the kernel was bound by the rows a wave takes one after the other (~12 at C3), one
+// memory latency each, not by the loads inside a row.  A longer row goes on with
+// kSpanK x 64 words a step (the longest row at C3, 11.5K words: 23 latency rounds of 8
+// loads; two steps at once needed 139 VGPRs, or spills at four waves per SIMD).
+constexpr int kSettleRows = 4;
+constexpr int kSettleK = 4;
+__global__ __launch_bounds__(256, 4) void k_settle_big(const int64_t* __restrict__ rp,
                                                     const unsigned long long* __restrict__ abits, int64_t n_hub,
                                                     const int32_t* __restrict__ fr_all,
                                                     const int32_t* __restrict__ gword, int32_t* __restrict__ Ln,
                                                     uint8_t* __restrict__ rdirty, uint8_t* __restrict__ udirty,
                                                     const int64_t* __restrict__ uoff) {
   if (!settle_on(fr_all, gword)) return;  // uniform
+  constexpr int K = kSpanK, R = kSettleRows, KF = kSettleK;
+  static_assert(64 % R == 0, "a bounds batch holds whole groups of rows");
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int32_t G = gword[GW_G];
-  for (int64_t v = (int64_t)blockIdx.x * 4 + w; v < n_hub; v += (int64_t)gridDim.x * 4) {
-    const int64_t a = rp[v], b = rp[v + 1];
-    const int64_t w0 = a >> 6, w1 = (b - 1) >> 6;
-    u32 c = 0;
-    for (int64_t x = w0 + lane; x <= w1; x += 64) c += (u32)__popcll(abits[x] & range_mask(x, w0, w1, a, b));
-    c = wave_sum_u32(c);
-    const bool settled = 2 * (int64_t)c > b - a;
-    if (lane == 0) {
-      if (settled) Ln[v] = G;
-      rdirty[v] = settled ? 0 : 1;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t vb = (int64_t)blockIdx.x * 4 + w; vb < n_hub; vb += 64 * stride) {
+    const SpanPair rb = span_pair_batch(rp, vb, stride, n_hub, lane);
+    const SpanPair ub = span_pair_batch(uoff, vb, stride, n_hub, lane);
+#pragma unroll 1
+    for (int p = 0; p < 64; p += R) {
+      if (vb + (int64_t)p * stride >= n_hub) break;  // uniform
+      // rows p .. p + R - 1 of the batch; past n_hub row p again (loaded, not counted)
+      SpanPair r[R];
+      unsigned long long first[R][KF];
+#pragma unroll
+      for (int q = 0; q < R; ++q) {
+        const bool live = vb + (int64_t)(p + q) * stride < n_hub;
+        r[q] = span_pair_at(rb, live ? p + q : p);
+        span_load<KF>(first[q], abits, r[q].b >> 6, (r[q].e - 1) >> 6, lane);
+      }
+#pragma unroll
+      for (int q = 0; q < R; ++q) {
+        const int64_t v = vb + (int64_t)(p + q) * stride;
+        if (v >= n_hub) break;  // uniform
+        const int64_t a = r[q].b, b = r[q].e;
+        const int64_t w0 = a >> 6, w1 = (b - 1) >> 6;
+        u32 c = 0;
+        auto count = [&](unsigned long long wd, int64_t x) {
+          const unsigned long long m = x <= w1 ? range_mask(x, w0, w1, a, b) : 0ull;
+          c += (u32)__popcll(wd & m);
+        };
+#pragma unroll
+        for (int k = 0; k < KF; ++k) count(first[q][k], span_idx(w0, k, lane));
+#pragma unroll 1
+        for (int64_t x0 = w0 + KF * 64; x0 <= w1; x0 += K * 64) {
+          unsigned long long s0[K];
+          span_load<K>(s0, abits, x0, w1, lane);
+#pragma unroll
+          for (int k = 0; k < K; ++k) count(s0[k], span_idx(x0, k, lane));
+        }
+        c = wave_sum_u32(c);
+        const bool settled = 2 * (int64_t)c > b - a;
+        if (lane == 0) {
+          if (settled) Ln[v] = G;
+          rdirty[v] = settled ? 0 : 1;
+        }
+        const uint8_t f = settled ? 0 : 1;
+        const SpanPair ur = span_pair_at(ub, p + q);
+        for (int64_t u = ur.b + lane; u < ur.e; u += 64) udirty[u] = f;
+      }
     }
-    const uint8_t f = settled ? 0 : 1;
-    for (int64_t u = uoff[v] + lane; u < uoff[v + 1]; u += 64) udirty[u] = f;
   }
 }
 
@@ -2110,29 +2151,25 @@ __global__ __launch_bounds__(256) void k_code_settle_hubs(const int64_t* __restr
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int32_t G = gword[GW_G];
-  for (int64_t h = (int64_t)blockIdx.x * 4 + w; h < n_hub; h += (int64_t)gridDim.x * 4) {
-    const int64_t u0 = uoff[h], u1 = uoff[h + 1];
-    u64 sg = 0, s1 = 0, s2 = 0, s3 = 0;   // umx: three bucket counts (k_lpa_units_code2)
-    for (int64_t u = u0 + lane; u < u1; u += 64) {
-      const u32 m = umx[u];
-      sg += ugc[u];
-      s1 += m & 1023u;
-      s2 += (m >> 10) & 1023u;
-      s3 += m >> 20;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t hb = (int64_t)blockIdx.x * 4 + w; hb < n_hub; hb += 64 * stride) {
+    const SpanPair ub = span_pair_batch(uoff, hb, stride, n_hub, lane);
+#pragma unroll 1
+    for (int p = 0; p < 64; ++p) {
+      const int64_t h = hb + (int64_t)p * stride;
+      if (h >= n_hub) break;  // uniform
+      const SpanPair ur = span_pair_at(ub, p);
+      const int64_t u0 = ur.b, u1 = ur.e;
+      // umx: three bucket counts (k_lpa_units_code2)
+      const UnitSums us = span_unit_sums(ugc, umx, u0, u1, lane);
+      const bool settled = us.sg > us.s1 && us.sg > us.s2 && us.sg > us.s3;
+      if (lane == 0) {
+        if (settled) Ln[h] = G;
+        rdirty[h] = settled ? 0 : 1;
+      }
+      const uint8_t f = settled ? 0 : 1;
+      for (int64_t u = u0 + lane; u < u1; u += 64) udirty[u] = f;
     }
-    for (int off = 32; off > 0; off >>= 1) {
-      sg += __shfl_xor(sg, off, 64);
-      s1 += __shfl_xor(s1, off, 64);
-      s2 += __shfl_xor(s2, off, 64);
-      s3 += __shfl_xor(s3, off, 64);
-    }
-    const bool settled = sg > s1 && sg > s2 && sg > s3;
-    if (lane == 0) {
-      if (settled) Ln[h] = G;
-      rdirty[h] = settled ? 0 : 1;
-    }
-    const uint8_t f = settled ? 0 : 1;
-    for (int64_t u = u0 + lane; u < u1; u += 64) udirty[u] = f;
   }
 }
 
@@ -2498,10 +2535,8 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
         LPA_HIP(hipStreamWaitEvent(sb, g->ev_fork, 0));
       }
       if (g->n_hub > 0) {
-        hipLaunchKernelGGL(k_settle_big, dim3(cap_grid((g->n_hub + 3) / 4, 2048)), dim3(256), 0, s, g->rp,
-                           g->abits, g->n_hub, fr_all, g->gword, Lown, g->rdirty[g->par], g->udirty[g->par],
-                           g->hub_uoff);
-        LPA_HIP(hipGetLastError());
+        LPA_TRY(launch_settle_big(s, g->rp, g->abits, g->n_hub, fr_all, g->gword, Lown, g->rdirty[g->par],
+                                  g->udirty[g->par], g->hub_uoff));
       }
       if (r1 > r0) {
         hipLaunchKernelGGL(k_settle_rows, dim3(cap_grid((r1 - r0 + 255) / 256, 8192)), dim3(256), 0,
@@ -2524,10 +2559,8 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
         hipLaunchKernelGGL(k_lpa_units_code2, dim3(cap_grid((g->n_segs + 3) / 4, 2048)), dim3(256), 0, s,
                            g->al2, g->segs, g->n_segs, g->gword, g->ugc, g->umx, g->gdec);
         LPA_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_code_settle_hubs, dim3(cap_grid((g->n_hub + 3) / 4, 2048)), dim3(256), 0, s,
-                           g->hub_uoff, g->ugc, g->umx, g->n_hub, g->gword, Lown, g->rdirty[g->par],
-                           g->udirty[g->par]);
-        LPA_HIP(hipGetLastError());
+        LPA_TRY(launch_code_settle_hubs(s, g->hub_uoff, g->ugc, g->umx, g->n_hub, g->gword, Lown,
+                                        g->rdirty[g->par], g->udirty[g->par]));
       }
       LPA_TRY(launch_code_settle(g, s, Lown));
       hipLaunchKernelGGL(k_code_commit, dim3(1), dim3(64), 0, s, const_cast<int32_t*>(fr_all), g->gword, fcnt);
@@ -2884,6 +2917,27 @@ int launch_tally(lpa_graph* g, int32_t* Lown, hipEvent_t* bev, const int32_t* Lc
 }
 
 }  // namespace
+
+// the hub-row settles of superstep 3 on plain device arrays (the superstep's own launches, and
+// tools/microbench/hub_rows_check.hip); max_blocks = 0: the schedule's grid cap
+int launch_settle_big(hipStream_t s, const int64_t* rp, const u64* abits, int64_t n_hub, const int32_t* fr_all,
+                      const int32_t* gword, int32_t* Ln, uint8_t* rdirty, uint8_t* udirty, const int64_t* uoff,
+                      int max_blocks) {
+  if (n_hub <= 0) return LPA_OK;
+  hipLaunchKernelGGL(k_settle_big, dim3(cap_grid((n_hub + 3) / 4, max_blocks > 0 ? max_blocks : 2048)), dim3(256), 0,
+                     s, rp, abits, n_hub, fr_all, gword, Ln, rdirty, udirty, uoff);
+  LPA_HIP(hipGetLastError());
+  return LPA_OK;
+}
+int launch_code_settle_hubs(hipStream_t s, const int64_t* uoff, const uint32_t* ugc, const uint32_t* umx,
+                            int64_t n_hub, const int32_t* gword, int32_t* Ln, uint8_t* rdirty, uint8_t* udirty,
+                            int max_blocks) {
+  if (n_hub <= 0) return LPA_OK;
+  hipLaunchKernelGGL(k_code_settle_hubs, dim3(cap_grid((n_hub + 3) / 4, max_blocks > 0 ? max_blocks : 2048)),
+                     dim3(256), 0, s, uoff, ugc, umx, n_hub, gword, Ln, rdirty, udirty);
+  LPA_HIP(hipGetLastError());
+  return LPA_OK;
+}
 
 // Capture `body` (launches on the handle's stream and the streams it forks) into an
 // executable graph.  Captures are serialised process-wide (several handles of one
