@@ -173,6 +173,29 @@ class LpaAmSummary(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+LPA_PG_MAX_COLUMNS = 4    # Pregel columns of one call
+LPA_PG_MAX_MESSAGES = 4   # message programs of one direction
+# the aggregates of lpa_pregel (include/lpa.h LPA_PG_*), by value
+PG_AGGREGATES = ("sum", "min", "max", "avg", "count")
+# opcodes of a vertex program (include/lpa.h LPA_VP_*), by value
+VP_OPCODES = ("const", "col", "msg", "add", "sub", "mul", "div", "neg", "abs", "eq", "ne", "lt", "le", "gt", "ge",
+              "and", "or", "not", "when", "when_else", "coalesce", "isnull")
+
+
+class LpaVpProgram(ctypes.Structure):
+    _fields_ = [("n_ops", ctypes.c_int32), ("n_consts", ctypes.c_int32), ("ops", ctypes.c_uint32 * LPA_AM_MAX_OPS),
+                ("consts", ctypes.c_double * LPA_AM_MAX_CONSTS)]
+
+
+class LpaPregelSummary(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int64) for k in ("edges", "messages_to_src", "messages_to_dst", "nulls", "rows_short",
+                                              "rows_wave", "rows_block", "max_row", "iterations", "null_iteration",
+                                              "null_column", "null_vertex")]
+
+    def to_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("null_")}
+
+
 class LpaSccSummary(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in ("n_components", "n_singletons", "largest_size", "largest_id",
                                               "rounds", "trimmed", "unresolved")]
@@ -264,6 +287,10 @@ SIGNATURES = {
     "lpa_aggregate_messages": (ctypes.c_int, [_vp, ctypes.POINTER(LpaAmProgram), ctypes.POINTER(LpaAmProgram), _vp,
                                               ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp,
                                               ctypes.POINTER(LpaAmSummary)]),
+    "lpa_pregel": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(LpaAmProgram), ctypes.c_int32,
+                                  ctypes.POINTER(LpaAmProgram), ctypes.c_int32, ctypes.POINTER(LpaVpProgram),
+                                  ctypes.POINTER(LpaVpProgram), ctypes.c_int32, _vp, ctypes.c_int32, _vp,
+                                  ctypes.c_int32, _vp, ctypes.POINTER(LpaPregelSummary)]),
     "lpa_strongly_connected_components": (ctypes.c_int, [_vp, ctypes.c_int32, _vp, ctypes.c_int32, _vp,
                                                          ctypes.POINTER(LpaSccSummary)]),
     "lpa_louvain": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int32, _vp,

@@ -905,15 +905,16 @@ int lpa_motif(lpa_graph* g, int32_t n_vars, const uint8_t* var_out, const lpa_mo
   return LPA_OK;
 }
 
-// A message program as lpa_aggregate_messages takes it (include/lpa.h): false with the error set
-static bool am_program_ok(const lpa_am_program* p, const char* name, int32_t n_vcols, int32_t n_ecols,
-                          bool* reads_v, bool* reads_e) {
+// A message program as lpa_aggregate_messages and lpa_pregel (fn) take it (include/lpa.h): false with
+// the error set
+static bool am_program_ok(const char* fn, const lpa_am_program* p, const char* name, int32_t n_vcols,
+                          int32_t n_ecols, bool* reads_v, bool* reads_e) {
   if (p->n_ops < 1 || p->n_ops > LPA_AM_MAX_OPS) {
-    set_error("lpa_aggregate_messages: %s has %d ops, outside [1, %d]", name, p->n_ops, LPA_AM_MAX_OPS);
+    set_error("%s: %s has %d ops, outside [1, %d]", fn, name, p->n_ops, LPA_AM_MAX_OPS);
     return false;
   }
   if (p->n_consts < 0 || p->n_consts > LPA_AM_MAX_CONSTS) {
-    set_error("lpa_aggregate_messages: %s has %d constants, outside [0, %d]", name, p->n_consts, LPA_AM_MAX_CONSTS);
+    set_error("%s: %s has %d constants, outside [0, %d]", fn, name, p->n_consts, LPA_AM_MAX_CONSTS);
     return false;
   }
   int depth = 0;
@@ -924,7 +925,7 @@ static bool am_program_ok(const lpa_am_program* p, const char* name, int32_t n_v
       case LPA_AM_CONST:
         pops = 0;
         if ((int32_t)arg >= p->n_consts) {
-          set_error("lpa_aggregate_messages: %s op %d reads constant %u of %d", name, i, arg, p->n_consts);
+          set_error("%s: %s op %d reads constant %u of %d", fn, name, i, arg, p->n_consts);
           return false;
         }
         break;
@@ -933,7 +934,7 @@ static bool am_program_ok(const lpa_am_program* p, const char* name, int32_t n_v
         pops = 0;
         *reads_v = true;
         if ((int32_t)arg >= n_vcols) {
-          set_error("lpa_aggregate_messages: %s op %d reads vertex column %u of %d", name, i, arg, n_vcols);
+          set_error("%s: %s op %d reads vertex column %u of %d", fn, name, i, arg, n_vcols);
           return false;
         }
         break;
@@ -941,7 +942,7 @@ static bool am_program_ok(const lpa_am_program* p, const char* name, int32_t n_v
         pops = 0;
         *reads_e = true;
         if ((int32_t)arg >= n_ecols) {
-          set_error("lpa_aggregate_messages: %s op %d reads edge column %u of %d", name, i, arg, n_ecols);
+          set_error("%s: %s op %d reads edge column %u of %d", fn, name, i, arg, n_ecols);
           return false;
         }
         break;
@@ -955,23 +956,23 @@ static bool am_program_ok(const lpa_am_program* p, const char* name, int32_t n_v
         break;
       default:
         if (op >= LPA_AM_NOPS) {
-          set_error("lpa_aggregate_messages: %s op %d has the unknown opcode %u", name, i, op);
+          set_error("%s: %s op %d has the unknown opcode %u", fn, name, i, op);
           return false;
         }
         break;
     }
     if (depth < pops) {
-      set_error("lpa_aggregate_messages: %s op %d underflows the stack (%d values, %d needed)", name, i, depth, pops);
+      set_error("%s: %s op %d underflows the stack (%d values, %d needed)", fn, name, i, depth, pops);
       return false;
     }
     depth += 1 - pops;
     if (depth > LPA_AM_MAX_STACK) {
-      set_error("lpa_aggregate_messages: %s op %d overflows the stack of %d values", name, i, LPA_AM_MAX_STACK);
+      set_error("%s: %s op %d overflows the stack of %d values", fn, name, i, LPA_AM_MAX_STACK);
       return false;
     }
   }
   if (depth != 1) {
-    set_error("lpa_aggregate_messages: %s leaves %d values on the stack, not 1", name, depth);
+    set_error("%s: %s leaves %d values on the stack, not 1", fn, name, depth);
     return false;
   }
   return true;
@@ -992,8 +993,9 @@ int lpa_aggregate_messages(lpa_graph* g, const lpa_am_program* to_src, const lpa
     return LPA_EINVAL;
   }
   bool reads_v = false, reads_e = false;
-  if (to_src && !am_program_ok(to_src, "to_src", n_vcols, n_ecols, &reads_v, &reads_e)) return LPA_EINVAL;
-  if (to_dst && !am_program_ok(to_dst, "to_dst", n_vcols, n_ecols, &reads_v, &reads_e)) return LPA_EINVAL;
+  const char* fn = "lpa_aggregate_messages";
+  if (to_src && !am_program_ok(fn, to_src, "to_src", n_vcols, n_ecols, &reads_v, &reads_e)) return LPA_EINVAL;
+  if (to_dst && !am_program_ok(fn, to_dst, "to_dst", n_vcols, n_ecols, &reads_v, &reads_e)) return LPA_EINVAL;
   if (!g) {
     set_error("null handle");
     return LPA_EINVAL;
@@ -1011,6 +1013,150 @@ int lpa_aggregate_messages(lpa_graph* g, const lpa_am_program* to_src, const lpa
   // columns no program reads are not uploaded
   return aggregate_messages(g, to_src, to_dst, vcols, reads_v ? n_vcols : 0, ecols, reads_e ? n_ecols : 0, count_out,
                             sum_out, min_out, max_out, summary);
+}
+
+// A vertex program as lpa_pregel takes it (include/lpa.h): false with the error set.  n_cols: the
+// columns COL may read (an init program: the static ones); msg_ok: MSG may appear
+static bool vp_program_ok(const lpa_vp_program* p, const char* name, int32_t n_cols, bool msg_ok) {
+  const char* fn = "lpa_pregel";
+  if (p->n_ops < 1 || p->n_ops > LPA_AM_MAX_OPS) {
+    set_error("%s: %s has %d ops, outside [1, %d]", fn, name, p->n_ops, LPA_AM_MAX_OPS);
+    return false;
+  }
+  if (p->n_consts < 0 || p->n_consts > LPA_AM_MAX_CONSTS) {
+    set_error("%s: %s has %d constants, outside [0, %d]", fn, name, p->n_consts, LPA_AM_MAX_CONSTS);
+    return false;
+  }
+  int depth = 0;
+  for (int i = 0; i < p->n_ops; ++i) {
+    const uint32_t op = p->ops[i] & 0xFFFFu, arg = p->ops[i] >> 16;
+    int pops = 2;
+    switch (op) {
+      case LPA_VP_CONST:
+        pops = 0;
+        if ((int32_t)arg >= p->n_consts) {
+          set_error("%s: %s op %d reads constant %u of %d", fn, name, i, arg, p->n_consts);
+          return false;
+        }
+        break;
+      case LPA_VP_COL:
+        pops = 0;
+        if ((int32_t)arg >= n_cols) {
+          set_error("%s: %s op %d reads vertex column %u of %d%s", fn, name, i, arg, n_cols,
+                    msg_ok ? "" : " (an initial program reads static columns only)");
+          return false;
+        }
+        break;
+      case LPA_VP_MSG:
+        pops = 0;
+        if (!msg_ok) {
+          set_error("%s: %s op %d reads the message, which an initial program cannot", fn, name, i);
+          return false;
+        }
+        break;
+      case LPA_VP_NEG:
+      case LPA_VP_ABS:
+      case LPA_VP_NOT:
+      case LPA_VP_ISNULL:
+        pops = 1;
+        break;
+      case LPA_VP_WHEN_ELSE:
+        pops = 3;
+        break;
+      default:
+        if (op >= LPA_VP_NOPS) {
+          set_error("%s: %s op %d has the unknown opcode %u", fn, name, i, op);
+          return false;
+        }
+        break;
+    }
+    if (depth < pops) {
+      set_error("%s: %s op %d underflows the stack (%d values, %d needed)", fn, name, i, depth, pops);
+      return false;
+    }
+    depth += 1 - pops;
+    if (depth > LPA_AM_MAX_STACK) {
+      set_error("%s: %s op %d overflows the stack of %d values", fn, name, i, LPA_AM_MAX_STACK);
+      return false;
+    }
+  }
+  if (depth != 1) {
+    set_error("%s: %s leaves %d values on the stack, not 1", fn, name, depth);
+    return false;
+  }
+  return true;
+}
+
+int lpa_pregel(lpa_graph* g, int32_t max_iter, int32_t agg, const lpa_am_program* to_src, int32_t n_to_src,
+               const lpa_am_program* to_dst, int32_t n_to_dst, const lpa_vp_program* init,
+               const lpa_vp_program* update, int32_t n_pcols, const double* vcols, int32_t n_vcols,
+               const double* ecols, int32_t n_ecols, double* cols_out, lpa_pregel_summary* summary) {
+  // the counts and the programs first: they are checked without a handle
+  if (max_iter <= 0) {
+    set_error("lpa_pregel: max_iter must be greater than 0, got %d", max_iter);
+    return LPA_EINVAL;
+  }
+  if (agg < 0 || agg >= LPA_PG_NAGGS) {
+    set_error("lpa_pregel: the unknown aggregate %d", agg);
+    return LPA_EINVAL;
+  }
+  if (n_pcols < 1 || n_pcols > LPA_PG_MAX_COLUMNS) {
+    set_error("lpa_pregel: n_pcols must be in [1, %d], got %d", LPA_PG_MAX_COLUMNS, n_pcols);
+    return LPA_EINVAL;
+  }
+  if (n_to_src < 0 || n_to_src > LPA_PG_MAX_MESSAGES || n_to_dst < 0 || n_to_dst > LPA_PG_MAX_MESSAGES) {
+    set_error("lpa_pregel: n_to_src and n_to_dst must be in [0, %d], got %d and %d", LPA_PG_MAX_MESSAGES, n_to_src,
+              n_to_dst);
+    return LPA_EINVAL;
+  }
+  if (n_to_src + n_to_dst == 0) {
+    set_error("lpa_pregel: no message program; to_src, to_dst, or both have to be provided");
+    return LPA_EINVAL;
+  }
+  if (n_vcols < 0 || n_vcols + n_pcols > LPA_AM_MAX_COLUMNS || n_ecols < 0 || n_ecols > LPA_AM_MAX_COLUMNS) {
+    set_error("lpa_pregel: n_vcols + n_pcols and n_ecols must be in [0, %d], got %d + %d and %d", LPA_AM_MAX_COLUMNS,
+              n_vcols, n_pcols, n_ecols);
+    return LPA_EINVAL;
+  }
+  if ((n_to_src > 0 && !to_src) || (n_to_dst > 0 && !to_dst) || !init || !update) {
+    set_error("lpa_pregel: null program array");
+    return LPA_EINVAL;
+  }
+  bool reads_v = false, reads_e = false;
+  char name[32];
+  for (int32_t i = 0; i < n_to_src; ++i) {
+    snprintf(name, sizeof name, "to_src[%d]", i);
+    if (!am_program_ok("lpa_pregel", to_src + i, name, n_vcols + n_pcols, n_ecols, &reads_v, &reads_e))
+      return LPA_EINVAL;
+  }
+  for (int32_t i = 0; i < n_to_dst; ++i) {
+    snprintf(name, sizeof name, "to_dst[%d]", i);
+    if (!am_program_ok("lpa_pregel", to_dst + i, name, n_vcols + n_pcols, n_ecols, &reads_v, &reads_e))
+      return LPA_EINVAL;
+  }
+  for (int32_t j = 0; j < n_pcols; ++j) {
+    snprintf(name, sizeof name, "init[%d]", j);
+    if (!vp_program_ok(init + j, name, n_vcols, false)) return LPA_EINVAL;
+    snprintf(name, sizeof name, "update[%d]", j);
+    if (!vp_program_ok(update + j, name, n_vcols + n_pcols, true)) return LPA_EINVAL;
+  }
+  if (!g) {
+    set_error("null handle");
+    return LPA_EINVAL;
+  }
+  if ((n_vcols > 0 && !vcols) || (reads_e && !ecols) || (g->V > 0 && !cols_out)) {
+    set_error("lpa_pregel: null %s pointer", n_vcols > 0 && !vcols ? "vertex column" : reads_e && !ecols
+                                                                       ? "edge column" : "output");
+    return LPA_EINVAL;
+  }
+  if (g->m > 0 && !g->e_src) {
+    set_error("lpa_pregel of a distributed job runs on rank 0 (the rank that keeps the edge list)");
+    return LPA_EINVAL;
+  }
+  LPA_HIP(hipSetDevice(g->device));
+  // edge columns no program reads are not uploaded
+  return pregel(g, max_iter, agg, to_src, n_to_src, to_dst, n_to_dst, init, update, n_pcols, vcols, n_vcols, ecols,
+                reads_e ? n_ecols : 0, cols_out, summary);
 }
 
 int64_t lpa_motif_rows(const lpa_motif_result* r) { return r ? r->rows : 0; }

@@ -813,6 +813,13 @@ int aggregate_messages(lpa_graph* g, const lpa_am_program* to_src, const lpa_am_
                        int32_t n_vcols, const double* ecols, int32_t n_ecols, int64_t* count_out, double* sum_out,
                        double* min_out, double* max_out, lpa_am_summary* summary);
 
+// Pregel over the directed multigraph (lpa_pregel.hip); the programs and the other arguments are
+// checked by the caller
+int pregel(lpa_graph* g, int32_t max_iter, int32_t agg, const lpa_am_program* to_src, int32_t n_to_src,
+           const lpa_am_program* to_dst, int32_t n_to_dst, const lpa_vp_program* init, const lpa_vp_program* update,
+           int32_t n_pcols, const double* vcols, int32_t n_vcols, const double* ecols, int32_t n_ecols,
+           double* cols_out, lpa_pregel_summary* summary);
+
 // strongly connected components of the directed graph, GraphX's rounds (lpa_scc.hip)
 int strongly_connected_components(lpa_graph* g, int32_t max_iter, int32_t* comp_out, int32_t out_is_device,
                                   int64_t* size_out, lpa_scc_summary* summary);

@@ -41,6 +41,15 @@ def _edge_ptrs(src, dst):
     return s.ctypes.data, d.ctypes.data, int(s.size), 0, (s, d)
 
 
+class PregelNullError(ValueError):
+    """An initial (``iteration`` 0) or updated value of Pregel column ``column`` was null at the
+    dense vertex ``vertex``: a column holds no null."""
+
+    def __init__(self, msg, iteration, column, vertex):
+        super().__init__(msg)
+        self.iteration, self.column, self.vertex = iteration, column, vertex
+
+
 class Graph:
     """A symmetrised, degree-sorted CSR resident in HBM plus its label vectors.
 
@@ -644,24 +653,29 @@ class Graph:
 
     # -- message aggregation ----------------------------------------------------------
     @staticmethod
+    def _program_array(progs, struct, what):
+        """Compiled programs (``ops``, ``consts``) as one C array of the ABI's fixed-size struct."""
+        progs = list(progs)
+        arr = (struct * max(len(progs), 1))()
+        for k, prog in enumerate(progs):
+            ops, consts = list(prog.ops), list(prog.consts)
+            if len(ops) > _lib.LPA_AM_MAX_OPS or len(consts) > _lib.LPA_AM_MAX_CONSTS:
+                raise ValueError(f"a {what} program holds at most {_lib.LPA_AM_MAX_OPS} ops and "
+                                 f"{_lib.LPA_AM_MAX_CONSTS} constants, got {len(ops)} and {len(consts)}")
+            arr[k].n_ops, arr[k].n_consts = len(ops), len(consts)
+            for i, (op, arg) in enumerate(ops):
+                if not 0 <= int(op) <= 0xFFFF or not 0 <= int(arg) <= 0xFFFF:
+                    raise ValueError(f"op {i}: opcode and argument are 16-bit values, got {op} and {arg}")
+                arr[k].ops[i] = int(op) | (int(arg) << 16)
+            for i, c in enumerate(consts):
+                arr[k].consts[i] = float(c)
+        return arr, len(progs)
+
+    @staticmethod
     def _am_program(prog):
         """A compiled message (``ops``: (opcode, argument) pairs, ``consts``: floats) as the C ABI's
         fixed-size struct; ``None`` stays ``None``."""
-        if prog is None:
-            return None
-        ops, consts = list(prog.ops), list(prog.consts)
-        if len(ops) > _lib.LPA_AM_MAX_OPS or len(consts) > _lib.LPA_AM_MAX_CONSTS:
-            raise ValueError(f"a message program holds at most {_lib.LPA_AM_MAX_OPS} ops and "
-                             f"{_lib.LPA_AM_MAX_CONSTS} constants, got {len(ops)} and {len(consts)}")
-        p = _lib.LpaAmProgram()
-        p.n_ops, p.n_consts = len(ops), len(consts)
-        for i, (op, arg) in enumerate(ops):
-            if not 0 <= int(op) <= 0xFFFF or not 0 <= int(arg) <= 0xFFFF:
-                raise ValueError(f"op {i}: opcode and argument are 16-bit values, got {op} and {arg}")
-            p.ops[i] = int(op) | (int(arg) << 16)
-        for i, c in enumerate(consts):
-            p.consts[i] = float(c)
-        return p
+        return None if prog is None else Graph._program_array([prog], _lib.LpaAmProgram, "message")[0][0]
 
     def aggregate_messages(self, to_src, to_dst, vcols=None, ecols=None, stats: bool = False):
         """Message aggregation over the directed input multigraph (lpa_aggregate_messages;
@@ -697,6 +711,59 @@ class Graph:
             vc.ctypes.data if vc.shape[0] else None, vc.shape[0], ec.ctypes.data if ec.shape[0] else None,
             ec.shape[0], out["count"].ctypes.data, out["sum"].ctypes.data, out["min"].ctypes.data,
             out["max"].ctypes.data, ctypes.byref(summ) if stats else None))
+        return (out, summ.to_dict()) if stats else out
+
+    # -- Pregel -----------------------------------------------------------------------
+    def pregel(self, max_iter, agg, to_src, to_dst, init, update, vcols=None, ecols=None, stats: bool = False):
+        """Pregel over the directed input multigraph (lpa_pregel; ``graphframes.lib.Pregel``):
+        ``len(init) == len(update)`` Pregel columns (1 to 4) live on the device for ``max_iter``
+        iterations.  Column j starts as the vertex program ``init[j]``; an iteration evaluates
+        the compiled messages ``to_dst`` (for the destination) and ``to_src`` (for the source)
+        of every input edge (lists of ``compile_message`` results, 0 to 4 each, not both empty),
+        reduces what a vertex receives with ``agg`` (``"sum"``, ``"min"``, ``"max"``, ``"avg"``,
+        ``"count"``) to ``msg`` -- null where nothing arrived -- and sets column j to
+        ``update[j]`` (``compile_vertex_program`` results) over the vertex's old columns and
+        ``msg``, all columns at once.  Column indices: the static columns ``vcols``
+        (``[n_vcols, num_vertices]`` float64) come first, then the Pregel columns; ``ecols`` is
+        ``[n_ecols, num_edges]`` float64 in the handle's input edge order.  Returns the columns
+        after ``max_iter`` iterations, ``[n_pcols, num_vertices]`` float64; with ``stats=True``
+        ``(columns, summary)``, the summary a dict of edges, messages_to_src, messages_to_dst,
+        nulls (all three summed over the iterations), rows_short, rows_wave, rows_block, max_row,
+        iterations.  A null initial or updated value raises ``PregelNullError`` (a
+        ``ValueError`` with ``iteration`` -- 0 for the start --, ``column`` and ``vertex``).
+        With min, max or count the columns depend on the inputs alone; with sum or avg they are
+        bit-identical across calls and handles, and across input edge orders for programs that
+        read no edge column.  The labels and the LPA state are not touched."""
+        V, m = self.num_vertices, self.num_edges
+        if agg not in _lib.PG_AGGREGATES:
+            raise ValueError(f"agg must be one of {', '.join(_lib.PG_AGGREGATES)}, got {agg!r}")
+
+        def cols(x, n, name):
+            if x is None:
+                return np.empty((0, n), dtype=np.float64)
+            a = np.ascontiguousarray(x, dtype=np.float64)
+            if a.ndim != 2 or a.shape[1] != n:
+                raise ValueError(f"{name} must have the shape [columns, {n}], got {list(a.shape)}")
+            return a
+
+        vc, ec = cols(vcols, V, "vcols"), cols(ecols, m, "ecols")
+        if len(init) != len(update):
+            raise ValueError(f"init and update hold one program per Pregel column, got {len(init)} and {len(update)}")
+        ps, n_ps = self._program_array(to_src or (), _lib.LpaAmProgram, "message")
+        pd_, n_pd = self._program_array(to_dst or (), _lib.LpaAmProgram, "message")
+        pi, n_p = self._program_array(init, _lib.LpaVpProgram, "vertex")
+        pu, _ = self._program_array(update, _lib.LpaVpProgram, "vertex")
+        out = np.empty((n_p, V), dtype=np.float64)
+        summ = _lib.LpaPregelSummary()
+        summ.null_iteration = -1   # set by the call only once the arguments have passed
+        rc = self._lib.lpa_pregel(self._handle(), int(max_iter), _lib.PG_AGGREGATES.index(agg), ps, n_ps, pd_, n_pd,
+                                  pi, pu, n_p, vc.ctypes.data if vc.shape[0] else None, vc.shape[0],
+                                  ec.ctypes.data if ec.shape[0] else None, ec.shape[0], out.ctypes.data,
+                                  ctypes.byref(summ))
+        if rc == _lib.LPA_EINVAL and summ.null_iteration >= 0:
+            raise PregelNullError(_lib.last_error(), int(summ.null_iteration), int(summ.null_column),
+                                  int(summ.null_vertex))
+        _lib.check(rc)
         return (out, summ.to_dict()) if stats else out
 
     # -- strongly connected components ------------------------------------------------

@@ -32,7 +32,7 @@ import numpy as np
 import pandas as pd
 
 from . import _lib
-from .graph import Graph
+from .graph import Graph, PregelNullError
 
 ID, SRC, DST, LABEL = "id", "src", "dst", "label"
 COMPONENT = "component"
@@ -400,6 +400,10 @@ _AM_UNARY = {"neg": "-", "not": "~"}
 _AM_BOOL_OPS = ("eq", "ne", "lt", "le", "gt", "ge", "and", "or", "not")
 _AM_COLUMN_KINDS = {"src": "vertex", "dst": "vertex", "edge": "edge"}
 AM_AGGREGATES = ("sum", "min", "max", "avg", "count")
+_VP_OPCODE = {name: i for i, name in enumerate(_lib.VP_OPCODES)}
+_VP_ONLY_OPS = ("col", "coalesce", "isnull")      # nodes of a vertex expression that no message holds
+PREGEL_MAX_COLUMNS = _lib.LPA_PG_MAX_COLUMNS      # Pregel columns of one run
+PREGEL_MAX_MESSAGES = _lib.LPA_PG_MAX_MESSAGES    # sendMsgToSrc, and sendMsgToDst, of one run
 
 
 class MessageExpr:
@@ -504,6 +508,10 @@ class MessageExpr:
             return f"({_AM_UNARY[self.op]}{self.args[0]})"
         if self.op == "abs":
             return f"abs({self.args[0]})"
+        if self.op == "col":
+            return f"col[{self.value!r}]"
+        if self.op in ("coalesce", "isnull"):
+            return f"{self.op}({', '.join(map(str, self.args))})"
         s = f"when({self.args[0]}, {self.args[1]})"
         return s + (f".otherwise({self.args[2]})" if len(self.args) == 3 else "")
 
@@ -641,6 +649,9 @@ def compile_message(expr, vertex_columns=(), edge_columns=()) -> CompiledMessage
     for node in root.walk():
         if node.op == "msg":
             raise ValueError(f"AM.msg appears inside the message {root}: it is what aggCol aggregates")
+        if node.op in _VP_ONLY_OPS:
+            raise ValueError(f"{node} appears inside the message {root}: Pregel.{node.op} belongs to a vertex "
+                             "expression of Pregel.withVertexColumn")
         if node.op == "const":
             bits = np.float64(node.value).tobytes()   # 0.0 and -0.0 are two constants
             at = [np.float64(c).tobytes() for c in consts]
@@ -726,6 +737,274 @@ def _am_prepare(v: pd.DataFrame, e: pd.DataFrame, aggCol, sendToSrc, sendToDst):
     vcols = [_am_column(v, name, "vertex") for name in last.vertex_columns]
     ecols = [_am_column(e, name, "edge") for name in last.edge_columns]
     return agg, to_src, to_dst, vcols, ecols
+
+
+# ---- Pregel: vertex programs and the builder (pure host) ----
+@dataclass(frozen=True)
+class CompiledVertexProgram:
+    """A vertex expression as the postfix program the Pregel kernels interpret (include/lpa.h
+    ``lpa_vp_program``): ``ops`` are (opcode, 16-bit argument) pairs over ``_lib.VP_OPCODES``, the
+    argument an index into ``consts`` or ``columns`` for the opcodes that push."""
+    ops: tuple
+    consts: tuple
+    columns: tuple
+    depth: int
+
+    def decode(self) -> MessageExpr:
+        """The expression back from the program."""
+        st = []
+        for code, arg in self.ops:
+            op = _lib.VP_OPCODES[code]
+            if op == "const":
+                st.append(MessageExpr("const", value=self.consts[arg]))
+            elif op == "col":
+                st.append(MessageExpr("col", value=self.columns[arg]))
+            elif op == "msg":
+                st.append(MessageExpr("msg"))
+            else:
+                n = 1 if op in ("neg", "abs", "not", "isnull") else 3 if op == "when_else" else 2
+                args = st[len(st) - n:]
+                del st[len(st) - n:]
+                st.append(MessageExpr("when" if op == "when_else" else op, args))
+        assert len(st) == 1
+        return st[0]
+
+
+def compile_vertex_program(expr, columns=(), n_static=None, initial=False) -> CompiledVertexProgram:
+    """Compile a vertex expression of Pregel (an initial or an update expression) to its postfix
+    program: operands left to right, then their operator.  ``columns``: the vertex columns of the
+    run in index order, the ``n_static`` static ones (default: all) and then the Pregel columns;
+    ``Pregel.col(name)`` must name one of them.  ``initial=True`` compiles an initial expression,
+    which reads static columns and constants only.  Pure host code.  ``ValueError`` for
+    ``Pregel.src`` / ``dst`` / ``edge`` inside the expression, an unknown column, the message or
+    a Pregel column in an initial expression, and a limit exceeded (AM_MAX_OPS ops, AM_MAX_STACK
+    stack values, AM_MAX_CONSTS constants)."""
+    root = MessageExpr.of(expr)
+    columns = list(columns)
+    n_static = len(columns) if n_static is None else int(n_static)
+    ops, consts = [], []
+    depth = top = 0
+    for node in root.walk():
+        if node.op in _AM_COLUMN_KINDS:
+            raise ValueError(f"{node} appears inside the vertex expression {root}: Pregel.src, Pregel.dst and "
+                             "Pregel.edge belong to a message; a vertex reads its own column with Pregel.col")
+        if node.op == "msg":
+            if initial:
+                raise ValueError(f"the initial expression {root} reads the message: no message exists before the "
+                                 "first iteration")
+            arg, pops = 0, 0
+        elif node.op == "const":
+            bits = np.float64(node.value).tobytes()   # 0.0 and -0.0 are two constants
+            at = [np.float64(c).tobytes() for c in consts]
+            if bits not in at:
+                consts.append(node.value)
+                at.append(bits)
+            arg, pops = at.index(bits), 0
+        elif node.op == "col":
+            if node.value not in columns:
+                raise ValueError(f"the vertex expression {root} reads the column {node.value!r}, which is none of: "
+                                 f"{','.join(map(str, columns))}")
+            arg, pops = columns.index(node.value), 0
+            if initial and arg >= n_static:
+                raise ValueError(f"the initial expression {root} reads the Pregel column {node.value!r}: it may read "
+                                 "columns of the vertex frame and constants only")
+        else:
+            arg, pops = 0, len(node.args)
+        code = "when_else" if node.op == "when" and pops == 3 else node.op
+        ops.append((_VP_OPCODE[code], arg))
+        depth += 1 - pops
+        top = max(top, depth)
+    if len(ops) > AM_MAX_OPS:
+        raise ValueError(f"the vertex expression {root} compiles to {len(ops)} ops, more than AM_MAX_OPS = "
+                         f"{AM_MAX_OPS}")
+    if top > AM_MAX_STACK:
+        raise ValueError(f"the vertex expression {root} needs a stack of {top} values, more than AM_MAX_STACK = "
+                         f"{AM_MAX_STACK}")
+    if len(consts) > AM_MAX_CONSTS:
+        raise ValueError(f"the vertex expression {root} holds {len(consts)} constants, more than AM_MAX_CONSTS = "
+                         f"{AM_MAX_CONSTS}")
+    return CompiledVertexProgram(tuple(ops), tuple(consts), tuple(columns), top)
+
+
+class Pregel:
+    """``GraphFrame.pregel``: the builder of ``graphframes.lib.Pregel`` (GraphFrames 0.8) and its
+    vocabulary::
+
+        from graphframes_amd import Pregel
+        ranks = (g.pregel.setMaxIter(10)
+                  .withVertexColumn("rank", Pregel.lit(1.0),
+                                    Pregel.coalesce(Pregel.msg(), 0.0) * 0.85 + 0.15)
+                  .sendMsgToDst(Pregel.src("rank") * Pregel.src("w"))
+                  .aggMsgs(Pregel.sum(Pregel.msg()))
+                  .run())
+
+    ``withVertexColumn(name, initialExpr, updateAfterAggMsgsExpr)`` adds a column (1 to
+    PREGEL_MAX_COLUMNS) that lives on the GPU across the iterations; ``sendMsgToDst`` /
+    ``sendMsgToSrc`` (repeatable, up to PREGEL_MAX_MESSAGES each) add a message along every edge;
+    ``aggMsgs`` sets the one aggregate; ``setMaxIter`` (default 10) the number of iterations, all
+    of which run: there is no early stop.  ``setCheckpointInterval`` is accepted and ignored.
+    ``run()`` returns the vertex rows sorted by ``id`` with the Pregel columns (float64) added.
+
+    In an iteration every edge evaluates the messages over the columns of its ends
+    (``Pregel.src(c)``, ``Pregel.dst(c)``: a column of the vertex frame or a Pregel column) and
+    its own (``Pregel.edge(c)``); a null message is not delivered; a vertex aggregates what it
+    receives into ``Pregel.msg()``, which is null for a vertex that received nothing (for count
+    too); every Pregel column then becomes its update expression over the vertex's own columns
+    (``Pregel.col(c)``, their values before the iteration) and the message, all columns at once.
+    An update expression whose value is null is an error: wrap it in ``Pregel.coalesce``.
+
+    ``Pregel.col``, ``lit``, ``when(...).otherwise(...)``, ``coalesce(a, b)`` and ``isnull(a)``
+    stand in for ``pyspark.sql.functions``; the operators, the null rules and the one deviation
+    from Spark (``&`` and ``|`` with a null operand give null) are those of
+    ``AggregateMessages``, whose aggregates (``AM.sum(AM.msg)``) are accepted too.  Everything is
+    IEEE binary64.  Out of scope: early stopping, active-vertex expressions, checkpoints."""
+
+    def __init__(self, graph: "GraphFrame"):
+        self._graph = graph
+        self._max_iter = 10
+        self._columns = []   # (name, initial expression, update expression)
+        self._to_src, self._to_dst = [], []
+        self._agg = None
+
+    # -- the vocabulary --
+    @staticmethod
+    def msg():
+        return MessageExpr("msg")
+
+    @staticmethod
+    def _column(kind, name):
+        if not isinstance(name, str):
+            raise TypeError(f"Pregel.{kind}(...) takes a column name, got {type(name).__name__}")
+        return MessageExpr(kind, value=name)
+
+    @staticmethod
+    def src(name): return Pregel._column("src", name)
+    @staticmethod
+    def dst(name): return Pregel._column("dst", name)
+    @staticmethod
+    def edge(name): return Pregel._column("edge", name)
+    @staticmethod
+    def col(name): return Pregel._column("col", name)
+
+    lit = staticmethod(AggregateMessages.lit)
+    when = staticmethod(AggregateMessages.when)
+
+    @staticmethod
+    def coalesce(a, b):
+        """``a`` where it is not null, else ``b``."""
+        a, b = MessageExpr.of(a), MessageExpr.of(b)
+        return MessageExpr("coalesce", (a, b), is_bool=a.is_bool and b.is_bool)
+
+    @staticmethod
+    def isnull(a):
+        """True where ``a`` is null; never null itself."""
+        return MessageExpr("isnull", (MessageExpr.of(a),), is_bool=True)
+
+    sum = staticmethod(AggregateMessages.sum)
+    min = staticmethod(AggregateMessages.min)
+    max = staticmethod(AggregateMessages.max)
+    avg = staticmethod(AggregateMessages.avg)
+    mean = avg
+    count = staticmethod(AggregateMessages.count)
+
+    # -- the builder --
+    def setMaxIter(self, value):
+        if not isinstance(value, (int, np.integer)) or isinstance(value, (bool, np.bool_)):
+            raise TypeError(f"maxIter must be an int, got {type(value).__name__}")
+        if value < 1:
+            raise ValueError(f"maxIter must be at least 1, got {value}")
+        self._max_iter = int(value)
+        return self
+
+    def setCheckpointInterval(self, value):
+        """Accepted for GraphFrames' call surface; nothing is checkpointed."""
+        return self
+
+    def withVertexColumn(self, colName, initialExpr, updateAfterAggMsgsExpr):
+        if not isinstance(colName, str):
+            raise TypeError(f"a Pregel column's name is a str, got {type(colName).__name__}")
+        if colName == ID or colName in self._graph.vertices.columns:
+            raise ValueError(f"the Pregel column {colName!r} would replace a column of the vertex frame")
+        if any(colName == name for name, _, _ in self._columns):
+            raise ValueError(f"the Pregel column {colName!r} is defined twice")
+        if len(self._columns) == PREGEL_MAX_COLUMNS:
+            raise ValueError(f"a run holds at most PREGEL_MAX_COLUMNS = {PREGEL_MAX_COLUMNS} Pregel columns")
+        self._columns.append((colName, MessageExpr.of(initialExpr), MessageExpr.of(updateAfterAggMsgsExpr)))
+        return self
+
+    def _send(self, to, msgExpr, what):
+        if len(to) == PREGEL_MAX_MESSAGES:
+            raise ValueError(f"a run holds at most PREGEL_MAX_MESSAGES = {PREGEL_MAX_MESSAGES} {what} messages")
+        to.append(MessageExpr.of(msgExpr))
+        return self
+
+    def sendMsgToSrc(self, msgExpr):
+        return self._send(self._to_src, msgExpr, "sendMsgToSrc")
+
+    def sendMsgToDst(self, msgExpr):
+        return self._send(self._to_dst, msgExpr, "sendMsgToDst")
+
+    def aggMsgs(self, aggExpr):
+        self._agg = _check_agg_col(aggExpr)
+        return self
+
+    def _prepare(self):
+        """The host side of run(), before any handle: (aggregate kind, to_src, to_dst, init and
+        update programs, the Pregel names, static vertex columns [n][rows of v], edge columns
+        [n][rows of e])."""
+        v, e = self._graph.vertices, self._graph.edges
+        if not self._columns:
+            raise ValueError("no vertex column: call withVertexColumn at least once")
+        if not self._to_src and not self._to_dst:
+            raise ValueError("no message: call sendMsgToSrc, sendMsgToDst, or both")
+        if self._agg is None:
+            raise ValueError("no aggregate: call aggMsgs")
+        pregel_names = [name for name, _, _ in self._columns]
+        static = []
+        exprs = self._to_src + self._to_dst + [x for _, i, u in self._columns for x in (i, u)]
+        for node in (n for x in exprs for n in x.walk()):
+            if node.op in ("src", "dst", "col") and node.value not in pregel_names and node.value not in static:
+                static.append(node.value)
+        names = static + pregel_names
+        if len(names) > AM_MAX_VERTEX_COLUMNS:
+            raise ValueError(f"the run holds {len(names)} vertex columns ({', '.join(names)}), the Pregel ones "
+                             f"included, more than AM_MAX_VERTEX_COLUMNS = {AM_MAX_VERTEX_COLUMNS}")
+        vcols = [_am_column(v, name, "vertex") for name in static]
+        edge_names = ()
+        to_src, to_dst = [], []
+        for exprs, out in ((self._to_src, to_src), (self._to_dst, to_dst)):
+            for x in exprs:
+                out.append(compile_message(x, names, edge_names))
+                edge_names = out[-1].edge_columns
+        ecols = [_am_column(e, name, "edge") for name in edge_names]
+        init = [compile_vertex_program(i, names, len(static), initial=True) for _, i, _ in self._columns]
+        update = [compile_vertex_program(u, names, len(static)) for _, _, u in self._columns]
+        return self._agg.kind, to_src, to_dst, init, update, pregel_names, vcols, ecols
+
+    def run(self) -> pd.DataFrame:
+        """The vertex rows sorted by ``id`` with every Pregel column (float64) after ``maxIter``
+        iterations.  Everything that can be refused is refused with ``ValueError`` before any
+        device work: no vertex column, message or aggregate; a column the frames lack, that is
+        not numeric or bool, or that holds NaN, None, an infinite value or an integer beyond
+        +-2^53; an initial expression that reads a Pregel column or the message;
+        ``Pregel.src`` / ``dst`` / ``edge`` in a vertex expression, ``Pregel.col`` / ``coalesce``
+        / ``isnull`` in a message; a limit exceeded.  An update (or initial) expression whose
+        value is null raises ``ValueError`` naming the column and the iteration."""
+        agg, to_src, to_dst, init, update, names, vcols, ecols = self._prepare()
+        gf = self._graph
+        ig = gf._indexed()
+        rep = gf._first_rows()
+        V, m = ig.num_vertices, int(ig.src.size)
+        vc = np.stack([c[rep] for c in vcols]) if vcols else np.empty((0, V), dtype=np.float64)
+        ec = np.stack([c[ig.kept] for c in ecols]) if ecols else np.empty((0, m), dtype=np.float64)
+        try:
+            cols = gf._gpu_graph().pregel(self._max_iter, agg, to_src, to_dst, init, update, vc, ec)
+        except PregelNullError as err:
+            what = "initial" if err.iteration == 0 else "update"
+            raise ValueError(f"Pregel column {names[err.column]!r}: the {what} expression is null in iteration "
+                             f"{err.iteration} at the vertex {ig.ids[err.vertex]!r}; a column holds no null: give "
+                             "the value to take with Pregel.coalesce(expression, value)") from None
+        return _attach(gf.vertices, ig, {name: cols[j] for j, name in enumerate(names)})
 
 
 def _check_cc_algorithm(algorithm):
@@ -1259,6 +1538,12 @@ class GraphFrame:
         else:
             values = res[agg.kind][got]
         return pd.DataFrame({ID: ig.ids[got], agg.name: values})
+
+    @property
+    def pregel(self) -> Pregel:
+        """``GraphFrame.pregel``: a new ``Pregel`` builder over this graph (its docstring has the
+        calls, the vocabulary and the semantics)."""
+        return Pregel(self)
 
     def inDegrees(self) -> pd.DataFrame:
         """Vertices + ``inDegree`` (int64): the kept edges ending at each vertex, duplicates

@@ -841,6 +841,104 @@ int lpa_aggregate_messages(lpa_graph* g, const lpa_am_program* to_src /* nullabl
                            double* min_out /* nullable */, double* max_out /* nullable */,
                            lpa_am_summary* summary /* nullable */);
 
+/*
+ * Pregel (graphframes.lib.Pregel.run of GraphFrames 0.8) over the DIRECTED input MULTIGRAPH:
+ * vertex columns that live across max_iter iterations on the device, messages along the edges,
+ * one aggregate, one update program per column.  Duplicates are edges of their own, a self-loop
+ * is an edge, an edge with an end outside [0, V) is no edge.  IEEE binary64, no fused
+ * multiply-adds; the null rules are those of lpa_aggregate_messages (AND and OR with a null
+ * operand give null).
+ * Columns.  The n_vcols static columns (vcols, host [n_vcols][V]) have the indices [0, n_vcols),
+ * the n_pcols Pregel columns (1 to LPA_PG_MAX_COLUMNS) the indices n_vcols + j; together at most
+ * LPA_AM_MAX_COLUMNS.  ecols: host [n_ecols][m], in the handle's input edge order.
+ * Start.  Pregel column j = init[j] per vertex.  An init program reads static columns and
+ * constants only.
+ * One iteration, max_iter times, no early stop; every read is of the state before the iteration
+ * and all Pregel columns change at once (a' = b, b' = a swaps):
+ *   1. every kept edge row s -> d evaluates the n_to_dst programs to_dst[] for d and the n_to_src
+ *      programs to_src[] for s (0 to LPA_PG_MAX_MESSAGES each, at least one in all): message
+ *      programs as lpa_aggregate_messages takes them, SRC c / DST c reading column c, static or
+ *      Pregel, of that end.  A null message is not delivered;
+ *   2. every vertex aggregates what was delivered to it with agg: LPA_PG_SUM, MIN, MAX, AVG (sum /
+ *      count, on the device) or COUNT.  That is msg; it is NULL for a vertex that received
+ *      nothing, for COUNT too;
+ *   3. Pregel column j becomes update[j] over the vertex's own columns (old values) and msg.
+ * init[] and update[] are vertex programs: postfix code with the stack discipline and the limits
+ * of a message program and opcodes of their own (LPA_VP_*).  CONST k pushes consts[k], COL c
+ * column c of this vertex, MSG the aggregate; the arithmetic, comparison, logic and conditional
+ * ops are those of the message programs; COALESCE pops b, then a, and pushes a where a is not
+ * null, else b; ISNULL replaces the top by 1.0 where it is null, else 0.0, and is never null.
+ * A null value of an init or update program is an error: the kernels record the smallest
+ * (iteration, column, vertex) -- iteration 0 is the start -- in one 64-bit atomic minimum, store
+ * NaN and go on; the call looks once, at its end, returns LPA_EINVAL with a lpa_last_error() text
+ * that names the iteration, the Pregel column and the dense id, and writes nothing to cols_out
+ * (summary then holds the three in null_iteration, null_column, null_vertex and nothing else of
+ * meaning; they are -1 after a success).
+ * cols_out: host [n_pcols][V], the columns after max_iter iterations.  summary (nullable) holds
+ * integers only, the message counts summed over the iterations: nulls = evaluated and not
+ * delivered; rows_* = the vertices by kernel form; max_row = the longest message list in rows.
+ * LPA_EINVAL, with a lpa_last_error() text naming the program, for a malformed program (as for
+ * lpa_aggregate_messages; also an init program that reads a Pregel column or MSG), max_iter <= 0,
+ * an unknown agg, n_pcols outside [1, LPA_PG_MAX_COLUMNS], n_to_src or n_to_dst outside
+ * [0, LPA_PG_MAX_MESSAGES] or both 0, n_vcols < 0 or n_vcols + n_pcols > LPA_AM_MAX_COLUMNS,
+ * n_ecols outside [0, LPA_AM_MAX_COLUMNS], a null pointer where something is read or written; all
+ * of it is checked on the host before the handle is looked at, and the kernels trust it.  Then a
+ * null handle.  V == 0: success, nothing written.  No kept edge: the iterations run, every msg is
+ * null.  LPA_EINVAL also where one direction's programs times m exceed 2^32 - 1: a vertex counts
+ * the messages of a direction in 32 bits.
+ * A vertex's message list is its in-list rows, sorted by (src, edge row), then its out-list rows,
+ * sorted by (dst, edge row); the entries are ROWS: a lane takes its strided share of rows in list
+ * order and, within a row, that direction's programs in the order given; then the xor-shuffle
+ * tree, then, in the block form, the 16 wave partials in order.  The row forms and their
+ * boundaries are those of lpa_aggregate_messages (LPA_AM_SHORT, LPA_AM_WAVE), by rows.  One fused
+ * launch per row form and iteration reduces a vertex's messages and applies its update programs:
+ * no per-edge message array, no per-vertex aggregate array, no host synchronisation between the
+ * iterations, no floating-point atomics (DESIGN.md "Pregel").  Hence with MIN, MAX or COUNT every
+ * column is a function of the inputs alone; with SUM or AVG the columns are bit-identical across
+ * calls and handles with the same boundaries, and across input edge orders for programs that read
+ * no edge column; with one program per direction, iteration 1's aggregate has the bits
+ * lpa_aggregate_messages returns for those programs over the initial columns.  The labels and
+ * every other piece of lpa_step's state are neither read nor written, nothing is kept on the
+ * handle.  On a distributed job only rank 0 keeps the edge list; the other ranks return
+ * LPA_EINVAL.  Since ABI 21.
+ */
+#define LPA_PG_MAX_COLUMNS 4    /* Pregel columns of one call          */
+#define LPA_PG_MAX_MESSAGES 4   /* message programs of one direction   */
+enum { LPA_PG_SUM = 0, LPA_PG_MIN = 1, LPA_PG_MAX = 2, LPA_PG_AVG = 3, LPA_PG_COUNT = 4, LPA_PG_NAGGS = 5 };
+enum {
+  LPA_VP_CONST = 0, LPA_VP_COL = 1, LPA_VP_MSG = 2,
+  LPA_VP_ADD = 3, LPA_VP_SUB = 4, LPA_VP_MUL = 5, LPA_VP_DIV = 6,
+  LPA_VP_NEG = 7, LPA_VP_ABS = 8,
+  LPA_VP_EQ = 9, LPA_VP_NE = 10, LPA_VP_LT = 11, LPA_VP_LE = 12, LPA_VP_GT = 13, LPA_VP_GE = 14,
+  LPA_VP_AND = 15, LPA_VP_OR = 16, LPA_VP_NOT = 17,
+  LPA_VP_WHEN = 18, LPA_VP_WHEN_ELSE = 19,
+  LPA_VP_COALESCE = 20, LPA_VP_ISNULL = 21,
+  LPA_VP_NOPS = 22
+};
+typedef struct lpa_vp_program {
+  int32_t n_ops, n_consts;
+  uint32_t ops[LPA_AM_MAX_OPS];       /* opcode | argument << 16                               */
+  double consts[LPA_AM_MAX_CONSTS];
+} lpa_vp_program;          /* 392 bytes */
+typedef struct lpa_pregel_summary {
+  int64_t edges;             /* valid input edge rows                                         */
+  int64_t messages_to_src;   /* delivered (non-null) messages, by direction, all iterations   */
+  int64_t messages_to_dst;
+  int64_t nulls;             /* evaluated and not delivered, all iterations                   */
+  int64_t rows_short, rows_wave, rows_block;   /* vertices by kernel form                     */
+  int64_t max_row;           /* the longest message list, in rows                             */
+  int64_t iterations;        /* iterations run                                                */
+  int64_t null_iteration, null_column, null_vertex;   /* the first null value, or -1          */
+} lpa_pregel_summary;      /* 96 bytes */
+int lpa_pregel(lpa_graph* g, int32_t max_iter, int32_t agg,
+               const lpa_am_program* to_src /* [n_to_src] */, int32_t n_to_src,
+               const lpa_am_program* to_dst /* [n_to_dst] */, int32_t n_to_dst,
+               const lpa_vp_program* init /* [n_pcols] */, const lpa_vp_program* update /* [n_pcols] */,
+               int32_t n_pcols,
+               const double* vcols /* host [n_vcols][V] */, int32_t n_vcols,
+               const double* ecols /* host [n_ecols][m] */, int32_t n_ecols,
+               double* cols_out /* host [n_pcols][V] */, lpa_pregel_summary* summary /* nullable */);
+
 /* Symmetrised degree of every vertex (dense ids), host output. */
 int lpa_degrees(lpa_graph* g, int32_t* deg_out);
 
@@ -865,8 +963,9 @@ int lpa_degrees(lpa_graph* g, int32_t* deg_out);
  * ABI 18: lpa_bfs.
  * ABI 19: lpa_motif, lpa_motif_rows, lpa_motif_vertex_column, lpa_motif_edge_column,
  *         lpa_motif_result_destroy.
- * ABI 20: lpa_aggregate_messages. */
-#define LPA_ABI_VERSION 20
+ * ABI 20: lpa_aggregate_messages.
+ * ABI 21: lpa_pregel. */
+#define LPA_ABI_VERSION 21
 int lpa_abi_version(void);
 int lpa_graph_get_info(const lpa_graph* g, lpa_graph_info* info);
 int lpa_graph_get_info_sized(const lpa_graph* g, lpa_graph_info* info, int64_t info_size);
