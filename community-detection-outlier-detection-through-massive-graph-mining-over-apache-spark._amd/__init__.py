@@ -10,7 +10,8 @@ and fails loudly if it has not been built.
 from .graph import Graph, Loopback, PregelNullError, comm_unique_id, gen_chunglu, gen_rmat, gen_sbm, run_ranks
 from .graphframe import (AggregateMessages, CompiledMessage, CompiledVertexProgram, GraphFrame, IndexedGraph,
                          MessageAggregate, MessageExpr,
-                         MotifTerm, OutlierResult, ParsedMotif, Pregel, aggregate_messages, bfs, compile_message,
+                         MotifTerm, OutlierResult, ParsedMotif, Pregel, aggregate_messages, betweenness_centrality, bfs,
+                         compile_message,
                          compile_vertex_program,
                          connected_components, core_number, count_paths, enumerate_paths, find, index_graph,
                          k_core, label_propagation, louvain, motif_count, outlier_scores, page_rank,
@@ -19,7 +20,7 @@ from .graphframe import (AggregateMessages, CompiledMessage, CompiledVertexProgr
 from . import ingest
 
 __all__ = ["Graph", "Loopback", "run_ranks", "GraphFrame", "IndexedGraph", "OutlierResult", "comm_unique_id", "gen_chunglu", "gen_rmat",
-           "gen_sbm", "bfs", "connected_components", "core_number", "count_paths", "enumerate_paths", "index_graph", "ingest", "k_core",
+           "gen_sbm", "betweenness_centrality", "bfs", "connected_components", "core_number", "count_paths", "enumerate_paths", "index_graph", "ingest", "k_core",
            "label_propagation", "louvain",
            "outlier_scores", "page_rank", "parallel_personalized_page_rank", "shortest_paths", "strongly_connected_components",
            "triangle_count", "find", "motif_count", "parse_motif", "plan_motif", "MotifTerm", "ParsedMotif",

@@ -129,6 +129,14 @@ class LpaSpSummary(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LpaBcSummary(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int64) for k in ("arcs", "sources", "batches", "batch_width", "reached", "max_depth",
+                                              "levels")]
+
+    def to_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class LpaBfsSummary(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in ("arcs", "sources", "targets", "length", "reached", "path_vertices",
                                               "path_edges", "push_levels", "pull_levels")]
@@ -277,6 +285,8 @@ SIGNATURES = {
                                              ctypes.c_int32, _vp, ctypes.POINTER(LpaPprSummary)]),
     "lpa_shortest_paths": (ctypes.c_int, [_vp, _i32p, ctypes.c_int32, _vp, ctypes.c_int32,
                                           ctypes.POINTER(LpaSpSummary)]),
+    "lpa_betweenness": (ctypes.c_int, [_vp, _i32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp,
+                                       ctypes.c_int32, ctypes.POINTER(LpaBcSummary)]),
     "lpa_bfs": (ctypes.c_int, [_vp, _u8p, _u8p, _u8p, ctypes.c_int32, _i32p, _u8p, ctypes.POINTER(LpaBfsSummary)]),
     "lpa_motif": (ctypes.c_int, [_vp, ctypes.c_int32, _u8p, ctypes.POINTER(LpaMotifTerm), ctypes.c_int32,
                                  ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(_vp),

@@ -82,6 +82,17 @@ __global__ __launch_bounds__(256) void k_arc_split(const u64* __restrict__ okeys
   }
 }
 
+// both orientations of every in-range non-loop edge (lpa_bc.hip, undirected): 2 m keys
+__global__ __launch_bounds__(256) void k_arc_keys_both(const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
+                                                       int64_t m, u32 V, u64* __restrict__ keys) {
+  GRID_STRIDE(i, m) {
+    const u32 a = (u32)__builtin_nontemporal_load(src + i), b = (u32)__builtin_nontemporal_load(dst + i);
+    const bool arc = a < V && b < V && a != b;
+    keys[i] = arc ? ((u64)a << 32) | b : ((u64)V << 32) | V;
+    keys[m + i] = arc ? ((u64)b << 32) | a : ((u64)V << 32) | V;
+  }
+}
+
 // ---- simple edges ----
 __global__ __launch_bounds__(256) void k_edge_keys(const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
                                                    int64_t m, u32 V, u64* __restrict__ keys) {
@@ -232,11 +243,16 @@ int key_col(const u64* keys, int64_t n, int32_t* col, hipStream_t s) {
   return LPA_OK;
 }
 
-int arcs_count(lpa_graph* g, Tmp& tmp, uint8_t* loop, ArcLists* a, const uint8_t* keep) {
+int arcs_count(lpa_graph* g, Tmp& tmp, uint8_t* loop, ArcLists* a, const uint8_t* keep, bool both) {
   hipStream_t s = g->stream;
-  const int64_t V = g->V, m = g->m;
+  const int64_t V = g->V, m = both ? 2 * g->m : g->m;   // m: the keys
   a->E = 0;
+  a->n = m;
   if (m == 0) return LPA_OK;
+  if (m >= (int64_t)1 << 32) {
+    set_error("%lld arc keys do not fit the 32-bit positions of the arc build", (long long)m);
+    return LPA_EOVERFLOW;
+  }
   const HalfShifts sh(bits_for((uint64_t)V));   // the halves hold values up to V (a dropped edge)
   LPA_TRY(tmp.get(&a->keys, 2 * m));
   LPA_TRY(tmp.get(&a->flag, m));
@@ -244,7 +260,10 @@ int arcs_count(lpa_graph* g, Tmp& tmp, uint8_t* loop, ArcLists* a, const uint8_t
   u64* keys = a->keys;
   auto* k_keys = loop ? (keep ? k_arc_keys<true, true> : k_arc_keys<true, false>)
                       : (keep ? k_arc_keys<false, true> : k_arc_keys<false, false>);
-  hipLaunchKernelGGL(k_keys, dim3(grid_for(m)), dim3(256), 0, s, g->e_src, g->e_dst, m, (u32)V, keys, loop, keep);
+  if (both)   // no loop marks, no keep mask
+    hipLaunchKernelGGL(k_arc_keys_both, dim3(grid_for(g->m)), dim3(256), 0, s, g->e_src, g->e_dst, g->m, (u32)V, keys);
+  else
+    hipLaunchKernelGGL(k_keys, dim3(grid_for(m)), dim3(256), 0, s, g->e_src, g->e_dst, m, (u32)V, keys, loop, keep);
   LPA_HIP(hipGetLastError());
   LPA_TRY(radix_sort_u64(keys, keys + m, m, sh.both(), 2 * sh.ns, s));
   hipLaunchKernelGGL(k_arc_uniq, dim3(grid_for(m)), dim3(256), 0, s, keys, m, (u32)V, a->flag);
@@ -259,7 +278,7 @@ int arcs_count(lpa_graph* g, Tmp& tmp, uint8_t* loop, ArcLists* a, const uint8_t
 
 int arcs_lists(lpa_graph* g, Tmp& tmp, ArcLists* a) {
   hipStream_t s = g->stream;
-  const int64_t V = g->V, m = g->m, E = a->E;
+  const int64_t V = g->V, m = a->n, E = a->E;
   LPA_TRY(tmp.get(&a->oo, V + 1));
   LPA_TRY(tmp.get(&a->io, V + 1));
   LPA_TRY(tmp.get(&a->ocol, E));

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <new>
+#include <vector>
 
 #include "lpa_internal.h"
 
@@ -250,6 +251,10 @@ int create_common(int32_t device, hipStream_t stream, const int32_t* src, const 
   if (const char* f = getenv("LPA_PPR_BATCH")) {
     const int b = atoi(f);
     g->ppr_batch = b == 4 || b == 8 || b == 16 ? b : lpa::kPprBatch;
+  }
+  if (const char* f = getenv("LPA_BC_BATCH")) {
+    const int b = atoi(f);
+    g->bc_batch = b == 1 || b == 4 || b == 8 || b == 16 ? b : lpa::kBcBatch;
   }
   if (const char* f = getenv("LPA_SP_ALPHA")) g->sp_alpha = atoi(f) < 0 ? 0 : atoi(f);
   if (const char* f = getenv("LPA_SP_PULL")) g->sp_pull = atoi(f) == 1 ? 1 : 0;
@@ -790,6 +795,56 @@ int lpa_shortest_paths(lpa_graph* g, const int32_t* landmarks, int32_t n_landmar
   }
   LPA_HIP(hipSetDevice(g->device));
   return shortest_paths(g, landmarks, n_landmarks, dist_out, out_is_device, summary);
+}
+
+int lpa_betweenness(lpa_graph* g, const int32_t* sources, int32_t n_sources, int32_t directed, int32_t batch,
+                    double* raw_out, int32_t out_is_device, lpa_bc_summary* summary) {
+  if (!g) {
+    set_error("null handle");
+    return LPA_EINVAL;
+  }
+  if (sources && n_sources < 0) {
+    set_error("lpa_betweenness: n_sources must not be negative, got %d", n_sources);
+    return LPA_EINVAL;
+  }
+  if (batch != 0 && batch != 1 && batch != 4 && batch != 8 && batch != 16) {
+    set_error("lpa_betweenness: batch must be 0, 1, 4, 8 or 16, got %d", batch);
+    return LPA_EINVAL;
+  }
+  const int64_t V = g->V;
+  std::vector<int32_t> all;   // null sources: every vertex
+  if (!sources) {
+    all.resize((size_t)V);
+    for (int64_t v = 0; v < V; ++v) all[(size_t)v] = (int32_t)v;
+    sources = all.data();
+    n_sources = (int32_t)V;
+  } else {
+    std::vector<uint8_t> taken((size_t)V, 0);
+    for (int32_t i = 0; i < n_sources; ++i) {
+      if (sources[i] < 0 || (int64_t)sources[i] >= V) {
+        set_error("lpa_betweenness: source %d (position %d) is not a vertex of [0, %lld)", sources[i], i,
+                  (long long)V);
+        return LPA_EINVAL;
+      }
+      if (taken[(size_t)sources[i]]) {
+        set_error("lpa_betweenness: source %d is repeated (position %d)", sources[i], i);
+        return LPA_EINVAL;
+      }
+      taken[(size_t)sources[i]] = 1;
+    }
+  }
+  if (!raw_out && V > 0) {
+    set_error("lpa_betweenness: null output");
+    return LPA_EINVAL;
+  }
+  if (g->m > 0 && !g->e_src) {
+    set_error("lpa_betweenness of a distributed job runs on rank 0 (the rank that keeps the edge list)");
+    return LPA_EINVAL;
+  }
+  if (summary) *summary = lpa_bc_summary{0, 0, 0, 0, 0, -1, 0};
+  if (V == 0) return LPA_OK;
+  LPA_HIP(hipSetDevice(g->device));
+  return betweenness(g, sources, n_sources, directed, batch, raw_out, out_is_device, summary);
 }
 
 int lpa_bfs(lpa_graph* g, const uint8_t* from_mask, const uint8_t* to_mask, const uint8_t* edge_keep, int32_t max_len,

@@ -105,6 +105,11 @@ constexpr int kPrShort = 32;          // 8 lanes per row up to this length
 constexpr int kPrWave = 1024;         // a wave per row up to this length; longer: a block of 1024 per row
 // parallel personalized PageRank (lpa_ppr.hip): sources to a pass (4, 8 or 16)
 constexpr int kPprBatch = 16;         // the default (DESIGN.md "Parallel personalized PageRank": the measured table)
+// betweenness centrality (lpa_bc.hip): sources to a pass (1, 4, 8 or 16) and the list lengths of its row
+// forms (out-lists in the push and the backward pull, in-lists in the sigma pull)
+constexpr int kBcBatch = 16;          // the default (DESIGN.md "Betweenness centrality": the measured table)
+constexpr int kBcShort = 32;          // one lane per source of the pass up to this length
+constexpr int kBcWave = 1024;         // four lanes per source up to this length; longer: 64 per source
 // shortest paths (lpa_sp.hip): list lengths of its row forms (in-lists in the push, out-lists in
 // the pull) and the default of the push / pull switch
 constexpr int kSpShort = 32;          // 8 lanes per row up to this length
@@ -467,6 +472,8 @@ struct lpa_graph {
   int pr_wave = lpa::kPrWave;               // LPA_PR_WAVE  (>= 0; 0, or <= LPA_PR_SHORT: no row takes the wave form)
   // parallel personalized PageRank (lpa_ppr.hip): sources to a pass
   int ppr_batch = lpa::kPprBatch;           // LPA_PPR_BATCH (4, 8 or 16; anything else: the default)
+  // betweenness centrality (lpa_bc.hip): sources to a pass
+  int bc_batch = lpa::kBcBatch;             // LPA_BC_BATCH (1, 4, 8 or 16; anything else: the default)
   // shortest paths (lpa_sp.hip): the push / pull switch of a level
   int sp_alpha = lpa::kSpAlpha;             // LPA_SP_ALPHA (>= 0; 0: never pull)
   int sp_pull = 0;                          // LPA_SP_PULL=1: pull at every level
@@ -738,13 +745,17 @@ struct Tmp;
 // no edge).  arcs_lists: the out-lists and in-lists from that.
 struct ArcLists {
   int64_t E = 0;               // distinct arcs
+  int64_t n = 0;               // keys of the build: m, or 2 m with both orientations
   int64_t *oo = nullptr, *io = nullptr;      // [V + 1] offsets of the out-lists / the in-lists
   int32_t *ocol = nullptr, *icol = nullptr;  // [E] their entries, a list ascending
-  u64* keys = nullptr;         // [2 m] between the steps: the sorted keys and the sort's other buffer
-  uint8_t* flag = nullptr;     // [m]
-  u32* pos = nullptr;          // [m + 1]
+  u64* keys = nullptr;         // [2 n] between the steps: the sorted keys and the sort's other buffer
+  uint8_t* flag = nullptr;     // [n]
+  u32* pos = nullptr;          // [n + 1]
 };
-int arcs_count(lpa_graph* g, Tmp& tmp, uint8_t* loop, ArcLists* a, const uint8_t* keep = nullptr);
+// both: every edge also counts in the other direction (the simple undirected graph as arcs: the
+// out-lists and the in-lists coincide); loop and keep are then null
+int arcs_count(lpa_graph* g, Tmp& tmp, uint8_t* loop, ArcLists* a, const uint8_t* keep = nullptr,
+               bool both = false);
 int arcs_lists(lpa_graph* g, Tmp& tmp, ArcLists* a);
 // Every in-range edge row of the multigraph (self-loops and duplicates kept) with its index in the
 // input: the out-lists sorted by (src, dst, edge row), the in-lists (want_in) by (dst, src, edge
@@ -796,6 +807,10 @@ int parallel_pagerank(lpa_graph* g, int32_t max_iter, double reset_prob, const i
 // landmark shortest paths of the directed graph (lpa_sp.hip); the landmarks are in [0, V)
 int shortest_paths(lpa_graph* g, const int32_t* landmarks, int32_t n_landmarks, int32_t* dist_out,
                    int32_t out_is_device, lpa_sp_summary* summary);
+
+// betweenness centrality (lpa_bc.hip); the sources are distinct and in [0, V), batch is 1, 4, 8 or 16
+int betweenness(lpa_graph* g, const int32_t* sources, int32_t n_sources, int32_t directed, int32_t batch,
+                double* raw_out, int32_t out_is_device, lpa_bc_summary* summary);
 
 // breadth-first search between two vertex sets over the kept edges (lpa_bfs.hip); the arguments
 // are checked by the caller

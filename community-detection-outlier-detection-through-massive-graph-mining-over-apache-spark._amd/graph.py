@@ -539,6 +539,61 @@ class Graph:
                                                 ctypes.byref(summ) if stats else None))
         return (dist, summ.to_dict()) if stats else dist
 
+    # -- betweenness centrality -----------------------------------------------------
+    def betweenness(self, sources=None, directed: bool = True, batch: int = 0, out=None, stats: bool = False):
+        """Unscaled betweenness centrality from ``sources`` (distinct dense ids; ``None``: every
+        vertex) by Brandes' algorithm (lpa_betweenness): ``raw[v]`` is the sum over the sources
+        s != v of the dependency of s on v, over the distinct non-loop arcs of the input graph
+        (``directed=False``: every arc in both directions).  With every vertex a source, ``raw``
+        (directed) and ``raw / 2`` (undirected) are ``networkx.betweenness_centrality(...,
+        normalized=False)``; ``GraphFrame.betweennessCentrality`` applies the scales.  The
+        sources run ``batch`` to a pass (1, 4, 8 or 16; 0: the handle's, ``LPA_BC_BATCH`` when
+        the handle is created).  Path counts are binary64, as in networkx: above 2^53 they are
+        rounded, the result is still deterministic.  Host float64 array of ``num_vertices``
+        entries by default, or written into the float64 device tensor ``out`` (this handle's
+        device).  ``stats=True`` returns ``(raw, summary)``: ``summary`` is a dict of arcs,
+        sources, batches, batch_width, reached, max_depth, levels.  ``raw`` is bit-identical
+        across runs, handles, input edge orders and batch widths.  The labels and the LPA state
+        are not touched."""
+        if not isinstance(batch, (int, np.integer)) or isinstance(batch, (bool, np.bool_)):
+            raise TypeError(f"batch must be an int, got {type(batch).__name__}")
+        if int(batch) not in (0, 1, 4, 8, 16):
+            raise ValueError(f"batch must be 0, 1, 4, 8 or 16, got {int(batch)}")
+        V = self.num_vertices
+        sv = None
+        if sources is not None:
+            srcs = list(sources) if not isinstance(sources, (str, bytes)) else [sources]
+            for x in srcs:
+                if not isinstance(x, (int, np.integer)) or isinstance(x, (bool, np.bool_)):
+                    raise TypeError(f"a source must be a dense vertex id (int), got {type(x).__name__}")
+            for x in srcs:
+                if not 0 <= int(x) < V:
+                    raise ValueError(f"source {int(x)} is not a vertex of [0, {V})")
+            if len(set(int(x) for x in srcs)) != len(srcs):
+                raise ValueError("a source is repeated")
+            sv = np.asarray(srcs, dtype=np.int32).reshape(len(srcs))
+        if out is not None and _is_device_tensor(out):
+            import torch
+
+            if out.dtype != torch.float64:
+                raise ValueError(f"out must be float64, got {out.dtype}")
+            if out.device.index != self.device:
+                raise ValueError(f"out must be on cuda:{self.device}, got {out.device}")
+            if out.numel() != V or not out.is_contiguous():
+                raise ValueError(f"out must hold {V} contiguous entries")
+            raw, ptr, on_dev = out, out.data_ptr(), 1
+            torch.cuda.current_stream(out.device).synchronize()   # the library works on its own stream
+        elif out is not None:
+            raise ValueError("out must be a float64 device tensor")
+        else:
+            raw = np.empty(V, dtype=np.float64)
+            ptr, on_dev = raw.ctypes.data, 0
+        summ = _lib.LpaBcSummary()
+        _lib.check(self._lib.lpa_betweenness(self._handle(), None if sv is None else sv.ctypes.data_as(_lib._i32p),
+                                             0 if sv is None else int(sv.size), 1 if directed else 0, int(batch),
+                                             ptr, on_dev, ctypes.byref(summ) if stats else None))
+        return (raw, summ.to_dict()) if stats else raw
+
     # -- breadth-first search ---------------------------------------------------------
     @staticmethod
     def _mask(name, x, n):

@@ -38,6 +38,7 @@ ID, SRC, DST, LABEL = "id", "src", "dst", "label"
 COMPONENT = "component"
 COUNT = "count"
 CORE = "core"
+BETWEENNESS = "betweenness"
 PAGERANK = "pagerank"
 PAGERANKS = "pageranks"
 WEIGHT = "weight"
@@ -1213,6 +1214,82 @@ class GraphFrame:
         out.attrs["core_sizes"] = [int(x) for x in sizes]
         return out
 
+    def _bc_sources(self, sources, k, seed):
+        """The dense ids of the sources of ``betweennessCentrality`` (None: every vertex); every
+        argument error is raised here, before any device work."""
+        V = self._indexed().num_vertices
+        if sources is not None and k is not None:
+            raise ValueError("betweennessCentrality: give sources or k, not both")
+        if k is not None:
+            if not isinstance(k, (int, np.integer)) or isinstance(k, (bool, np.bool_)):
+                raise TypeError(f"k must be an int, got {type(k).__name__}")
+            if not isinstance(seed, (int, np.integer)) or isinstance(seed, (bool, np.bool_)):
+                raise TypeError(f"seed must be an int, got {type(seed).__name__}")
+            if not 1 <= k <= V:
+                raise ValueError(f"k must belong to [1, {V}] (the number of vertices), got {k}")
+            return np.sort(np.random.default_rng(int(seed)).choice(V, size=int(k), replace=False)).astype(np.int32)
+        if sources is None:
+            return None
+        if isinstance(sources, (str, bytes)) or not isinstance(sources, (list, tuple, np.ndarray)):
+            raise TypeError(f"sources must be a list, tuple or array of vertex ids, got {type(sources).__name__}")
+        if isinstance(sources, np.ndarray) and sources.ndim != 1:
+            raise TypeError(f"sources must be one-dimensional, got {sources.ndim} dimensions")
+        if len(sources) == 0:
+            raise ValueError("betweennessCentrality: sources is empty")
+        dense = []
+        for sid in sources:
+            sid = sid.item() if isinstance(sid, np.generic) else sid
+            try:
+                pos = None if sid is None else self._source_dense(sid)
+            except ValueError:
+                pos = None
+            if pos is None:
+                raise ValueError(f"betweennessCentrality: source {sid!r} is not a vertex id")
+            dense.append(pos)
+        if len(set(dense)) != len(dense):
+            raise ValueError("betweennessCentrality: a source is repeated")
+        return np.asarray(dense, dtype=np.int32)
+
+    def betweennessCentrality(self, sources=None, k: int | None = None, seed: int = 0, normalized: bool = True,
+                              directed: bool = True) -> pd.DataFrame:
+        """Betweenness centrality per vertex -- this package's own addition, not a GraphFrames
+        call (like ``louvain`` and ``coreNumber``): the share of the shortest paths that pass
+        through a vertex, ``networkx.betweenness_centrality``'s definition on the simple graph
+        of the input (the distinct edges src -> dst with src != dst: duplicate edges and
+        self-loops change nothing).  ``directed=False``: every edge counts in both directions,
+        the simple undirected graph of ``triangleCount`` and ``coreNumber``.  Returns the vertex
+        rows sorted by id, all columns kept, + ``betweenness`` (float64).  With neither
+        ``sources`` nor ``k`` the result is exact (every vertex a source) and equals
+        ``networkx.betweenness_centrality(G, normalized=normalized)``.  ``sources`` (a non-empty
+        list, tuple or 1-D array of distinct vertex ids) or ``k`` (an int in [1, V]: the pivots
+        ``np.sort(np.random.default_rng(seed).choice(V, size=k, replace=False))`` as dense ids,
+        ascending id order) give the pivot estimate, the sum over those sources scaled by
+        V / |sources| as networkx scales its ``k`` samples.  With raw the unscaled sum:
+        ``normalized=False`` gives raw V / |S| (directed) or raw V / |S| / 2 (undirected),
+        ``normalized=True`` raw V / |S| / ((V - 1) (V - 2)), all zeros when V <= 2; V counts
+        every vertex row.  An id that is no vertex id, a repeat, an empty ``sources`` or both
+        ``sources`` and ``k`` raise ``ValueError`` before any device work.  ``.attrs`` holds
+        ``sources`` (their number), ``max_depth`` (the largest distance from a source) and
+        ``exact`` (bool).  The numbers of shortest paths are binary64, as in networkx: above
+        2^53 they are rounded, the result is still deterministic -- bit-identical across runs
+        and input edge orders."""
+        dense = self._bc_sources(sources, k, seed)
+        ig = self._indexed()
+        V = ig.num_vertices
+        raw, summ = self._gpu_graph().betweenness(dense, directed=bool(directed), stats=True)
+        n = V if dense is None else int(dense.size)
+        if normalized:
+            bc = raw * (V / n) / ((V - 1) * (V - 2)) if V > 2 else np.zeros(V, np.float64)
+        else:
+            bc = raw * (V / n) if V > 0 else raw
+            if not directed:
+                bc = bc / 2
+        out = _attach(self._v, ig, {BETWEENNESS: bc})
+        out.attrs["sources"] = n
+        out.attrs["max_depth"] = int(summ["max_depth"])
+        out.attrs["exact"] = dense is None
+        return out
+
     def kCore(self, k: int) -> "GraphFrame":
         """The k-core as a graph -- this package's own addition (see ``coreNumber``): the
         sub-multigraph induced by the vertices of core number >= ``k``.  Returns a
@@ -1635,6 +1712,17 @@ def core_number(vertices: pd.DataFrame, edges: pd.DataFrame, device: int = 0) ->
     gf = GraphFrame(vertices, edges, device=device)
     try:
         return gf.coreNumber()
+    finally:
+        gf.close()
+
+
+def betweenness_centrality(vertices: pd.DataFrame, edges: pd.DataFrame, sources=None, k: int | None = None,
+                           seed: int = 0, normalized: bool = True, directed: bool = True,
+                           device: int = 0) -> pd.DataFrame:
+    """Function form of ``GraphFrame(vertices, edges).betweennessCentrality(...)``."""
+    gf = GraphFrame(vertices, edges, device=device)
+    try:
+        return gf.betweennessCentrality(sources=sources, k=k, seed=seed, normalized=normalized, directed=directed)
     finally:
         gf.close()
 

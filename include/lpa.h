@@ -472,6 +472,58 @@ int lpa_shortest_paths(lpa_graph* g, const int32_t* landmarks /* host, dense ids
                        int32_t out_is_device, lpa_sp_summary* summary /* nullable */);
 
 /*
+ * Betweenness centrality (this package's GraphFrame.betweennessCentrality; the definition is
+ * networkx.betweenness_centrality's) by Brandes' algorithm from a set S of sources.  The graph
+ * is the simple directed graph of the input: the distinct arcs src -> dst with src != dst and
+ * both ends in [0, V); duplicate edges and self-loops change nothing.  directed == 0: every arc
+ * also counts in the other direction (the simple undirected graph of lpa_triangle_count and
+ * lpa_core_numbers).  For every vertex v
+ *   raw_out[v] = sum over s in S, s != v, of delta_s(v)
+ *   delta_s(v) = sum over the arcs v -> w with level_s(w) == level_s(v) + 1
+ *                of sigma_s(v) / sigma_s(w) * (1 + delta_s(w))
+ * level_s the breadth-first distance from s, sigma_s the number of shortest paths from s, 0
+ * where s does not reach v.  raw_out is UNSCALED: with S = every vertex, raw (directed) and
+ * raw / 2 (undirected) are networkx's unnormalised values; with a subset the caller applies
+ * V / |S| (the pivot estimate).  sigma is binary64, as in networkx: above 2^53 the path counts
+ * are rounded, the result is still deterministic.  sources (distinct dense ids) is always
+ * host memory; null means every vertex, 0 ... V - 1 in order, and n_sources is then ignored.
+ * raw_out ([V] binary64) is host memory unless out_is_device; summary is nullable.  batch: the
+ * sources to a pass, 1, 4, 8 or 16; 0: the handle's (LPA_BC_BATCH = 1, 4, 8 or 16 at handle
+ * creation; anything else: the default).  V == 0: success, nothing written, summary {0, 0, 0,
+ * 0, 0, -1, 0}.  n_sources == 0 with a non-null sources: raw_out all zeros, max_depth -1.
+ * LPA_EINVAL for n_sources < 0, a source outside [0, V), a repeated source, a batch outside
+ * {0, 1, 4, 8, 16}, a null raw_out with V > 0.  The call blocks until the work is done.  The
+ * out-lists and in-lists of the arcs are built once per call; the sources then run batch_width
+ * to a pass in lockstep by level, their level, sigma and delta values interleaved per vertex so
+ * that one gathered arc serves the whole pass from one contiguous piece: forward, a level's
+ * new vertices are discovered by integer atomic ORs of slot masks along the frontier's out-lists
+ * and then pull their sigma over their in-lists; backward, level by level, the vertices of a
+ * level pull their delta over their out-lists (DESIGN.md "Betweenness centrality").  If the
+ * state of the chosen width cannot be allocated the call falls back to a narrower one before it
+ * returns LPA_ENOMEM; batch_width tells.  No floating-point atomics: every sum has a shape
+ * fixed by the row's length and form, the same at every batch width and slot, and a pass adds
+ * its deltas into raw_out in source order, so raw_out is a function of (V, arc set, sources in
+ * their order) alone: bit-identical across runs, handles, input edge orders and batch widths.
+ * All working memory is stream-ordered temporaries, the labels and every other piece of
+ * lpa_step's state are neither read nor written, nothing is kept on the handle.  On a
+ * distributed job (nranks > 1) only rank 0 keeps the edge list this needs; the other ranks
+ * return LPA_EINVAL.  Since ABI 22.
+ */
+typedef struct lpa_bc_summary {
+  int64_t arcs;         /* distinct non-loop arcs walked (both orientations when undirected) */
+  int64_t sources;      /* |S|                                                              */
+  int64_t batches;      /* passes = ceil(|S| / batch_width); 0 with none                    */
+  int64_t batch_width;  /* B: sources to a pass in this call                                */
+  int64_t reached;      /* sum over sources of the vertices given a level, the source included */
+  int64_t max_depth;    /* largest level of any source; -1 if no source or V == 0           */
+  int64_t levels;       /* sum over passes of (the pass's largest level + 1)                */
+} lpa_bc_summary;       /* 56 bytes */
+int lpa_betweenness(lpa_graph* g, const int32_t* sources /* host dense ids; null = every vertex */,
+                    int32_t n_sources, int32_t directed, int32_t batch /* 0: the library's */,
+                    double* raw_out /* [V], unscaled */, int32_t out_is_device,
+                    lpa_bc_summary* summary /* nullable */);
+
+/*
  * Breadth-first search between two vertex sets (GraphFrames lib.BFS / GraphFrame.bfs(fromExpr,
  * toExpr, edgeFilter, maxPathLength)) over the DIRECTED input graph.  F = the vertices with
  * from_mask != 0, T = those with to_mask != 0; the kept edges are the input edges with
@@ -964,8 +1016,9 @@ int lpa_degrees(lpa_graph* g, int32_t* deg_out);
  * ABI 19: lpa_motif, lpa_motif_rows, lpa_motif_vertex_column, lpa_motif_edge_column,
  *         lpa_motif_result_destroy.
  * ABI 20: lpa_aggregate_messages.
- * ABI 21: lpa_pregel. */
-#define LPA_ABI_VERSION 21
+ * ABI 21: lpa_pregel.
+ * ABI 22: lpa_betweenness. */
+#define LPA_ABI_VERSION 22
 int lpa_abi_version(void);
 int lpa_graph_get_info(const lpa_graph* g, lpa_graph_info* info);
 int lpa_graph_get_info_sized(const lpa_graph* g, lpa_graph_info* info, int64_t info_size);
