@@ -15,8 +15,8 @@ from .graphframe import (AggregateMessages, CompiledMessage, CompiledVertexProgr
                          compile_vertex_program,
                          connected_components, core_number, count_paths, enumerate_paths, find, index_graph,
                          k_core, label_propagation, louvain, motif_count, outlier_scores, page_rank,
-                         parallel_personalized_page_rank, parse_motif, plan_motif, shortest_paths,
-                         strongly_connected_components, triangle_count)
+                         parallel_personalized_page_rank, parse_motif, plan_motif, scan, shortest_paths,
+                         strongly_connected_components, structural_similarity, triangle_count)
 from . import ingest
 
 __all__ = ["Graph", "Loopback", "run_ranks", "GraphFrame", "IndexedGraph", "OutlierResult", "comm_unique_id", "gen_chunglu", "gen_rmat",
@@ -25,4 +25,5 @@ __all__ = ["Graph", "Loopback", "run_ranks", "GraphFrame", "IndexedGraph", "Outl
            "outlier_scores", "page_rank", "parallel_personalized_page_rank", "shortest_paths", "strongly_connected_components",
            "triangle_count", "find", "motif_count", "parse_motif", "plan_motif", "MotifTerm", "ParsedMotif",
            "AggregateMessages", "aggregate_messages", "compile_message", "CompiledMessage", "MessageExpr", "MessageAggregate",
-           "Pregel", "PregelNullError", "compile_vertex_program", "CompiledVertexProgram"]
+           "Pregel", "PregelNullError", "compile_vertex_program", "CompiledVertexProgram", "scan",
+           "structural_similarity"]

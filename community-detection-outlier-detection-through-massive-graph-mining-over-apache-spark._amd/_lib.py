@@ -229,6 +229,15 @@ class LpaLouvainSummary(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LpaScanSummary(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int64) for k in ("simple_edges", "triangles", "similar_edges", "n_clusters", "n_cores",
+                                              "n_borders", "n_hubs", "n_outliers", "largest_cluster",
+                                              "largest_cluster_label")]
+
+    def to_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class LpaCoreSummary(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in ("degeneracy", "main_core_size", "levels", "simple_edges",
                                               "max_degree", "n_core0", "passes")]
@@ -307,6 +316,8 @@ SIGNATURES = {
                                    ctypes.POINTER(LpaLouvainLevel), ctypes.c_int32, ctypes.POINTER(LpaLouvainSummary)]),
     "lpa_core_numbers": (ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32,
                                         ctypes.POINTER(LpaCoreSummary)]),
+    "lpa_scan": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_int32,
+                                ctypes.POINTER(LpaScanSummary)]),
     "lpa_loopback_create": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(_vp)]),
     "lpa_loopback_abort": (None, [_vp]),
     "lpa_loopback_destroy": (None, [_vp]),

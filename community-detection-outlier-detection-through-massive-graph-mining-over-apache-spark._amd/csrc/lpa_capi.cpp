@@ -1321,6 +1321,32 @@ int lpa_core_numbers(lpa_graph* g, int32_t max_k, int32_t* core_out, int32_t* si
   return core_numbers(g, max_k, core_out, simple_degree_out, out_is_device, summary);
 }
 
+int lpa_scan(lpa_graph* g, double eps, int32_t mu, int32_t* label_out, uint8_t* role_out, int32_t* nsim_out,
+             int32_t* common_out, int32_t out_is_device, lpa_scan_summary* summary) {
+  if (!g) {
+    set_error("null handle");
+    return LPA_EINVAL;
+  }
+  if (!(eps > 0.0 && eps <= 1.0)) {   // NaN fails both
+    set_error("lpa_scan: eps must belong to (0, 1], got %g", eps);
+    return LPA_EINVAL;
+  }
+  if (mu < 1) {
+    set_error("lpa_scan: mu must be at least 1, got %d", mu);
+    return LPA_EINVAL;
+  }
+  if ((!label_out || !role_out) && g->V > 0) {
+    set_error("lpa_scan: null label or role output");
+    return LPA_EINVAL;
+  }
+  if (g->m > 0 && !g->e_src) {
+    set_error("lpa_scan of a distributed job runs on rank 0 (the rank that keeps the edge list)");
+    return LPA_EINVAL;
+  }
+  LPA_HIP(hipSetDevice(g->device));
+  return scan(g, eps, mu, label_out, role_out, nsim_out, common_out, out_is_device, summary);
+}
+
 int lpa_degrees(lpa_graph* g, int32_t* deg_out) {
   if (!g || (!deg_out && g->V > 0)) {
     set_error("null handle or output");

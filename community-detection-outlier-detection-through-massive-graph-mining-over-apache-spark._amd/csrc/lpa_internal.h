@@ -843,6 +843,32 @@ int strongly_connected_components(lpa_graph* g, int32_t max_iter, int32_t* comp_
 int louvain(lpa_graph* g, int32_t max_levels, int32_t max_rounds, int32_t* comm_out, int32_t out_is_device,
             int64_t* size_out, lpa_louvain_level* levels_out, int32_t levels_cap, lpa_louvain_summary* summary);
 
+// The rank-oriented out-lists of the canonical simple undirected graph, as lpa_tc.hip builds and
+// describes them: ek[E] the sorted oriented keys (from << 32 | to), rp[V + 1] / col[E] the CSR
+// with every out-list ascending (slot i of col[] is the oriented edge ek[i]), lists[4 V] the
+// rows of the four forms (form k at lists + k V, rows[k] of them), lmax the longest out-list.
+// carry: ckeys[E] keeps the sorted canonical keys (min << 32 | max) and canon[i] is the index in
+// ckeys of slot i's edge, carried through the second sort.  Every array is a temporary of tmp.
+struct TcLists {
+  int64_t E = 0;
+  u64* ek = nullptr;
+  int64_t* rp = nullptr;
+  int32_t* col = nullptr;
+  int32_t* lists = nullptr;
+  u32 rows[4] = {0, 0, 0, 0};
+  int32_t lmax = 0;
+  u64* ckeys = nullptr;
+  u64* canon = nullptr;
+};
+// d: [V], zeroed by the caller, receives the simple degrees.  One host synchronisation (two
+// with simple_edges').  E == 0: nothing but d is made
+int tc_build(lpa_graph* g, Tmp& tmp, int32_t* d, bool carry, TcLists* t);
+
+// SCAN structural clustering of the canonical simple undirected graph (lpa_scan.hip); the
+// arguments are checked by the caller
+int scan(lpa_graph* g, double eps, int32_t mu, int32_t* label_out, uint8_t* role_out, int32_t* nsim_out,
+         int32_t* common_out, int32_t out_is_device, lpa_scan_summary* summary);
+
 // k-core decomposition of the canonical simple undirected graph (lpa_kcore.hip)
 int core_numbers(lpa_graph* g, int32_t max_k, int32_t* core_out, int32_t* simple_degree_out, int32_t out_is_device,
                  lpa_core_summary* summary);

@@ -34,11 +34,16 @@
 //   its list by a search of the T + 1 scanned offsets in LDS, reads x = col[..] and
 //   binary-searches x in N+(u).  Lanes stay busy whatever the mix of list lengths.
 //
+// Everything up to the row lists is tc_build (declared in lpa_internal.h), which lpa_scan.hip
+// calls too -- there also with carry: the second sort takes every slot's index in the sorted
+// canonical keys along as a payload.  tc_has / tc_pos and the teams' LDS layout are lpa_tc.h.
+//
 // count[] takes 64-bit integer atomic adds (they commute: every interleaving gives the
 // same bits); the apex's share is summed in registers and across the team, one atomic
 // per row.  Every offset and count is 64-bit; a vertex id is 32-bit.
 #include "lpa_device.h"
 #include "lpa_algo.h"
+#include "lpa_tc.h"
 
 namespace lpa {
 
@@ -49,6 +54,10 @@ __global__ __launch_bounds__(256) void k_tc_compact(const u64* __restrict__ keys
   GRID_STRIDE(i, m) {
     if (first[i]) out[pos[i]] = keys[i];
   }
+}
+
+__global__ __launch_bounds__(256) void k_tc_iota(u64* __restrict__ v, int64_t n) {
+  GRID_STRIDE(i, n) v[i] = (u64)i;
 }
 
 // ek: the E simple edges, sorted.  A run of equal min endpoints inside a wave is one
@@ -116,20 +125,6 @@ __global__ __launch_bounds__(256) void k_tc_classify(const int32_t* __restrict__
   if (lane == 0 && lmax > 0) atomicMax(&cnt[4], (u32)lmax);
 }
 
-// is x in the ascending list p[0, n)?
-template <typename P>
-__device__ __forceinline__ bool tc_has(P p, int32_t n, int32_t x) {
-  int32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int32_t mid = (lo + hi) >> 1;
-    const int32_t y = p[mid];
-    if (y == x) return true;
-    if (y < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return false;
-}
-
 // G lanes per row (256 / G rows per block).  Items: the ordered pairs (v, w) of N+(u).
 template <int G>
 __global__ __launch_bounds__(256) void k_tc_group(const int32_t* __restrict__ rows, int64_t nrows,
@@ -164,22 +159,6 @@ __global__ __launch_bounds__(256) void k_tc_group(const int32_t* __restrict__ ro
 #pragma unroll
     for (int off = G / 2; off > 0; off >>= 1) cu += __shfl_xor(cu, off, 64);
     if (act && sub == 0 && cu) atomicAdd(&count[u], cu);
-  }
-}
-
-// LDS of one team, in 8-byte words: rpv[T] (first col[] index of each out-neighbour's
-// list), pre[T + 1] (+ 1 pad: their scanned lengths), nu[cap] (N+(u), LDS forms only)
-template <int T>
-constexpr int64_t tc_team_words(int64_t cap) { return T + (T + 2) / 2 + (cap + 1) / 2; }
-
-template <int T>
-__device__ __forceinline__ void tc_team_sync() {
-  if (T == 256) {
-    __syncthreads();
-  } else {
-    // one wave: its LDS operations complete in order; nothing may move across
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
   }
 }
 
@@ -344,12 +323,65 @@ int launch_team(const int32_t* rows, int64_t nrows, const int64_t* rp, const int
 
 }  // namespace
 
+// d: [V], zeroed by the caller; filled with the simple degrees.  E == 0: no array but d.
+int tc_build(lpa_graph* g, Tmp& tmp, int32_t* d, bool carry, TcLists* t) {
+  hipStream_t s = g->stream;
+  const int64_t V = g->V, m = g->m;
+  SimpleEdges se;
+  LPA_TRY(simple_edges(g, tmp, &se));
+  const int64_t E = t->E = se.E;
+  u64* keys = se.keys;   // [2 m]: the sorted edge keys, then [m, m + E) the simple edges
+  if (E == 0) return LPA_OK;
+  const HalfShifts sh(bits_for((uint64_t)(V - 1)));
+  u64* ek = t->ek = keys + m;
+  hipLaunchKernelGGL(k_tc_compact, dim3(grid_for(m)), dim3(256), 0, s, keys, se.first, se.pos, m, ek);
+  LPA_HIP(hipGetLastError());
+  int32_t* od = nullptr;
+  u32* cnt = nullptr;
+  LPA_TRY(tmp.get(&od, V));
+  LPA_TRY(tmp.get(&t->col, E));
+  LPA_TRY(tmp.get(&t->rp, V + 1));
+  LPA_TRY(tmp.get(&t->lists, 4 * V));
+  LPA_TRY(tmp.get(&cnt, 8));
+  LPA_HIP(hipMemsetAsync(od, 0, sizeof(int32_t) * (size_t)V, s));
+  LPA_HIP(hipMemsetAsync(cnt, 0, sizeof(u32) * 8, s));
+  hipLaunchKernelGGL(k_tc_degrees, dim3(grid_for(E)), dim3(256), 0, s, ek, E, d);
+  if (carry) {
+    // the canonical keys stay (sorted: canonical edge i is ckeys[i]); the payload of slot i is i
+    u64* tvals = nullptr;
+    LPA_TRY(tmp.get(&t->ckeys, E));
+    LPA_TRY(tmp.get(&t->canon, E));
+    LPA_TRY(tmp.get(&tvals, E));
+    LPA_HIP(hipMemcpyAsync(t->ckeys, ek, sizeof(u64) * (size_t)E, hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(k_tc_iota, dim3(grid_for(E)), dim3(256), 0, s, t->canon, E);
+    hipLaunchKernelGGL(k_tc_orient, dim3(grid_for(E)), dim3(256), 0, s, ek, E, d, od);
+    LPA_HIP(hipGetLastError());
+    LPA_TRY(radix_sort_u64_kv(ek, t->canon, keys, tvals, E, sh.both(), 2 * sh.ns, s));
+    tmp.drop(tvals);
+  } else {
+    hipLaunchKernelGGL(k_tc_orient, dim3(grid_for(E)), dim3(256), 0, s, ek, E, d, od);
+    LPA_HIP(hipGetLastError());
+    LPA_TRY(radix_sort_u64(ek, keys, E, sh.both(), 2 * sh.ns, s));
+  }
+  LPA_TRY(key_col(ek, E, t->col, s));
+  LPA_TRY(exclusive_scan_i32_i64(od, t->rp, V, s));
+  hipLaunchKernelGGL(k_tc_classify, dim3(grid_bh(V)), dim3(256), 0, s, od, V, g->tc_short, g->tc_wave, g->tc_lds,
+                     t->lists, cnt);
+  LPA_HIP(hipGetLastError());
+  u32 h[8] = {0};
+  LPA_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, s));
+  LPA_HIP(hipStreamSynchronize(s));
+  for (int k = 0; k < 4; ++k) t->rows[k] = h[k];
+  t->lmax = (int32_t)h[4];
+  return LPA_OK;
+}
+
 // Reads V, m, e_src / e_dst, the stream and the tc_* boundaries of the handle, nothing of
 // the LPA state; every array is a stream-ordered temporary.
 int triangle_count(lpa_graph* g, int64_t* count_out, int64_t* simple_degree_out, int32_t out_is_device,
                    lpa_triangle_summary* summary) {
   hipStream_t s = g->stream;
-  const int64_t V = g->V, m = g->m;
+  const int64_t V = g->V;
   if (summary) *summary = lpa_triangle_summary{0, 0, 0, 0, 0, -1};
   if (V == 0) return LPA_OK;
   Tmp tmp(s);
@@ -359,46 +391,22 @@ int triangle_count(lpa_graph* g, int64_t* count_out, int64_t* simple_degree_out,
   LPA_TRY(tmp.get(&d, V));
   LPA_HIP(hipMemsetAsync(count, 0, sizeof(ull) * (size_t)V, s));
   LPA_HIP(hipMemsetAsync(d, 0, sizeof(int32_t) * (size_t)V, s));
-  SimpleEdges se;
-  LPA_TRY(simple_edges(g, tmp, &se));
-  const int64_t E = se.E;
-  u64* keys = se.keys;   // [2 m]: the sorted edge keys, then [m, m + E) the simple edges
+  TcLists t;
+  LPA_TRY(tc_build(g, tmp, d, false, &t));
+  const int64_t E = t.E;
   if (E > 0) {
-    const HalfShifts sh(bits_for((uint64_t)(V - 1)));
-    u64* ek = keys + m;
-    hipLaunchKernelGGL(k_tc_compact, dim3(grid_for(m)), dim3(256), 0, s, keys, se.first, se.pos, m, ek);
-    LPA_HIP(hipGetLastError());
-    int32_t *od = nullptr, *col = nullptr, *lists = nullptr;
-    int64_t* rp = nullptr;
-    u32* cnt = nullptr;
-    LPA_TRY(tmp.get(&od, V));
-    LPA_TRY(tmp.get(&col, E));
-    LPA_TRY(tmp.get(&rp, V + 1));
-    LPA_TRY(tmp.get(&lists, 4 * V));
-    LPA_TRY(tmp.get(&cnt, 8));
-    LPA_HIP(hipMemsetAsync(od, 0, sizeof(int32_t) * (size_t)V, s));
-    LPA_HIP(hipMemsetAsync(cnt, 0, sizeof(u32) * 8, s));
-    hipLaunchKernelGGL(k_tc_degrees, dim3(grid_for(E)), dim3(256), 0, s, ek, E, d);
-    hipLaunchKernelGGL(k_tc_orient, dim3(grid_for(E)), dim3(256), 0, s, ek, E, d, od);
-    LPA_HIP(hipGetLastError());
-    LPA_TRY(radix_sort_u64(ek, keys, E, sh.both(), 2 * sh.ns, s));
-    LPA_TRY(key_col(ek, E, col, s));
-    LPA_TRY(exclusive_scan_i32_i64(od, rp, V, s));
-    hipLaunchKernelGGL(k_tc_classify, dim3(grid_bh(V)), dim3(256), 0, s, od, V, g->tc_short, g->tc_wave, g->tc_lds,
-                       lists, cnt);
-    LPA_HIP(hipGetLastError());
-    u32 h[8] = {0};
-    LPA_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, s));
-    LPA_HIP(hipStreamSynchronize(s));
-    const int32_t lmax = (int32_t)h[4];
-    if (h[0]) {
-      hipLaunchKernelGGL(k_tc_group<8>, dim3(grid_rows(h[0], 32, 16384)), dim3(256), 0, s, lists, (int64_t)h[0], rp,
-                         col, count);
+    const int32_t* lists = t.lists;
+    const int64_t* rp = t.rp;
+    const int32_t* col = t.col;
+    const int32_t lmax = t.lmax;
+    if (t.rows[0]) {
+      hipLaunchKernelGGL(k_tc_group<8>, dim3(grid_rows(t.rows[0], 32, 16384)), dim3(256), 0, s, lists,
+                         (int64_t)t.rows[0], rp, col, count);
       LPA_HIP(hipGetLastError());
     }
-    LPA_TRY((launch_team<64, true>(lists + V, h[1], rp, col, count, lmax < g->tc_wave ? lmax : g->tc_wave, s)));
-    LPA_TRY((launch_team<256, true>(lists + 2 * V, h[2], rp, col, count, lmax < g->tc_lds ? lmax : g->tc_lds, s)));
-    LPA_TRY((launch_team<256, false>(lists + 3 * V, h[3], rp, col, count, 0, s)));
+    LPA_TRY((launch_team<64, true>(lists + V, t.rows[1], rp, col, count, lmax < g->tc_wave ? lmax : g->tc_wave, s)));
+    LPA_TRY((launch_team<256, true>(lists + 2 * V, t.rows[2], rp, col, count, lmax < g->tc_lds ? lmax : g->tc_lds, s)));
+    LPA_TRY((launch_team<256, false>(lists + 3 * V, t.rows[3], rp, col, count, 0, s)));
   }
   ull h[5] = {0, 0, 0, 0, 0};
   if (summary) {

@@ -41,6 +41,24 @@ def _edge_ptrs(src, dst):
     return s.ctypes.data, d.ctypes.data, int(s.size), 0, (s, d)
 
 
+# role codes of Graph.scan / lpa_scan, by value
+SCAN_ROLES = ("outlier", "hub", "border", "core")
+
+
+def _check_scan(eps, mu, eps_name="eps"):
+    """The argument checks of Graph.scan and GraphFrame.scan, before any device work; returns
+    (float eps, int mu)."""
+    if isinstance(eps, (bool, np.bool_)) or not isinstance(eps, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{eps_name} must be a real number, got {type(eps).__name__}")
+    if not isinstance(mu, (int, np.integer)) or isinstance(mu, (bool, np.bool_)):
+        raise TypeError(f"mu must be an int, got {type(mu).__name__}")
+    if not 0 < eps <= 1:   # NaN fails both
+        raise ValueError(f"{eps_name} must belong to (0, 1], but got {eps}")
+    if mu < 1:
+        raise ValueError(f"mu must be at least 1, but got {mu}")
+    return float(eps), min(int(mu), 2 ** 31 - 1)
+
+
 class PregelNullError(ValueError):
     """An initial (``iteration`` 0) or updated value of Pregel column ``column`` was null at the
     dense vertex ``vertex``: a column holds no null."""
@@ -985,6 +1003,64 @@ class Graph:
         _lib.check(self._lib.lpa_core_numbers(self._handle(), max_k, ptr, deg_ptr, on_dev,
                                               ctypes.byref(summ) if stats else None))
         return (core, deg, summ.to_dict()) if stats else core
+
+    # -- SCAN structural clustering -----------------------------------------------------
+    def scan(self, eps, mu, out=None, stats: bool = False, common: bool = False):
+        """SCAN structural clustering (Xu et al., KDD 2007; lpa_scan, include/lpa.h states the
+        definition) of the canonical simple undirected graph of the input multigraph (self-loops
+        dropped, direction ignored, duplicates collapsed, as ``triangle_count``).  An edge
+        {u, v} with c common neighbours is similar iff ``(c+2)^2 >= eps^2 (d[u]+1) (d[v]+1)`` in
+        binary64; a vertex with ``nsim + 1 >= mu`` similar edges (itself counted) is a core;
+        cores joined over similar edges form a cluster, labelled by its smallest core; a
+        non-core with a similar edge to a core is a border of the smallest such label; every
+        other vertex keeps its own id as label and is a hub (its neighbours carry at least two
+        cluster labels) or an outlier.  ``eps`` in (0, 1], ``mu`` an int >= 1.
+        Returns ``(label, role)``: int32 labels (dense ids) and uint8 roles (0 outlier, 1 hub,
+        2 border, 3 core; ``SCAN_ROLES`` names them), host arrays by default, or with ``label``
+        written into the int32 device tensor ``out`` (this handle's device, ``num_vertices``
+        entries) and every other array a device tensor beside it.  ``stats=True`` appends
+        ``nsim`` (int32: similar edges per vertex) and ``summary`` (a dict of simple_edges,
+        triangles, similar_edges, n_clusters, n_cores, n_borders, n_hubs, n_outliers,
+        largest_cluster, largest_cluster_label).  ``common=True`` appends, last, ``common``
+        (int32, one entry per input edge row): the common neighbours of the row's edge, -1 for
+        a self-loop row or one with an end outside the vertex range.  The result is a function
+        of the vertex count, the edge set, eps and mu alone.  The labels and the LPA state are
+        not touched."""
+        eps, mu = _check_scan(eps, mu)
+        V, m = self.num_vertices, self.num_edges
+        nsim = cmn = None
+        if out is not None and _is_device_tensor(out):
+            import torch
+
+            if out.dtype != torch.int32:
+                raise ValueError(f"out must be int32, got {out.dtype}")
+            if out.device.index != self.device:
+                raise ValueError(f"out must be on cuda:{self.device}, got {out.device}")
+            if out.numel() != V or not out.is_contiguous():
+                raise ValueError(f"out must hold {V} contiguous entries")
+            label, on_dev = out, 1
+            role = torch.empty(V, dtype=torch.uint8, device=out.device)
+            if stats:
+                nsim = torch.empty(V, dtype=torch.int32, device=out.device)
+            if common:
+                cmn = torch.empty(m, dtype=torch.int32, device=out.device)
+            torch.cuda.current_stream(out.device).synchronize()   # the library works on its own stream
+            ptr = lambda x: None if x is None else x.data_ptr()   # noqa: E731
+        elif out is not None:
+            raise ValueError("out must be an int32 device tensor")
+        else:
+            label, on_dev = np.empty(V, dtype=np.int32), 0
+            role = np.empty(V, dtype=np.uint8)
+            if stats:
+                nsim = np.empty(V, dtype=np.int32)
+            if common:
+                cmn = np.empty(m, dtype=np.int32)
+            ptr = lambda x: None if x is None else x.ctypes.data   # noqa: E731
+        summ = _lib.LpaScanSummary()
+        _lib.check(self._lib.lpa_scan(self._handle(), eps, mu, ptr(label), ptr(role), ptr(nsim), ptr(cmn), on_dev,
+                                      ctypes.byref(summ) if stats else None))
+        res = (label, role) + ((nsim, summ.to_dict()) if stats else ()) + ((cmn,) if common else ())
+        return res
 
 
 class Loopback:

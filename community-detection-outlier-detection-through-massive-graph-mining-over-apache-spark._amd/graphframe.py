@@ -32,12 +32,13 @@ import numpy as np
 import pandas as pd
 
 from . import _lib
-from .graph import Graph, PregelNullError
+from .graph import SCAN_ROLES, Graph, PregelNullError, _check_scan
 
 ID, SRC, DST, LABEL = "id", "src", "dst", "label"
 COMPONENT = "component"
 COUNT = "count"
 CORE = "core"
+ROLE, COMMON, SIMILARITY = "role", "common", "similarity"
 BETWEENNESS = "betweenness"
 PAGERANK = "pagerank"
 PAGERANKS = "pageranks"
@@ -1214,6 +1215,53 @@ class GraphFrame:
         out.attrs["core_sizes"] = [int(x) for x in sizes]
         return out
 
+    def scan(self, epsilon: float = 0.7, mu: int = 2) -> pd.DataFrame:
+        """SCAN structural clustering (Xu, Yuruk, Feng, Schweiger, KDD 2007) -- this package's own
+        addition, not a GraphFrames call (like ``louvain`` and ``coreNumber``).  On the canonical
+        simple undirected graph (self-loops dropped, direction ignored, duplicates collapsed, as
+        ``triangleCount``) an edge is similar when the structural similarity of its ends,
+        (common neighbours + 2) / sqrt((d[u] + 1) (d[v] + 1)), is at least ``epsilon``; a vertex
+        with at least ``mu`` similar closed neighbours (itself counted) is a core; cores joined
+        over similar edges form a cluster and similar neighbours of a core are its borders.
+        Every other vertex is a hub, when its neighbours lie in at least two clusters, or an
+        outlier.  Returns the vertex rows sorted by id, all columns kept, + ``label`` (int64: the
+        smallest core of the vertex's cluster, a hub's or outlier's own id -- original ids for
+        integral ids, dense indices in ascending id order otherwise, as ``labelPropagation``'s
+        ``label``; ``outlierScores(labels=...)`` takes the result) + ``role`` (str: ``core``,
+        ``border``, ``hub`` or ``outlier``).  ``.attrs`` holds the summary: simple_edges,
+        triangles, similar_edges, n_clusters, n_cores, n_borders, n_hubs, n_outliers,
+        largest_cluster and largest_cluster_label (as ``label``; None without a cluster)."""
+        epsilon, mu = _check_scan(epsilon, mu, "epsilon")
+        ig = self._indexed()
+        dense, role, _, summ = self._gpu_graph().scan(epsilon, mu, stats=True)
+        names = np.array(SCAN_ROLES, dtype=object)
+        out = _attach(self._v, ig, {LABEL: _label_values(ig, dense), ROLE: names[role]})
+        big = summ["largest_cluster_label"]
+        summ["largest_cluster_label"] = None if big < 0 else int(_label_values(ig, np.array([big]))[0])
+        out.attrs.update(summ)
+        return out
+
+    def structuralSimilarity(self) -> pd.DataFrame:
+        """The per-edge quantities ``scan`` decides by -- this package's own addition.  Returns the
+        edge rows whose two ends are vertex ids (the rows the graph keeps), all columns kept, in
+        input order, + ``common`` (int64: the common neighbours of the row's ends in the canonical
+        simple undirected graph) + ``similarity`` (float64: (common + 2) / sqrt((d[src] + 1)
+        (d[dst] + 1)), computed on the host from ``common`` and the simple degrees, for reading
+        only: ``scan`` decides by the root-free integer-exact test).  Rows of one edge, in either
+        direction, carry the same values.  A self-loop row is no edge of the simple graph: it
+        shows ``common`` -1 and ``similarity`` NaN."""
+        ig = self._indexed()
+        g = self._gpu_graph()
+        common = g.scan(1.0, 1, common=True)[2].astype(np.int64)
+        deg = g.core_numbers(max_k=0, stats=True)[1].astype(np.float64)
+        sim = np.full(common.shape, np.nan, np.float64)
+        ok = common >= 0
+        sim[ok] = (common[ok] + 2.0) / np.sqrt((deg[ig.src[ok]] + 1.0) * (deg[ig.dst[ok]] + 1.0))
+        out = self._e[ig.kept].reset_index(drop=True) if ig.kept is not None else self._e.reset_index(drop=True)
+        out[COMMON] = common
+        out[SIMILARITY] = sim
+        return out
+
     def _bc_sources(self, sources, k, seed):
         """The dense ids of the sources of ``betweennessCentrality`` (None: every vertex); every
         argument error is raised here, before any device work."""
@@ -1712,6 +1760,26 @@ def core_number(vertices: pd.DataFrame, edges: pd.DataFrame, device: int = 0) ->
     gf = GraphFrame(vertices, edges, device=device)
     try:
         return gf.coreNumber()
+    finally:
+        gf.close()
+
+
+def scan(vertices: pd.DataFrame, edges: pd.DataFrame, epsilon: float = 0.7, mu: int = 2,
+         device: int = 0) -> pd.DataFrame:
+    """Function form of ``GraphFrame(vertices, edges).scan(epsilon, mu)``."""
+    _check_scan(epsilon, mu, "epsilon")
+    gf = GraphFrame(vertices, edges, device=device)
+    try:
+        return gf.scan(epsilon, mu)
+    finally:
+        gf.close()
+
+
+def structural_similarity(vertices: pd.DataFrame, edges: pd.DataFrame, device: int = 0) -> pd.DataFrame:
+    """Function form of ``GraphFrame(vertices, edges).structuralSimilarity()``."""
+    gf = GraphFrame(vertices, edges, device=device)
+    try:
+        return gf.structuralSimilarity()
     finally:
         gf.close()
 

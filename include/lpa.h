@@ -747,6 +747,64 @@ int lpa_core_numbers(lpa_graph* g, int32_t max_k /* INT32_MAX: no cap */, int32_
                      lpa_core_summary* summary /* nullable */);
 
 /*
+ * SCAN structural clustering (Xu, Yuruk, Feng, Schweiger: "SCAN: A Structural Clustering
+ * Algorithm for Networks", KDD 2007): clusters, and the two kinds of vertex that belong to none,
+ * hubs and outliers.  This is the package's own call (GraphFrames has none).  It works on the
+ * canonical simple undirected graph of the input multigraph, exactly lpa_triangle_count's and
+ * lpa_core_numbers': self-loops dropped, direction ignored, duplicates collapsed, an edge with an
+ * end outside [0, V) is no edge.
+ *   d[v]      the simple degree; c(u,v) the number of common neighbours of an edge {u,v}.  With
+ *             closed neighbourhoods the structural similarity is
+ *             sigma(u,v) = (c + 2) / sqrt((d[u] + 1) (d[v] + 1)).
+ *   similar   an edge is similar iff, in IEEE binary64, evaluated exactly as written, every
+ *             product rounded once, no fused multiply-add:
+ *               (double)(c+2) * (double)(c+2) >= (eps * eps) * ((double)(d[u]+1) * (double)(d[v]+1))
+ *             (sigma >= eps without the root and the division; numpy performs the same
+ *             operations, so the decision is reproducible bit for bit, equality included).
+ *   core      nsim[v] is the number of similar edges at v; v is a core iff nsim[v] + 1 >= mu
+ *             (the vertex counts itself, as in the paper).
+ *   cluster   cores are joined over similar edges whose two ends are both cores; a cluster's
+ *             label is the smallest dense id among its CORES.
+ *   border    a non-core with at least one similar edge to a core; it takes the SMALLEST label
+ *             among those cores' clusters (the deterministic replacement for the paper's visit
+ *             order).
+ *   the rest  are non-members and keep label[v] = v (no collision: a cluster label is a core's
+ *             id).  A non-member is a hub iff its neighbours, over all simple edges, carry at
+ *             least two different cluster labels among the members; otherwise an outlier.
+ *   role[v]   0 outlier, 1 hub, 2 border, 3 core.
+ * label_out (int32) and role_out (uint8), V entries each, are required; nsim_out (int32, V
+ * entries) is nullable.  common_out (nullable, int32, m entries: one per INPUT EDGE ROW i) is
+ * c of row i's edge, or -1 where the row is a self-loop or has an end outside [0, V).  All are
+ * host memory unless out_is_device; summary is nullable.  The result is a function of
+ * (V, edge set, eps, mu) alone: identical across runs, edge orders, edge directions, handles,
+ * devices and kernel schedules (every accumulation is an integer atomic; the only
+ * floating-point work is the three products of the similarity test).
+ * LPA_EINVAL for a null handle, for eps NaN or outside (0, 1], for mu < 1 and for a null
+ * label_out or role_out with V > 0.  V == 0: success, nothing written, the summary all zeros
+ * (largest_cluster_label -1).  The call blocks until the work is done.  All working memory is
+ * stream-ordered temporaries, the labels and every other piece of lpa_step's state are neither
+ * read nor written, nothing is kept on the handle.  The LPA_TC_* boundaries of
+ * lpa_triangle_count choose the row forms of the common-neighbour pass.  On a distributed job
+ * (nranks > 1) only rank 0 keeps the edge list this needs; the other ranks return LPA_EINVAL.
+ * Since ABI 23.
+ */
+typedef struct lpa_scan_summary {
+  int64_t simple_edges;          /* as lpa_triangle_summary                                   */
+  int64_t triangles;             /* as lpa_triangle_summary.n_triangles                       */
+  int64_t similar_edges;         /* simple edges that pass the test                           */
+  int64_t n_clusters;
+  int64_t n_cores;
+  int64_t n_borders;
+  int64_t n_hubs;
+  int64_t n_outliers;
+  int64_t largest_cluster;       /* members (cores and borders) of the largest cluster; 0 if none */
+  int64_t largest_cluster_label; /* its label, the smallest among equals; -1 if none          */
+} lpa_scan_summary;              /* 80 bytes */
+int lpa_scan(lpa_graph* g, double eps, int32_t mu, int32_t* label_out, uint8_t* role_out,
+             int32_t* nsim_out /* nullable */, int32_t* common_out /* nullable, m entries */,
+             int32_t out_is_device, lpa_scan_summary* summary /* nullable */);
+
+/*
  * Motif finding (GraphFrames GraphFrame.find(pattern)) over the DIRECTED input MULTIGRAPH.  The
  * caller has parsed the pattern into n_vars vertex variables and n_terms terms; a term is an
  * edge src_var -> dst_var, negated or not.  A result row is one assignment of vertices to the
@@ -1017,8 +1075,9 @@ int lpa_degrees(lpa_graph* g, int32_t* deg_out);
  *         lpa_motif_result_destroy.
  * ABI 20: lpa_aggregate_messages.
  * ABI 21: lpa_pregel.
- * ABI 22: lpa_betweenness. */
-#define LPA_ABI_VERSION 22
+ * ABI 22: lpa_betweenness.
+ * ABI 23: lpa_scan. */
+#define LPA_ABI_VERSION 23
 int lpa_abi_version(void);
 int lpa_graph_get_info(const lpa_graph* g, lpa_graph_info* info);
 int lpa_graph_get_info_sized(const lpa_graph* g, lpa_graph_info* info, int64_t info_size);
